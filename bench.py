@@ -21,10 +21,14 @@ Hankel matrix loses positive definiteness -- the reference does the same, SURVEY
 kernel stops computing for a poisoned replicate, so counting B x T would credit skipped work.  The nominal B x T rate
 is reported next to it as `nominal_value`.
 
-Beside the contract's fields the line carries (rank 0, N = 1 only): `cpu_baseline` (the oracle's C port on the host
-cores, with BASELINE.json's "max |moment err|" per quantity and the first-NaN agreement), `end_to_end_ms` (the
-reference-shaped Python API moment_filter_cms on the same workload, host pointers in and out) and `other_workloads`
-(short runs of BASELINE configs 3, 4 and 5).
+A plain run sets up, warms up, times --steps passes and prints the line (with the `roofline` object, computed from this
+run's HIP-event times and the committed counters under profiles/).  With --full the line also carries (rank 0, N = 1
+only): `cpu_baseline` (the oracle's C port on the host cores, with BASELINE.json's "max |moment err|" per quantity and the
+first-NaN agreement), `end_to_end_ms` (the reference-shaped Python API moment_filter_cms on the same workload, host
+pointers in and out) and `other_workloads` (short runs of BASELINE configs 3, 4 and 5).
+
+--dump-outputs DIR writes what the last timed pass computed (dump_outputs below); the inputs are seeded, so two builds
+run with the same arguments can be compared file by file.
 
 Multi-rank runs: exit status 3 (mfs_amd.dist.EXIT_RCCL_FAILED) and `nll_allgather_ok: false` when the NLL all-gather did
 not go through RCCL, unless --allow-host-gather is given; the fallback gather is never inside the timed region.
@@ -76,7 +80,7 @@ WORKLOADS = {
     'prey_predator_N5_T500_B512_central_tme_normal2': ('prey', 5, 500, 512, 'central', 'tme_normal_2'),
 }
 DEFAULT_WORKLOAD = 'benes_bernoulli_N15_T1000_B4096_central_tme3'
-# (workload, B override, label): short runs reported under `other_workloads` by the default single-GPU run
+# (workload, B override, label): short runs reported under `other_workloads` by a single-GPU --full run
 OTHER_WORKLOADS = [
     ('benes_bernoulli_N7_T100_B4096_central_tme3', 0, 'config1_size_B4096'),
     # config 2 in the other two representations (with the divergence counts) and with the Normal closure
@@ -109,10 +113,14 @@ def parse_args():
     p.add_argument('--T', type=int, default=0, help='override time steps')
     p.add_argument('--chunk', type=int, default=0, help='time steps per kernel launch (0 = whole T in one launch)')
     p.add_argument('--no-moments', action='store_true', help='NLL only: do not stream the (B, T, 2N) moments out')
+    p.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                   help='one GPU: write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)')
+    p.add_argument('--full', action='store_true',
+                   help='also run what the headline does not need: cpu_baseline, end_to_end and other_workloads')
     p.add_argument('--cpu-seconds', type=float, default=12., help='target wall time of the cpu_baseline sample')
-    p.add_argument('--no-cpu-baseline', action='store_true')
-    p.add_argument('--no-end-to-end', action='store_true', help='skip the reference-shaped host API timing')
-    p.add_argument('--no-other-workloads', action='store_true', help='skip the short runs of configs 3 / 4 / 5')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the cpu_baseline')
+    p.add_argument('--no-end-to-end', action='store_true', help='--full without the reference-shaped host API timing')
+    p.add_argument('--no-other-workloads', action='store_true', help='--full without the short runs of configs 3 / 4 / 5')
     p.add_argument('--extra-kernels', action='store_true',
                    help='run only the gradient and characteristic-function entries of `other_workloads` and print them '
                         '(what tools/profile.sh puts under rocprofv3 for those two kernels)')
@@ -454,6 +462,57 @@ def summarise(w, res, steps, world, want_moments, live_total=None):
             'hbm_gbs': algo / (kern_ms * 1e-3) / 1e9}
 
 
+DUMP_BYTES = 60_000_000     # --dump-outputs: stays under 64 MB with the .npy headers
+
+
+def device_rows(buf, row_shape, idx):
+    """Rows `idx` of a float64 device array of shape (B, *row_shape), one D2H copy per row."""
+    import ctypes as C
+    from mfs_amd import _lib
+    row = int(np.prod(row_shape)) * 8
+    out = np.empty((len(idx),) + tuple(row_shape))
+    for k, i in enumerate(int(i) for i in idx):
+        assert 0 <= i and (i + 1) * row <= buf.nbytes
+        _lib.check(_lib.lib().mfs_memcpy_d2h(_lib.ptr(out[k]), C.c_void_p(buf.ptr.value + i * row), row, None))
+    return out
+
+
+def dump_outputs(w, res, outdir):
+    """--dump-outputs: what a caller of the plan receives from the last timed pass, as float64 .npy files: `first_nan`
+    (first step whose outputs are non-finite, -1: none) and `nell` for every replicate, and the whole trajectories of
+    moments, means and scales for a fixed, seeded sample of replicates (`replicates`), as many as fit in DUMP_BYTES --
+    chosen from B and the shapes alone, so that every build dumps the same rows.  A poisoned replicate's outputs are NaN
+    from its first_nan step on; those values, and its NLL, are written as 0, so that every file is finite and compares
+    value by value, and first_nan says which entries they are."""
+    os.makedirs(outdir, exist_ok=True)
+    B, T = w.B, w.T
+    dims = 2 if isinstance(w, WorkloadND) else 1
+    per_step = {}
+    if w.d_mom is not None:
+        per_step['moments'] = (w.d_mom, (T, w.z))
+    if w.mode != 'raw':                      # the kernels write the means in central and scaled mode only ...
+        per_step['means'] = (w.d_means, (T, dims) if dims > 1 else (T,))
+    if w.mode == 'scaled':                   # ... and the scales in scaled mode only
+        per_step['scales'] = (w.d_scales, (T, dims) if dims > 1 else (T,))
+    row = 8 * (1 + sum(int(np.prod(shape)) for _, shape in per_step.values()))
+    n = int(max(0, min(B, (DUMP_BYTES - 2 * 8 * B) // row)))
+    idx = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    first_nan = res['first_nan']
+    poisoned = first_nan >= 0
+    out = {'first_nan': first_nan.astype(np.float64), 'replicates': idx.astype(np.float64),
+           'nell': np.where(poisoned, 0., res['nell'])}
+    after = np.arange(T)[None, :] >= np.where(poisoned[idx], first_nan[idx], T)[:, None]     # (n, T)
+    for name, (buf, shape) in per_step.items():
+        a = device_rows(buf, shape, idx)
+        a[after] = 0.
+        out[name] = a
+    bad = [name for name, a in out.items() if not np.isfinite(a).all()]
+    if bad:     # include/mfs_hip.h: no output before a replicate's first_nan step is non-finite
+        raise RuntimeError(f'--dump-outputs: non-finite values before first_nan in {bad}')
+    for name, a in out.items():
+        np.save(os.path.join(outdir, f'{name}.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher: one child process per GPU, this process only supervises.  It must not
@@ -526,6 +585,8 @@ def main():
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    if args.dump_outputs and max(args.gpus, world) > 1:
+        sys.exit('bench.py: --dump-outputs writes the outputs of a single process: run it with --gpus 1')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))         # launcher: nothing below runs in this process
     if world != args.gpus:
@@ -555,6 +616,8 @@ def main():
 
     w = make_workload(args.workload, args.B, args.T, rank, device)
     res = timed_passes(w, comm, args.steps, args.warmup, want_moments, args.chunk)
+    if args.dump_outputs:
+        dump_outputs(w, res, args.dump_outputs)
     live_total = comm.sum_over_ranks(res['live_steps'])
     alive_total = comm.sum_over_ranks(res['alive'])
     gather_ok = all(comm._allgather_obj(bool(res['gather_matches']))) and not comm.degraded
@@ -601,7 +664,7 @@ def main():
             'target_1e6_steps_per_s_met': bool(s['value'] >= 1e6 * world),
             'roofline': roofline,
         }
-        if world == 1:
+        if world == 1 and args.full:
             if not args.no_cpu_baseline:
                 try:
                     out['cpu_baseline'] = (cpu_baseline_nd(args, w, res) if isinstance(w, WorkloadND)
@@ -611,7 +674,7 @@ def main():
             if not args.no_end_to_end:
                 out.update(end_to_end(w))
         w.release()
-        if world == 1 and not args.no_other_workloads and args.workload == DEFAULT_WORKLOAD and w.full_size:
+        if world == 1 and args.full and not args.no_other_workloads and args.workload == DEFAULT_WORKLOAD and w.full_size:
             out['other_workloads'] = other_workloads(comm, device)
         print(json.dumps(out), flush=True)
     else:
