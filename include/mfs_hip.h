@@ -312,6 +312,68 @@ int mfs_plan_nd_destroy(mfs_plan_nd* plan);
 int mfs_plan_nd_geometry(const mfs_plan_nd* plan, int* threads_per_filter, int* grid, int* lds_bytes_per_block);
 
 /*
+ * ---- N-D moment filter for three-dimensional states (d = 3), host pointers ----------------------------------------
+ * The same three filters (mfs/multi_dims/filtering.py:33-344) for d = 3 (Lorenz-63, three-species Lotka--Volterra, 3-D OU),
+ * on a kernel of its own (mfs_amd/csrc/filternd3_kernel.hpp).  Gram size s = C(N + 2, 3), z = C(2N + 2, 3) moments
+ * (|n| <= 2N - 1), s^3 tensor nodes; MFS_ND3_MIN_N <= N <= MFS_ND3_MAX_N (s = 4, 10, 20; z = 20, 56, 120).
+ *
+ * mfs_model_nd3.coef is [MFS_ND3_ROWS][D][D][D] (or [B][MFS_ND3_ROWS][D][D][D] when coef_batched), D = extent, entry
+ * [row][a][b][c] the coefficient of x0^a x1^b x2^c:
+ *   MFS_ND_TRANS_OPERATOR: rows 0..33 the operator table Q_kappa, 1 <= |kappa| <= 4 (TME order <= 2), in graded-lex kappa
+ *     order (0,0,1),(0,1,0),(1,0,0),(0,0,2),(0,1,1),(0,2,0),(1,0,1),(1,1,0),(2,0,0),(0,0,3),... -- the row of kappa is its
+ *     position in the graded-lex multi-index table minus one; zeros where the model has no term.  Rows 34..36: the
+ *     conditional variances of X'_0, X'_1, X'_2 (scaled mode).  Conditional mean_k = x_k + Q_{e_k}.
+ *   MFS_ND_TRANS_GAUSSIAN: rows 0..8 = mu_0, mu_1, mu_2, S_00, S_01, S_02, S_11, S_12, S_22 of X' | x ~ N(mu(x), S(x))
+ *     (Euler--Maruyama, TME-normal, exact linear-Gaussian steps); the other rows are ignored.
+ * Likelihood: a product of up to MFS_ND3_MAX_FACTORS factors, each a function of one state component (fac_component 0..2) and
+ * one measurement column (fac_ycol < ny <= 3); kinds Bernoulli-logistic, Poisson-softplus, Gaussian (no joint factors).
+ *
+ *   multi_indices  [z][3] int32, the graded-lex table (checked);  inds [4][s][s] int32, the Gram / Hankel gather tables (checked)
+ *   m0 [z] or [B][z]; mean0, scale0 [3] or [B][3]; ys [B][T][ny]
+ *   out_moments [B][T][z]; out_means [B][T][3] (central, scaled); out_scales [B][T][3] (scaled); out_nell [B]; out_first_nan [B]
+ * A replicate whose moment matrix is not positive definite is NaN-poisoned from that step on, and only that replicate.
+ */
+#define MFS_ND3_MIN_N 2
+#define MFS_ND3_MAX_N 4
+#define MFS_ND3_TERMS 34      /* kappa terms with 1 <= |kappa| <= 4 in three variables */
+#define MFS_ND3_ROWS 37       /* coefficient blocks: MFS_ND3_TERMS operator terms + 3 variance rows */
+#define MFS_ND3_GAUSS_TERMS 9 /* mu_0..2 and the 6 covariance polynomials */
+#define MFS_ND3_MAX_EXTENT 6  /* per-variable extent (degree + 1) of the coefficient blocks */
+#define MFS_ND3_MAX_FACTORS 3
+typedef struct mfs_model_nd3 {
+    int32_t trans_kind;    /* MFS_ND_TRANS_* */
+    int32_t n_terms;       /* MFS_ND3_TERMS (operator) or MFS_ND3_GAUSS_TERMS (Gaussian) */
+    int32_t extent;        /* D <= MFS_ND3_MAX_EXTENT */
+    int32_t n_factors;     /* 1 .. MFS_ND3_MAX_FACTORS */
+    int32_t ny;            /* measurement columns per step (1 .. 3) */
+    int32_t fac_kind[MFS_ND3_MAX_FACTORS];      /* MFS_LIK_* (not MFS_LIK_BEARING_GAUSSIAN) */
+    int32_t fac_component[MFS_ND3_MAX_FACTORS]; /* 0 .. 2 */
+    int32_t fac_ycol[MFS_ND3_MAX_FACTORS];      /* < ny */
+    int32_t fac_n_par[MFS_ND3_MAX_FACTORS];     /* <= MFS_MAX_LIK */
+    int32_t coef_batched;
+    int32_t lik_batched;
+    const double* coef;    /* [MFS_ND3_ROWS][D][D][D] or [B][MFS_ND3_ROWS][D][D][D] */
+    const double* lik;     /* [n_factors][MFS_MAX_LIK] or [B][n_factors][MFS_MAX_LIK], unused entries 0 */
+} mfs_model_nd3;
+
+int mfs_filter_nd3(const mfs_model_nd3* model, int mode, int N, int T, int B, int z, const int32_t* multi_indices,
+                   const int32_t* inds, const double* m0, int m0_batched, const double* mean0, const double* scale0,
+                   const double* ys, int stable, double* out_moments, double* out_means, double* out_scales,
+                   double* out_nell, int32_t* out_first_nan, int device, void* stream);
+
+/* d = 3 plan, device pointers: as mfs_plan_nd (tables uploaded at create, run() only enqueues the kernel on `stream`;
+ * d_out_moments, d_out_means, d_out_scales, d_out_first_nan may be NULL).  mfs_filter_nd3 runs the same launch. */
+typedef struct mfs_plan_nd3 mfs_plan_nd3;
+
+int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* model /* host pointers inside */, int mode, int N,
+                        int T, int B, int z, const int32_t* multi_indices, const int32_t* inds, int stable, int device);
+int mfs_plan_nd3_run(mfs_plan_nd3* plan, const double* d_m0, int m0_batched, const double* d_mean0,
+                     const double* d_scale0, const double* d_ys, double* d_out_moments, double* d_out_means,
+                     double* d_out_scales, double* d_out_nell, int32_t* d_out_first_nan, void* stream);
+int mfs_plan_nd3_destroy(mfs_plan_nd3* plan);
+int mfs_plan_nd3_geometry(const mfs_plan_nd3* plan, int* threads_per_filter, int* grid, int* lds_bytes_per_block);
+
+/*
  * ---- multi-GPU: one process per GPU, replicates sharded, NLL all-gather over RCCL / xGMI -----------------------
  * The reference has no multi-device code (its Monte-Carlo runs are separate OS processes,
  * dardel/run_benes_bernoulli_mf.sh:26-31); replicates share nothing, so the data path needs no collective and the

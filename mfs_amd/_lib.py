@@ -35,6 +35,14 @@ class MfsModelNd(C.Structure):
                 ('coef_batched', C.c_int32), ('lik_batched', C.c_int32), ('coef', c_double_p), ('lik', c_double_p)]
 
 
+class MfsModelNd3(C.Structure):
+    """struct mfs_model_nd3 (include/mfs_hip.h): the d = 3 model descriptor."""
+    _fields_ = [('trans_kind', C.c_int32), ('n_terms', C.c_int32), ('extent', C.c_int32), ('n_factors', C.c_int32),
+                ('ny', C.c_int32), ('fac_kind', C.c_int32 * 3), ('fac_component', C.c_int32 * 3), ('fac_ycol', C.c_int32 * 3),
+                ('fac_n_par', C.c_int32 * 3), ('coef_batched', C.c_int32), ('lik_batched', C.c_int32), ('coef', c_double_p),
+                ('lik', c_double_p)]
+
+
 ND_TERMS = 14          # kappa terms with |kappa| <= 4 (TME order <= 2): the 16-row table layout
 ND_ROWS = 16
 ND_TERMS_MAX = 27      # ... |kappa| <= 6 (TME order 3): the 29-row layout
@@ -47,6 +55,15 @@ MAX_LIK = 4
 ABI_VERSION = 2
 # derivative multi-indices kappa, 1 <= |kappa| <= 6, graded-lex (the order of mfs_model_nd.coef rows; the first 14 are |kappa| <= 4)
 ND_KAPPAS = [(a, s - a) for s in range(1, 7) for a in range(s + 1)]
+
+# d = 3 (mfs_model_nd3): N range, 34 operator terms (|kappa| <= 4) + 3 variance rows, 9 Normal-closure polynomials
+ND3_MIN_N, ND3_MAX_N = 2, 4
+ND3_TERMS, ND3_ROWS, ND3_GAUSS_TERMS = 34, 37, 9
+ND3_MAX_EXTENT = 6
+ND3_MAX_FACTORS = 3
+# derivative multi-indices kappa, 1 <= |kappa| <= 4, in the graded-lex order of the multi-index tables (each degree in ascending
+# tuple order): the order of the operator rows of mfs_model_nd3.coef, the kernel's nd3_kappa_row
+ND3_KAPPAS = [(a, b, s - a - b) for s in range(1, 5) for a in range(s + 1) for b in range(s - a + 1)]
 
 
 def nd_table_rows(n_terms: int) -> int:
@@ -102,6 +119,12 @@ _SIGNATURES = [
     ('mfs_plan_nd_run', _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ('mfs_plan_nd_destroy', _i, [_vp]),
     ('mfs_plan_nd_geometry', _i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ('mfs_filter_nd3', _i, [C.POINTER(MfsModelNd3), _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i,
+                            _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ('mfs_plan_nd3_create', _i, [_vpp, C.POINTER(MfsModelNd3), _i, _i, _i, _i, _i, _vp, _vp, _i, _i]),
+    ('mfs_plan_nd3_run', _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ('mfs_plan_nd3_destroy', _i, [_vp]),
+    ('mfs_plan_nd3_geometry', _i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ('mfs_elementary', _i, [_i, _i, _vp, _vp, _i]),
     ('mfs_comm_unique_id', _i, [_vp]),
     ('mfs_comm_init', _i, [_vpp, _vp, _i, _i, _i]),

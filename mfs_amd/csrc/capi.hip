@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "filternd_kernel.hpp"
+#include "filternd3_kernel.hpp"
 #include "filter1d_grad.hpp"
 #include "pool.hpp"
 
@@ -29,6 +30,9 @@ Cf1dLaunch g_cf[MFS_MAX_N + 1][4];
 using FilterNdLaunch = hipError_t (*)(const FilterNdArgs&, int grid, hipStream_t);
 struct NdEntry { FilterNdLaunch launch, launch_gauss, launch_hi, launch_joint; int S, Z, lds_bytes, carry_doubles; };
 extern NdEntry g_nd_table[8];  // filternd_inst.hip
+using FilterNd3Launch = hipError_t (*)(const FilterNd3Args&, int grid, hipStream_t);
+struct Nd3Entry { FilterNd3Launch launch, launch_gauss; int S, Z, lds_bytes; };
+extern Nd3Entry g_nd3_table[MFS_ND3_MAX_N + 1];  // filternd3_inst.hip
 hipError_t launch_elementary(int which, int n, const double* d_x, double* d_out, hipStream_t s);
 extern Filter1dGradLaunch g_grad_table[17][5];  // filter1d_grad_inst.hip: [N <= 16][P <= 4]
 }
@@ -953,6 +957,218 @@ extern "C" int mfs_filter_nd(const mfs_model_nd* model, int mode, int N, int T, 
     if (e == hipSuccess) e = (es != hipSuccess) ? es : ec;
     if (rc != MFS_OK) return rc;
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_nd: %s", hipGetErrorString(e));
+    return MFS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// N-D filter, d = 3
+// ---------------------------------------------------------------------------------------------------------------
+struct mfs_plan_nd3 {
+    int mode, N, T, B, stable, device, trans_kind, ny;
+    mfs::FilterNd3Args args;  // model part filled at create (device pointers), data pointers per run
+    double* d_coef = nullptr;
+    double* d_lik = nullptr;
+    int32_t* d_inds = nullptr;
+};
+
+static void destroy_plan_nd3(mfs_plan_nd3* p, bool quiesced) {
+    hipSetDevice(p->device);
+    if (!quiesced) hipDeviceSynchronize();
+    mfs::BlockPool<false>& pool = mfs::device_state(p->device).device;
+    pool.release(p->d_coef); pool.release(p->d_lik); pool.release(p->d_inds);
+    delete p;
+}
+
+extern "C" int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* model, int mode, int N, int T, int B, int z,
+                                   const int32_t* multi_indices, const int32_t* inds, int stable, int device) {
+    if (!plan) return fail(MFS_EINVAL, "plan is NULL");
+    *plan = nullptr;
+    if (!model) return fail(MFS_EINVAL, "model is NULL");
+    if (mode != MFS_MODE_RAW && mode != MFS_MODE_CENTRAL && mode != MFS_MODE_SCALED)
+        return fail(MFS_EINVAL, "unknown moment mode %d", mode);
+    if (N < MFS_ND3_MIN_N || N > MFS_ND3_MAX_N)
+        return fail(MFS_EUNSUPPORTED, "N = %d outside [%d, %d] for d = 3", N, MFS_ND3_MIN_N, MFS_ND3_MAX_N);
+    const mfs::Nd3Entry& ke = mfs::g_nd3_table[N];
+    if (!ke.launch) return fail(MFS_EUNSUPPORTED, "no d = 3 kernel compiled for N = %d", N);
+    if (model->trans_kind != MFS_ND_TRANS_OPERATOR && model->trans_kind != MFS_ND_TRANS_GAUSSIAN)
+        return fail(MFS_EINVAL, "unknown N-D transition kind %d", model->trans_kind);
+    if (model->n_terms != (model->trans_kind == MFS_ND_TRANS_GAUSSIAN ? MFS_ND3_GAUSS_TERMS : MFS_ND3_TERMS))
+        return fail(MFS_EINVAL, "n_terms %d: the d = 3 tables carry %d operator terms or %d Normal-closure polynomials",
+                    model->n_terms, MFS_ND3_TERMS, MFS_ND3_GAUSS_TERMS);
+    if (z != ke.Z) return fail(MFS_EINVAL, "The size of multi_indices %d must match that of the moments %d.", z, ke.Z);
+    if (model->extent < 1 || model->extent > MFS_ND3_MAX_EXTENT)
+        return fail(MFS_EUNSUPPORTED, "coefficient extent %d outside [1, %d]", model->extent, MFS_ND3_MAX_EXTENT);
+    if (model->n_factors < 1 || model->n_factors > MFS_ND3_MAX_FACTORS)
+        return fail(MFS_EINVAL, "n_factors %d outside [1, %d]", model->n_factors, MFS_ND3_MAX_FACTORS);
+    if (model->ny < 1 || model->ny > 3) return fail(MFS_EINVAL, "ny %d outside [1, 3]", model->ny);
+    for (int f = 0; f < model->n_factors; ++f) {
+        if (model->fac_kind[f] == MFS_LIK_BEARING_GAUSSIAN)
+            return fail(MFS_EUNSUPPORTED, "a likelihood of several state components is not supported at d = 3");
+        if (model->fac_kind[f] < 0 || model->fac_kind[f] > MFS_LIK_GAUSSIAN || model->fac_n_par[f] < 1 ||
+            model->fac_n_par[f] > MFS_MAX_LIK || model->fac_component[f] < 0 || model->fac_component[f] > 2 ||
+            model->fac_ycol[f] < 0 || model->fac_ycol[f] >= model->ny)
+            return fail(MFS_EINVAL, "bad description of likelihood factor %d", f);
+    }
+    if (T < 0 || B < 0) return fail(MFS_EINVAL, "negative T or B");
+    if (!multi_indices || !inds || !model->coef || !model->lik) return fail(MFS_EINVAL, "NULL buffer");
+    const int S = ke.S;
+    // the kernel derives a moment's multi-index from its position: insist on the graded-lex tables
+    for (int zi = 0; zi < z; ++zi)
+        for (int k = 0; k < 3; ++k)
+            if (multi_indices[3 * zi + k] != mfs::nd3_exp(zi, k))
+                return fail(MFS_EINVAL, "multi_indices is not the graded-lexicographic table of order 2N-1");
+    for (int t = 0; t < 4; ++t)
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j) {
+                const int want = mfs::nd3_index(mfs::nd3_exp(i, 0) + mfs::nd3_exp(j, 0) + (t == 1),
+                                                mfs::nd3_exp(i, 1) + mfs::nd3_exp(j, 1) + (t == 2),
+                                                mfs::nd3_exp(i, 2) + mfs::nd3_exp(j, 2) + (t == 3));
+                if (inds[((size_t)t * S + i) * S + j] != want)
+                    return fail(MFS_EUNSUPPORTED, "inds[%d][%d][%d] = %d is not the graded-lexicographic Gram / Hankel table (expected %d)",
+                                t, i, j, inds[((size_t)t * S + i) * S + j], want);
+            }
+    HIP_TRY(hipSetDevice(device));
+    mfs_plan_nd3* p = new (std::nothrow) mfs_plan_nd3();
+    if (!p) return fail(MFS_ENOMEM, "out of host memory");
+    p->mode = mode; p->N = N; p->T = T; p->B = B; p->stable = stable; p->device = device;
+    p->trans_kind = model->trans_kind; p->ny = model->ny;
+    const size_t D = (size_t)model->extent, DDD = D * D * D;
+    const size_t ncoef = (size_t)(model->coef_batched ? B : 1) * MFS_ND3_ROWS * DDD;
+    const size_t nlik = (size_t)(model->lik_batched ? B : 1) * model->n_factors * MFS_MAX_LIK;
+    const size_t ninds = (size_t)4 * S * S;
+    mfs::BlockPool<false>& pool = mfs::device_state(device).device;
+    hipError_t e = pool.acquire((void**)&p->d_coef, ncoef * 8);
+    if (e == hipSuccess) e = pool.acquire((void**)&p->d_lik, nlik * 8);
+    if (e == hipSuccess) e = pool.acquire((void**)&p->d_inds, ninds * 4);
+    if (e == hipSuccess && ncoef) e = hipMemcpy(p->d_coef, model->coef, ncoef * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nlik) e = hipMemcpy(p->d_lik, model->lik, nlik * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_inds, inds, ninds * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        destroy_plan_nd3(p, true);
+        return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_plan_nd3_create: %s", hipGetErrorString(e));
+    }
+    mfs::FilterNd3Args& a = p->args;
+    memset(&a, 0, sizeof(a));
+    a.mode = mode; a.T = T; a.B = B; a.stable = stable ? 1 : 0;
+    a.trans_kind = model->trans_kind; a.D = model->extent;
+    a.n_factors = model->n_factors; a.ny = model->ny;
+    for (int f = 0; f < model->n_factors; ++f) {
+        a.fac_kind[f] = model->fac_kind[f]; a.fac_comp[f] = model->fac_component[f]; a.fac_ycol[f] = model->fac_ycol[f];
+    }
+    a.coef_batched = model->coef_batched; a.lik_batched = model->lik_batched;
+    // true extents of each coefficient block (trailing zero planes cut); the union over replicates when batched
+    const size_t ntab = model->coef_batched ? (size_t)B : 1;
+    const int used_rows = (model->trans_kind == MFS_ND_TRANS_GAUSSIAN) ? MFS_ND3_GAUSS_TERMS : MFS_ND3_ROWS;
+    for (int k = 0; k < MFS_ND3_ROWS; ++k) {
+        int ea = 0, eb = 0, ec = 0;
+        for (size_t r = 0; r < ntab && k < used_rows; ++r) {
+            const double* blk = model->coef + (r * MFS_ND3_ROWS + k) * DDD;
+            for (size_t i = 0; i < D; ++i)
+                for (size_t j = 0; j < D; ++j)
+                    for (size_t l = 0; l < D; ++l)
+                        if (blk[(i * D + j) * D + l] != 0.0) {
+                            if ((int)i + 1 > ea) ea = (int)i + 1;
+                            if ((int)j + 1 > eb) eb = (int)j + 1;
+                            if ((int)l + 1 > ec) ec = (int)l + 1;
+                        }
+        }
+        a.ext[k] = (ea == 0) ? 0 : (ea | (eb << 8) | (ec << 16));
+    }
+    a.coef = p->d_coef; a.lik = p->d_lik; a.inds = p->d_inds;
+    *plan = p;
+    return MFS_OK;
+}
+
+extern "C" int mfs_plan_nd3_run(mfs_plan_nd3* p, const double* d_m0, int m0_batched, const double* d_mean0,
+                                const double* d_scale0, const double* d_ys, double* d_out_moments, double* d_out_means,
+                                double* d_out_scales, double* d_out_nell, int32_t* d_out_first_nan, void* stream) {
+    if (!p) return fail(MFS_EINVAL, "plan is NULL");
+    if (p->B == 0) return MFS_OK;
+    if (!d_m0 || !d_out_nell || (p->T > 0 && !d_ys)) return fail(MFS_EINVAL, "NULL buffer");
+    if (p->mode != MFS_MODE_RAW && !d_mean0) return fail(MFS_EINVAL, "mean0 is required in central and scaled modes");
+    if (p->mode == MFS_MODE_SCALED && !d_scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    HIP_TRY(hipSetDevice(p->device));
+    mfs::FilterNd3Args a = p->args;
+    a.m0 = d_m0; a.m0_batched = m0_batched; a.mean0 = d_mean0; a.scale0 = d_scale0; a.ys = d_ys;
+    a.out_mom = d_out_moments;
+    a.out_mean = (p->mode != MFS_MODE_RAW) ? d_out_means : nullptr;
+    a.out_scale = (p->mode == MFS_MODE_SCALED) ? d_out_scales : nullptr;
+    a.out_nell = d_out_nell; a.out_first_nan = d_out_first_nan;
+    const mfs::Nd3Entry& ke = mfs::g_nd3_table[p->N];
+    hipError_t e = (p->trans_kind == MFS_ND_TRANS_GAUSSIAN ? ke.launch_gauss : ke.launch)(a, p->B, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MFS_EHIP, "d = 3 kernel launch: %s", hipGetErrorString(e));
+    return MFS_OK;
+}
+
+extern "C" int mfs_plan_nd3_destroy(mfs_plan_nd3* p) {
+    if (p) destroy_plan_nd3(p, false);
+    return MFS_OK;
+}
+
+extern "C" int mfs_plan_nd3_geometry(const mfs_plan_nd3* p, int* threads_per_filter, int* grid, int* lds_bytes_per_block) {
+    if (!p) return fail(MFS_EINVAL, "plan is NULL");
+    if (threads_per_filter) *threads_per_filter = 256;
+    if (grid) *grid = p->B;
+    if (lds_bytes_per_block) *lds_bytes_per_block = mfs::g_nd3_table[p->N].lds_bytes;
+    return MFS_OK;
+}
+
+extern "C" int mfs_filter_nd3(const mfs_model_nd3* model, int mode, int N, int T, int B, int z,
+                              const int32_t* multi_indices, const int32_t* inds, const double* m0, int m0_batched,
+                              const double* mean0, const double* scale0, const double* ys, int stable,
+                              double* out_moments, double* out_means, double* out_scales, double* out_nell,
+                              int32_t* out_first_nan, int device, void* stream) {
+    mfs_plan_nd3* plan = nullptr;
+    int rc = mfs_plan_nd3_create(&plan, model, mode, N, T, B, z, multi_indices, inds, stable, device);
+    if (rc != MFS_OK) return rc;
+    struct Guard { mfs_plan_nd3* p; ~Guard() { destroy_plan_nd3(p, true); } } guard{plan};   // (every exit below is quiesced)
+    if (!m0 || !out_nell || (T > 0 && B > 0 && !ys)) return fail(MFS_EINVAL, "NULL buffer");
+    if (mode != MFS_MODE_RAW && !mean0) return fail(MFS_EINVAL, "mean0 is required in central and scaled modes");
+    if (mode == MFS_MODE_SCALED && !scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    if (B == 0) return MFS_OK;
+    const size_t Z = (size_t)z, nb = m0_batched ? B : 1, ny = (size_t)model->ny;
+    double *d_m0 = nullptr, *d_mean0 = nullptr, *d_scale0 = nullptr, *d_ys = nullptr, *d_mom = nullptr, *d_means = nullptr,
+           *d_scales = nullptr, *d_nell = nullptr;
+    int32_t* d_fn = nullptr;
+    mfs::Lease lease(device);
+    mfs::CallContext* cx = nullptr;
+    hipError_t e = lease.context(&cx);
+    if (e != hipSuccess) return fail(MFS_EHIP, "mfs_filter_nd3: %s", hipGetErrorString(e));
+    hipStream_t s = stream ? (hipStream_t)stream : cx->compute;
+    auto alloc = [&](auto** d, size_t bytes) { if (e == hipSuccess) e = lease.device_block(d, bytes); };
+    auto h2d = [&](void* d, const void* h, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
+    };
+    auto d2h = [&](void* h, const void* d, size_t bytes) {
+        if (e == hipSuccess && h && d && bytes) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
+    };
+    alloc(&d_m0, nb * Z * 8);
+    alloc(&d_mean0, nb * 3 * 8);
+    alloc(&d_scale0, nb * 3 * 8);
+    alloc(&d_ys, (size_t)B * T * ny * 8 + 8);
+    if (out_moments) alloc(&d_mom, (size_t)B * T * Z * 8 + 8);
+    if (out_means && mode != MFS_MODE_RAW) alloc(&d_means, (size_t)B * T * 3 * 8 + 8);
+    if (out_scales && mode == MFS_MODE_SCALED) alloc(&d_scales, (size_t)B * T * 3 * 8 + 8);
+    alloc(&d_nell, (size_t)B * 8);
+    alloc(&d_fn, (size_t)B * 4);
+    h2d(d_m0, m0, nb * Z * 8);
+    if (mean0 && mode != MFS_MODE_RAW) h2d(d_mean0, mean0, nb * 3 * 8);
+    if (scale0 && mode == MFS_MODE_SCALED) h2d(d_scale0, scale0, nb * 3 * 8);
+    h2d(d_ys, ys, (size_t)B * T * ny * 8);
+    if (e == hipSuccess) {
+        rc = mfs_plan_nd3_run(plan, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn, s);
+        if (rc == MFS_OK) {
+            d2h(out_moments, d_mom, (size_t)B * T * Z * 8);
+            d2h(out_means, d_means, (size_t)B * T * 3 * 8);
+            d2h(out_scales, d_scales, (size_t)B * T * 3 * 8);
+            d2h(out_nell, d_nell, (size_t)B * 8);
+            d2h(out_first_nan, d_fn, (size_t)B * 4);
+        }
+    }
+    const hipError_t es = hipStreamSynchronize(s);   // always: the pool blocks go back on return
+    if (e == hipSuccess) e = es;
+    if (rc != MFS_OK) return rc;
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_nd3: %s", hipGetErrorString(e));
     return MFS_OK;
 }
 

@@ -2,7 +2,8 @@
 
 Same names, positional order and return tuples as the reference (mfs/multi_dims/filtering.py:283-288, 210-217,
 33-41); both closure signatures ('multi-index' for sde_cond_moments_tme, 'index' for the Normal closures, :245-249).
-d = 2 runs on `filternd_kernel` (mfs_amd/csrc/filternd_kernel.hpp); d = 1 is routed to the 1-D kernels (the reference
+d = 2 runs on `filternd_kernel` (mfs_amd/csrc/filternd_kernel.hpp), d = 3 on `filternd3_kernel` (filternd3_kernel.hpp, N = 2..4,
+TME order <= 2 operator tables or a Normal closure, likelihood factors of one component each); d = 1 is routed to the 1-D kernels (the reference
 guarantees the d = 1 N-D path equals the 1-D path, tests/test_filtering.py:304-329).  Extensions over the reference:
 `ys` may carry a leading replicate axis -- (B, T) for scalar measurements, (B, T, ny) for vector ones -- initial
 moments may be (z,) shared or (B, z), model parameters may be per-replicate.  No CPU fallback.
@@ -72,8 +73,9 @@ def _trace_likelihood(fn, d):
             f'measurement_cond_pdf returned {type(spec).__name__} when traced; use mfs_amd.stats.bernoulli_pmf / '
             'poisson_pmf / norm_pdf with mfs_amd.sym.exp / log (mfs_amd has no CPU path for arbitrary callables)')
     factors = spec.factors
-    if not 1 <= len(factors) <= _lib.ND_MAX_FACTORS:
-        raise sym.NotDeviceDescribable(f'{len(factors)} likelihood factors; the device takes 1..{_lib.ND_MAX_FACTORS}')
+    most = _lib.ND3_MAX_FACTORS if d == 3 else _lib.ND_MAX_FACTORS
+    if not 1 <= len(factors) <= most:
+        raise sym.NotDeviceDescribable(f'{len(factors)} likelihood factors; the device takes 1..{most}')
     return factors
 
 
@@ -123,6 +125,60 @@ def _model_struct(tables, factors, B=1):
     m.d, m.n_terms, m.extent = 2, last, D
     m.trans_kind = kind
     m.n_factors = nf
+    m.ny = max(f.ycol for f in factors) + 1
+    for i, f in enumerate(factors):
+        m.fac_kind[i], m.fac_component[i], m.fac_ycol[i] = _lib.LIK[f.kind], int(f.component), int(f.ycol)
+        m.fac_n_par[i] = int(np.asarray(f.params).shape[-1])
+    m.coef_batched, m.lik_batched = int(batched_coef), int(lik_batched)
+    coef, lp = np.ascontiguousarray(coef), np.ascontiguousarray(lp)
+    m.coef = coef.ctypes.data_as(_lib.c_double_p)
+    m.lik = lp.ctypes.data_as(_lib.c_double_p)
+    return m, (coef, lp)
+
+
+def _lik_params(factors, B):
+    """[n_factors][MAX_LIK], or [B][n_factors][MAX_LIK] when a factor has per-replicate parameters -> (array, batched)."""
+    nf = len(factors)
+    lik_batched = any(np.asarray(f.params).ndim > 1 for f in factors)
+    lp = np.zeros(((B,) if lik_batched else ()) + (nf, _lib.MAX_LIK))
+    for i, f in enumerate(factors):
+        prm = np.asarray(f.params, dtype=np.float64)
+        if prm.ndim > 2 or (prm.ndim == 2 and prm.shape[0] != B):
+            raise ValueError(f'likelihood parameters are batched with shape {prm.shape[:-1]}, the filter batch is {B}')
+        lp[..., i, :prm.shape[-1]] = prm
+    return lp, lik_batched
+
+
+def _model_struct3(tables, factors, B=1):
+    """mfs_model_nd3 of a d = 3 transition family and likelihood (include/mfs_hip.h)."""
+    if isinstance(factors, sym.LikelihoodSpec):
+        factors = [factors]
+    for f in factors:
+        if f.kind == 'bearing_gaussian' or int(f.component) not in (0, 1, 2):
+            raise sym.NotDeviceDescribable('at d = 3 every likelihood factor reads one state component (no joint factors)')
+    dense, D = tables.dense_table()
+    batched_coef = dense.ndim == 5          # (B, rows, D, D, D): per-replicate drift / dispersion parameters
+    if batched_coef and dense.shape[0] != B:
+        raise ValueError(f'transition tables are batched over {dense.shape[0]} replicates, the filter batch is {B}')
+    if D > _lib.ND3_MAX_EXTENT:
+        raise sym.NotDeviceDescribable(f'coefficient extent {D} exceeds MFS_ND3_MAX_EXTENT = {_lib.ND3_MAX_EXTENT}')
+    lead = (B,) if batched_coef else ()
+    coef = np.zeros(lead + (_lib.ND3_ROWS, D, D, D))
+    if tables.is_gaussian:
+        coef[..., :_lib.ND3_GAUSS_TERMS, :, :, :] = dense    # mu_0..2, S_00, S_01, S_02, S_11, S_12, S_22
+        kind, n_terms = _lib.ND_TRANS_GAUSSIAN, _lib.ND3_GAUSS_TERMS
+    else:
+        kind, n_terms = _lib.ND_TRANS_OPERATOR, _lib.ND3_TERMS
+        for t, kap in enumerate(tables.kappas):
+            kap = tuple(int(v) for v in kap)
+            if kap not in _lib.ND3_KAPPAS:
+                raise sym.NotDeviceDescribable(f'derivative term {kap} needs |kappa| <= 4, i.e. tme_order <= 2 at d = 3')
+            coef[..., _lib.ND3_KAPPAS.index(kap), :, :, :] = dense[..., t, :, :, :]
+        coef[..., _lib.ND3_TERMS:, :, :, :] = tables.var_blocks(D)   # diagonal of tme.mean_and_cov (scaled mode)
+    lp, lik_batched = _lik_params(factors, B)
+    m = _lib.MfsModelNd3()
+    m.trans_kind, m.n_terms, m.extent = kind, n_terms, D
+    m.n_factors = len(factors)
     m.ny = max(f.ycol for f in factors) + 1
     for i, f in enumerate(factors):
         m.fac_kind[i], m.fac_component[i], m.fac_ycol[i] = _lib.LIK[f.kind], int(f.component), int(f.ycol)
@@ -185,9 +241,18 @@ def _run_nd(mode, tables, factors, ys, moments_partial_order, ms0, mean0, stable
         return _run_1d(mode, tables, factors, ys, ms0, mean0, scale0, stable, device)
     inds = np.asarray(inds)
     s = inds.shape[1]
-    N = next((n for n in range(2, 8) if n * (n + 1) // 2 == s), None)
-    if d != 2 or N is None:
-        raise sym.NotDeviceDescribable(f'the device N-D path supports d <= 2 with 2 <= N <= 7 (got d = {d}, s = {s})')
+    if d == 3:
+        N = next((n for n in range(_lib.ND3_MIN_N, _lib.ND3_MAX_N + 1) if n * (n + 1) * (n + 2) // 6 == s), None)
+        if N is None:
+            raise sym.NotDeviceDescribable(f'the device d = 3 path supports {_lib.ND3_MIN_N} <= N <= {_lib.ND3_MAX_N} '
+                                           f'(got s = {s})')
+        if len(factors) > _lib.ND3_MAX_FACTORS:
+            raise sym.NotDeviceDescribable(f'{len(factors)} likelihood factors; the device takes 1..{_lib.ND3_MAX_FACTORS}')
+    else:
+        N = next((n for n in range(2, 8) if n * (n + 1) // 2 == s), None)
+        if d != 2 or N is None:
+            raise sym.NotDeviceDescribable(f'the device N-D path supports d <= 3 with 2 <= N <= 7 at d = 2, 2 <= N <= 4 '
+                                           f'at d = 3 (got d = {d}, s = {s})')
     ny = max(f.ycol for f in factors) + 1
     ys3, squeeze = _split_ys(ys, ny)
     B, T = ys3.shape[:2]
@@ -197,20 +262,21 @@ def _run_nd(mode, tables, factors, ys, moments_partial_order, ms0, mean0, stable
     z = multi_indices.shape[0]
     mean_a = scale_a = None
     if mode != 'raw':
-        mean_a = np.ascontiguousarray(np.broadcast_to(np.asarray(mean0, dtype=np.float64), ((B, 2) if batched else (2,))))
+        mean_a = np.ascontiguousarray(np.broadcast_to(np.asarray(mean0, dtype=np.float64), ((B, d) if batched else (d,))))
     if mode == 'scaled':
         scale_a = np.ascontiguousarray(np.broadcast_to(np.asarray(scale0, dtype=np.float64),
-                                                       ((B, 2) if batched else (2,))))
-    model, keep = _model_struct(tables, factors, B)
+                                                       ((B, d) if batched else (d,))))
+    model, keep = (_model_struct3 if d == 3 else _model_struct)(tables, factors, B)
     if squeeze and (model.coef_batched or model.lik_batched):
         raise ValueError('per-replicate model parameters need ys with a leading replicate axis')
     mi32 = np.ascontiguousarray(multi_indices, dtype=np.int32)
     inds32 = np.ascontiguousarray(inds, dtype=np.int32)
     out_m = _lib.pinned_empty((B, T, z), device=device)
-    out_mean = _lib.pinned_empty((B, T, 2), device=device) if mode != 'raw' else None
-    out_scale = _lib.pinned_empty((B, T, 2), device=device) if mode == 'scaled' else None
+    out_mean = _lib.pinned_empty((B, T, d), device=device) if mode != 'raw' else None
+    out_scale = _lib.pinned_empty((B, T, d), device=device) if mode == 'scaled' else None
     out_nell, out_fn = np.empty((B,)), np.empty((B,), dtype=np.int32)
-    _lib.check(_lib.lib().mfs_filter_nd(C.byref(model), _lib.MODE[mode], N, T, B, z, _lib.ptr(mi32), _lib.ptr(inds32),
+    entry = _lib.lib().mfs_filter_nd3 if d == 3 else _lib.lib().mfs_filter_nd
+    _lib.check(entry(C.byref(model), _lib.MODE[mode], N, T, B, z, _lib.ptr(mi32), _lib.ptr(inds32),
                                         _lib.ptr(ms0), int(batched), _lib.ptr(mean_a), _lib.ptr(scale_a), _lib.ptr(ys3),
                                         int(bool(stable)), _lib.ptr(out_m), _lib.ptr(out_mean), _lib.ptr(out_scale),
                                         _lib.ptr(out_nell), _lib.ptr(out_fn), device, None))

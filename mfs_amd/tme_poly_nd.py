@@ -298,12 +298,13 @@ def tme_tables_nd(drift, dispersion, d: int, dt: float, order: int) -> Transitio
 # Normal closures (mfs/multi_dims/moments.py:257-337 Euler--Maruyama, :340-411 TME mean / covariance)
 # ---------------------------------------------------------------------------------------------------------------------
 class GaussianTablesND:
-    """X' | x ~ N(mu(x), Sigma(x)) with polynomial mean vector and covariance matrix (d = 2 on the device).
+    """X' | x ~ N(mu(x), Sigma(x)) with polynomial mean vector and covariance matrix (d = 2 and d = 3 on the device).
 
     The reference evaluates E[prod (X'_k - c_k)^{n_k}] with Kan's formula per multi-index
     (mfs/multi_dims/moments.py:110-154); for d = 2 the same numbers follow from Stein's lemma as a two-term recursion,
         M(a, b) = m_0 M(a-1, b) + (a-1) S_00 M(a-2, b) + b S_01 M(a-1, b-1),     M(0, b) = m_1 M(0, b-1) + (b-1) S_11 M(0, b-2),
-    with m = mu(x) - c, which is what the kernel runs per node.
+    with m = mu(x) - c, which is what the kernel runs per node.  For d = 3 the kernel runs the general form
+        M(a) = m_k M(a - e_k) + sum_j (a - e_k)_j S_kj M(a - e_k - e_j),     k the first nonzero index of a.
     """
 
     is_gaussian = True
@@ -320,12 +321,12 @@ class GaussianTablesND:
                              self.label)
 
     def dense_table(self):
-        """(5, D, D): mu_0, mu_1, S_00, S_01, S_11."""
-        if self.d != 2:
-            raise NotDeviceDescribable('the device N-D path supports d = 2')
-        polys = [self.mean[0], self.mean[1], self.cov[0][0], self.cov[0][1], self.cov[1][1]]
+        """(5, D, D): mu_0, mu_1, S_00, S_01, S_11 (d = 2); (9, D, D, D): mu_0..2, S_00, S_01, S_02, S_11, S_12, S_22 (d = 3)."""
+        if self.d not in (2, 3):
+            raise NotDeviceDescribable(f'the device N-D path supports d = 2 and d = 3 (got d = {self.d})')
+        polys = list(self.mean) + [self.cov[i][j] for i in range(self.d) for j in range(i, self.d)]
         D = max(max(p.coef.shape) for p in polys)
-        out = np.zeros((5, D, D))
+        out = np.zeros((len(polys),) + (D,) * self.d)
         for t, p in enumerate(polys):
             out[(t,) + tuple(slice(0, n) for n in p.coef.shape)] = p.coef
         return np.ascontiguousarray(out), D
@@ -339,6 +340,8 @@ class GaussianTablesND:
         return np.stack([self.cov[i][i](x) for i in range(self.d)], axis=-1)
 
     def cond_moments(self, x, multi_indices, mean=None, scale=None):
+        if self.d == 3:
+            return self._cond_moments_3d(x, multi_indices, mean, scale)
         if self.d != 2:
             raise NotImplementedError
         x = np.asarray(x, dtype=np.float64)
@@ -362,6 +365,44 @@ class GaussianTablesND:
         if scale is not None:
             out = out / np.prod(np.asarray(scale, dtype=np.float64) ** mi, axis=-1)
         return out
+
+
+    def _cond_moments_3d(self, x, multi_indices, mean=None, scale=None):
+        """E[prod_k ((X'_k - c_k) / scale_k)^{n_k} | x] for d = 3 by the Stein recursion, vectorised over the nodes x (..., 3)."""
+        x = np.asarray(x, dtype=np.float64)
+        mi = np.asarray(multi_indices, dtype=int)
+        c = np.zeros(3) if mean is None else np.broadcast_to(np.asarray(mean, dtype=np.float64), (3,))
+        return stein_moments_3d([self.mean[k](x) - c[k] for k in range(3)],
+                                [[self.cov[i][j](x) for j in range(3)] for i in range(3)], mi, scale)
+
+
+def stein_moments_3d(m, S, multi_indices, scale=None):
+    """E[prod_k Y_k^{n_k}] for Y ~ N(m, S) in three variables, for every row n of multi_indices (z, 3): the recursion
+    M(a) = m_k M(a - e_k) + sum_j (a - e_k)_j S_kj M(a - e_k - e_j), k the first nonzero index of a, over the graded table up
+    to the highest |n| -- the same polynomial in (m, S) as Kan's formula (mfs/multi_dims/moments.py:110-154).  m: 3 arrays of
+    one shape, S: 3 x 3 nested lists of such arrays.  Returns (..., z); with `scale` divided by prod_k scale_k^{n_k}."""
+    mi = np.asarray(multi_indices, dtype=int)
+    m = [np.asarray(v, dtype=np.float64) for v in m]
+    shape = np.broadcast_shapes(*(v.shape for v in m), *(np.shape(S[i][j]) for i in range(3) for j in range(3)))
+    M = {(0, 0, 0): np.ones(shape)}
+    for deg in range(1, int(mi.sum(axis=1).max(initial=0)) + 1):
+        for a0 in range(deg + 1):
+            for a1 in range(deg - a0 + 1):
+                a = (a0, a1, deg - a0 - a1)
+                k = next(i for i in range(3) if a[i] > 0)
+                b = list(a)
+                b[k] -= 1
+                v = m[k] * M[tuple(b)]
+                for j in range(3):
+                    if b[j] > 0:
+                        bb = list(b)
+                        bb[j] -= 1
+                        v = v + b[j] * S[k][j] * M[tuple(bb)]
+                M[a] = v
+    out = np.stack([M[tuple(int(v) for v in n)] for n in mi], axis=-1)
+    if scale is not None:
+        out = out / np.prod(np.asarray(scale, dtype=np.float64) ** mi, axis=-1)
+    return out
 
 
 def normal_tables_nd(drift, dispersion, d: int, dt: float, order) -> GaussianTablesND:
@@ -421,7 +462,7 @@ class BatchedTablesND:
         tabs = [m.dense_table() for m in self.members]
         D = max(t[1] for t in tabs)
         if self.is_gaussian:
-            out = np.zeros((len(tabs), 5) + (D,) * self.d)
+            out = np.zeros((len(tabs), tabs[0][0].shape[0]) + (D,) * self.d)
             for b, (t, _) in enumerate(tabs):
                 out[(b, slice(None)) + tuple(slice(0, n) for n in t.shape[1:])] = t
             return out, D
