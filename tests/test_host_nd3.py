@@ -67,6 +67,30 @@ def test_normal_closure_cond_moments_match_oracle(order):
     npt.assert_allclose(fns[3](x), omean(x), rtol=1e-12)
 
 
+@pytest.mark.parametrize('order', ['euler', 2, 3])
+def test_lotka_volterra_normal_closures_match_kan(order):
+    """The host closures that tests/test_gpu_nd3_envelope.py hands the oracle for the Normal families, on the model with a
+    state-dependent dispersion (3-species Lotka--Volterra) and at TME order 3: against the oracle's per-node Kan moments."""
+    from .test_gpu_nd3_envelope import LV_DT, lv_model
+    rng = np.random.default_rng(6)
+    mi = generate_graded_lexico_multi_indices(3, 7)
+    m = lv_model()
+    if order == 'euler':
+        fns = moments.sde_cond_moments_euler_maruyama(m.drift, m.disp, LV_DT, mi)
+    else:
+        fns = moments.sde_cond_moments_tme_normal(m.drift, m.disp, LV_DT, order, mi)
+    _, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(m.odrift, m.odisp, 3, LV_DT, order, mi)
+    x = 1. + rng.normal(scale=0.3, size=(6, 3))
+    c = 1. + rng.normal(scale=0.1, size=3)
+    idx = np.arange(mi.shape[0])
+    want = ocms(x, idx, c)
+    npt.assert_allclose(fns[1](x, idx, c), want, rtol=1e-9, atol=1e-12 * np.abs(want).max())
+    npt.assert_allclose(fns[3](x), omean(x), rtol=1e-12)
+    scale = np.array([0.2, 0.3, 0.25])
+    npt.assert_allclose(fns[2](x, idx, c, scale), want / np.prod(scale ** mi, axis=-1), rtol=1e-9,
+                        atol=1e-12 * np.abs(want / np.prod(scale ** mi, axis=-1)).max())
+
+
 def test_operator_dense_table_matches_sympy():
     """The d = 3 operator rows, evaluated at random points through the kernel's row order, against the oracle's SymPy TME."""
     rng = np.random.default_rng(7)
