@@ -326,7 +326,8 @@ int mfs_plan_nd_geometry(const mfs_plan_nd* plan, int* threads_per_filter, int* 
  *   MFS_ND_TRANS_GAUSSIAN: rows 0..8 = mu_0, mu_1, mu_2, S_00, S_01, S_02, S_11, S_12, S_22 of X' | x ~ N(mu(x), S(x))
  *     (Euler--Maruyama, TME-normal, exact linear-Gaussian steps); the other rows are ignored.
  * Likelihood: a product of up to MFS_ND3_MAX_FACTORS factors, each a function of one state component (fac_component 0..2) and
- * one measurement column (fac_ycol < ny <= 3); kinds Bernoulli-logistic, Poisson-softplus, Gaussian (no joint factors).
+ * one measurement column (fac_ycol < ny <= 3); kinds Bernoulli-logistic, Poisson-softplus, Gaussian.  Factors of several
+ * components: mfs_joint_nd3 below.
  *
  *   multi_indices  [z][3] int32, the graded-lex table (checked);  inds [4][s][s] int32, the Gram / Hankel gather tables (checked)
  *   m0 [z] or [B][z]; mean0, scale0 [3] or [B][3]; ys [B][T][ny]
@@ -372,6 +373,51 @@ int mfs_plan_nd3_run(mfs_plan_nd3* plan, const double* d_m0, int m0_batched, con
                      double* d_out_scales, double* d_out_nell, int32_t* d_out_first_nan, void* stream);
 int mfs_plan_nd3_destroy(mfs_plan_nd3* plan);
 int mfs_plan_nd3_geometry(const mfs_plan_nd3* plan, int* threads_per_filter, int* grid, int* lds_bytes_per_block);
+
+/*
+ * ---- d = 3: joint likelihood factors (functions of all three state components) -------------------------------------
+ * A joint factor is kind(y ; u(x), par) with kind one of MFS_LIK_BERNOULLI_LOGISTIC (p = logistic(u)),
+ * MFS_LIK_POISSON_SOFTPLUS (rate = softplus(u)), MFS_LIK_GAUSSIAN (y ~ N(u, par), par the variance), and u a scalar link of
+ * at most two trivariate polynomials p, q:
+ *   MFS_ND3_LINK_POLY        u = p(x)                     y ~ N(x0 x1, var); Poisson(softplus(x0 + x1 + x2))
+ *   MFS_ND3_LINK_SQRT        u = sqrt(p(x))               range |x - s|
+ *   MFS_ND3_LINK_ATAN2       u = atan2(p(x), q(x))        azimuth atan2(x1 - s1, x0 - s0); no angle wrapping of y - u
+ *   MFS_ND3_LINK_ATAN2_SQRT  u = atan2(p(x), sqrt(q(x)))  elevation atan2(x2 - s2, hypot(x0 - s0, x1 - s1))
+ * coef is [n_joint][2][E][E][E] (or [B][n_joint][2][E][E][E] when batched): block [f][0] is p, [f][1] is q (zeros where the
+ * link has no q), entry [a][b][c] the coefficient of x0^a x1^b x2^c, E = extent <= MFS_ND3_JOINT_MAX_EXTENT (degree 3).
+ * par is [n_joint] (or [B][n_joint]): the Gaussian variance, ignored by the other kinds.  `batched` covers coef and par.
+ * The factors multiply the single-component factors of mfs_model_nd3, whose n_factors may then be 0 (lik may be NULL) and
+ * whose ny may reach MFS_ND3_JOINT_MAX_NY; every ycol, single or joint, is < ny.  sqrt of a negative value and any
+ * non-finite u NaN-poison the replicate from that step on, as a non-finite posterior does.
+ * mfs_plan_nd3_create_joint makes an ordinary mfs_plan_nd3 (run / destroy / geometry as above); joint == NULL or
+ * n_joint == 0 is refused -- such a model goes through mfs_plan_nd3_create and runs the kernel it always ran.
+ */
+#define MFS_ND3_MAX_JOINT 3
+#define MFS_ND3_JOINT_MAX_EXTENT 4 /* per-variable extent (degree + 1) of p and q */
+#define MFS_ND3_JOINT_MAX_NY 6
+#define MFS_ND3_LINK_POLY 0
+#define MFS_ND3_LINK_SQRT 1
+#define MFS_ND3_LINK_ATAN2 2
+#define MFS_ND3_LINK_ATAN2_SQRT 3
+typedef struct mfs_joint_nd3 {
+    int32_t n_joint;                       /* 1 .. MFS_ND3_MAX_JOINT */
+    int32_t extent;                        /* E, 1 .. MFS_ND3_JOINT_MAX_EXTENT */
+    int32_t batched;                       /* coef and par carry a leading [B] */
+    int32_t kind[MFS_ND3_MAX_JOINT];       /* MFS_LIK_BERNOULLI_LOGISTIC / _POISSON_SOFTPLUS / _GAUSSIAN */
+    int32_t link[MFS_ND3_MAX_JOINT];       /* MFS_ND3_LINK_* */
+    int32_t ycol[MFS_ND3_MAX_JOINT];       /* < ny of the model */
+    const double* coef;                    /* [n_joint][2][E][E][E] or [B][...] */
+    const double* par;                     /* [n_joint] or [B][n_joint] */
+} mfs_joint_nd3;
+
+int mfs_filter_nd3_joint(const mfs_model_nd3* model, const mfs_joint_nd3* joint, int mode, int N, int T, int B, int z,
+                         const int32_t* multi_indices, const int32_t* inds, const double* m0, int m0_batched,
+                         const double* mean0, const double* scale0, const double* ys, int stable, double* out_moments,
+                         double* out_means, double* out_scales, double* out_nell, int32_t* out_first_nan, int device,
+                         void* stream);
+int mfs_plan_nd3_create_joint(mfs_plan_nd3** plan, const mfs_model_nd3* model, const mfs_joint_nd3* joint /* host pointers */,
+                              int mode, int N, int T, int B, int z, const int32_t* multi_indices, const int32_t* inds,
+                              int stable, int device);
 
 /*
  * ---- multi-GPU: one process per GPU, replicates sharded, NLL all-gather over RCCL / xGMI -----------------------

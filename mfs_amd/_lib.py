@@ -43,6 +43,12 @@ class MfsModelNd3(C.Structure):
                 ('lik', c_double_p)]
 
 
+class MfsJointNd3(C.Structure):
+    """struct mfs_joint_nd3 (include/mfs_hip.h): the joint likelihood factors of a d = 3 model."""
+    _fields_ = [('n_joint', C.c_int32), ('extent', C.c_int32), ('batched', C.c_int32), ('kind', C.c_int32 * 3),
+                ('link', C.c_int32 * 3), ('ycol', C.c_int32 * 3), ('coef', c_double_p), ('par', c_double_p)]
+
+
 ND_TERMS = 14          # kappa terms with |kappa| <= 4 (TME order <= 2): the 16-row table layout
 ND_ROWS = 16
 ND_TERMS_MAX = 27      # ... |kappa| <= 6 (TME order 3): the 29-row layout
@@ -61,6 +67,11 @@ ND3_MIN_N, ND3_MAX_N = 2, 4
 ND3_TERMS, ND3_ROWS, ND3_GAUSS_TERMS = 34, 37, 9
 ND3_MAX_EXTENT = 6
 ND3_MAX_FACTORS = 3
+# joint likelihood factors at d = 3 (mfs_joint_nd3): u = p, sqrt(p), atan2(p, q), atan2(p, sqrt(q)) of trivariate polynomials
+ND3_MAX_JOINT = 3
+ND3_JOINT_MAX_EXTENT = 4
+ND3_JOINT_MAX_NY = 6
+ND3_LINK = {'poly': 0, 'sqrt': 1, 'atan2': 2, 'atan2_sqrt': 3}
 # derivative multi-indices kappa, 1 <= |kappa| <= 4, in the graded-lex order of the multi-index tables (each degree in ascending
 # tuple order): the order of the operator rows of mfs_model_nd3.coef, the kernel's nd3_kappa_row
 ND3_KAPPAS = [(a, b, s - a - b) for s in range(1, 5) for a in range(s + 1) for b in range(s - a + 1)]
@@ -125,6 +136,10 @@ _SIGNATURES = [
     ('mfs_plan_nd3_run', _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ('mfs_plan_nd3_destroy', _i, [_vp]),
     ('mfs_plan_nd3_geometry', _i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ('mfs_filter_nd3_joint', _i, [C.POINTER(MfsModelNd3), C.POINTER(MfsJointNd3), _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp,
+                                  _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ('mfs_plan_nd3_create_joint', _i, [_vpp, C.POINTER(MfsModelNd3), C.POINTER(MfsJointNd3), _i, _i, _i, _i, _i, _vp, _vp, _i,
+                                       _i]),
     ('mfs_elementary', _i, [_i, _i, _vp, _vp, _i]),
     ('mfs_comm_unique_id', _i, [_vp]),
     ('mfs_comm_init', _i, [_vpp, _vp, _i, _i, _i]),

@@ -31,7 +31,8 @@ using FilterNdLaunch = hipError_t (*)(const FilterNdArgs&, int grid, hipStream_t
 struct NdEntry { FilterNdLaunch launch, launch_gauss, launch_hi, launch_joint; int S, Z, lds_bytes, carry_doubles; };
 extern NdEntry g_nd_table[8];  // filternd_inst.hip
 using FilterNd3Launch = hipError_t (*)(const FilterNd3Args&, int grid, hipStream_t);
-struct Nd3Entry { FilterNd3Launch launch, launch_gauss; int S, Z, lds_bytes; };
+using FilterNd3JointLaunch = hipError_t (*)(const FilterNd3Args&, const FilterNd3Joint&, int grid, hipStream_t);
+struct Nd3Entry { FilterNd3Launch launch, launch_gauss; int S, Z, lds_bytes; FilterNd3JointLaunch joint, joint_gauss; };
 extern Nd3Entry g_nd3_table[MFS_ND3_MAX_N + 1];  // filternd3_inst.hip
 hipError_t launch_elementary(int which, int n, const double* d_x, double* d_out, hipStream_t s);
 extern Filter1dGradLaunch g_grad_table[17][5];  // filter1d_grad_inst.hip: [N <= 16][P <= 4]
@@ -966,9 +967,12 @@ extern "C" int mfs_filter_nd(const mfs_model_nd* model, int mode, int N, int T, 
 struct mfs_plan_nd3 {
     int mode, N, T, B, stable, device, trans_kind, ny;
     mfs::FilterNd3Args args;  // model part filled at create (device pointers), data pointers per run
+    mfs::FilterNd3Joint joint;  // n = 0: no joint factors, the plain kernels
     double* d_coef = nullptr;
     double* d_lik = nullptr;
     int32_t* d_inds = nullptr;
+    double* d_jcoef = nullptr;
+    double* d_jpar = nullptr;
 };
 
 static void destroy_plan_nd3(mfs_plan_nd3* p, bool quiesced) {
@@ -976,11 +980,28 @@ static void destroy_plan_nd3(mfs_plan_nd3* p, bool quiesced) {
     if (!quiesced) hipDeviceSynchronize();
     mfs::BlockPool<false>& pool = mfs::device_state(p->device).device;
     pool.release(p->d_coef); pool.release(p->d_lik); pool.release(p->d_inds);
+    pool.release(p->d_jcoef); pool.release(p->d_jpar);
     delete p;
 }
 
-extern "C" int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* model, int mode, int N, int T, int B, int z,
-                                   const int32_t* multi_indices, const int32_t* inds, int stable, int device) {
+// packed true extents of one [D][D][D] coefficient block over ntab tables `stride` doubles apart (0: all zero)
+static int nd3_block_extents(const double* blk, size_t D, size_t ntab, size_t stride) {
+    int ea = 0, eb = 0, ec = 0;
+    for (size_t r = 0; r < ntab; ++r)
+        for (size_t i = 0; i < D; ++i)
+            for (size_t j = 0; j < D; ++j)
+                for (size_t l = 0; l < D; ++l)
+                    if (blk[r * stride + (i * D + j) * D + l] != 0.0) {
+                        if ((int)i + 1 > ea) ea = (int)i + 1;
+                        if ((int)j + 1 > eb) eb = (int)j + 1;
+                        if ((int)l + 1 > ec) ec = (int)l + 1;
+                    }
+    return (ea == 0) ? 0 : (ea | (eb << 8) | (ec << 16));
+}
+
+// joint == nullptr: the model of mfs_plan_nd3_create (1..3 single-component factors, ny <= 3)
+static int plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* model, const mfs_joint_nd3* joint, int mode, int N, int T,
+                           int B, int z, const int32_t* multi_indices, const int32_t* inds, int stable, int device) {
     if (!plan) return fail(MFS_EINVAL, "plan is NULL");
     *plan = nullptr;
     if (!model) return fail(MFS_EINVAL, "model is NULL");
@@ -998,9 +1019,25 @@ extern "C" int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* mod
     if (z != ke.Z) return fail(MFS_EINVAL, "The size of multi_indices %d must match that of the moments %d.", z, ke.Z);
     if (model->extent < 1 || model->extent > MFS_ND3_MAX_EXTENT)
         return fail(MFS_EUNSUPPORTED, "coefficient extent %d outside [1, %d]", model->extent, MFS_ND3_MAX_EXTENT);
-    if (model->n_factors < 1 || model->n_factors > MFS_ND3_MAX_FACTORS)
-        return fail(MFS_EINVAL, "n_factors %d outside [1, %d]", model->n_factors, MFS_ND3_MAX_FACTORS);
-    if (model->ny < 1 || model->ny > 3) return fail(MFS_EINVAL, "ny %d outside [1, 3]", model->ny);
+    const int min_factors = joint ? 0 : 1, max_ny = joint ? MFS_ND3_JOINT_MAX_NY : 3;
+    if (model->n_factors < min_factors || model->n_factors > MFS_ND3_MAX_FACTORS)
+        return fail(MFS_EINVAL, "n_factors %d outside [%d, %d]", model->n_factors, min_factors, MFS_ND3_MAX_FACTORS);
+    if (model->ny < 1 || model->ny > max_ny) return fail(MFS_EINVAL, "ny %d outside [1, %d]", model->ny, max_ny);
+    if (joint) {
+        if (joint->n_joint < 1 || joint->n_joint > MFS_ND3_MAX_JOINT)
+            return fail(MFS_EINVAL, "n_joint %d outside [1, %d]", joint->n_joint, MFS_ND3_MAX_JOINT);
+        if (joint->extent < 1 || joint->extent > MFS_ND3_JOINT_MAX_EXTENT)
+            return fail(MFS_EUNSUPPORTED, "joint polynomial extent %d outside [1, %d]", joint->extent, MFS_ND3_JOINT_MAX_EXTENT);
+        for (int f = 0; f < joint->n_joint; ++f) {
+            if (joint->kind[f] < 0 || joint->kind[f] > MFS_LIK_GAUSSIAN)
+                return fail(MFS_EINVAL, "joint factor %d: kind %d is not Bernoulli-logistic, Poisson-softplus or Gaussian", f, joint->kind[f]);
+            if (joint->link[f] < MFS_ND3_LINK_POLY || joint->link[f] > MFS_ND3_LINK_ATAN2_SQRT)
+                return fail(MFS_EINVAL, "joint factor %d: unknown link %d", f, joint->link[f]);
+            if (joint->ycol[f] < 0 || joint->ycol[f] >= model->ny)
+                return fail(MFS_EINVAL, "joint factor %d: measurement column %d outside [0, ny = %d)", f, joint->ycol[f], model->ny);
+        }
+        if (!joint->coef || !joint->par) return fail(MFS_EINVAL, "NULL buffer");
+    }
     for (int f = 0; f < model->n_factors; ++f) {
         if (model->fac_kind[f] == MFS_LIK_BEARING_GAUSSIAN)
             return fail(MFS_EUNSUPPORTED, "a likelihood of several state components is not supported at d = 3");
@@ -1010,7 +1047,7 @@ extern "C" int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* mod
             return fail(MFS_EINVAL, "bad description of likelihood factor %d", f);
     }
     if (T < 0 || B < 0) return fail(MFS_EINVAL, "negative T or B");
-    if (!multi_indices || !inds || !model->coef || !model->lik) return fail(MFS_EINVAL, "NULL buffer");
+    if (!multi_indices || !inds || !model->coef || (model->n_factors > 0 && !model->lik)) return fail(MFS_EINVAL, "NULL buffer");
     const int S = ke.S;
     // the kernel derives a moment's multi-index from its position: insist on the graded-lex tables
     for (int zi = 0; zi < z; ++zi)
@@ -1043,6 +1080,15 @@ extern "C" int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* mod
     if (e == hipSuccess && ncoef) e = hipMemcpy(p->d_coef, model->coef, ncoef * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && nlik) e = hipMemcpy(p->d_lik, model->lik, nlik * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->d_inds, inds, ninds * 4, hipMemcpyHostToDevice);
+    const size_t E = joint ? (size_t)joint->extent : 0, jblk = 2 * E * E * E, jtab = joint ? (size_t)joint->n_joint * jblk : 0;
+    const size_t njb = (joint && joint->batched) ? (size_t)B : 1;
+    if (joint) {
+        const size_t njpar = njb * joint->n_joint;
+        if (e == hipSuccess) e = pool.acquire((void**)&p->d_jcoef, njb * jtab * 8);
+        if (e == hipSuccess) e = pool.acquire((void**)&p->d_jpar, njpar * 8);
+        if (e == hipSuccess && njb) e = hipMemcpy(p->d_jcoef, joint->coef, njb * jtab * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && njb) e = hipMemcpy(p->d_jpar, joint->par, njpar * 8, hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         destroy_plan_nd3(p, true);
         return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_plan_nd3_create: %s", hipGetErrorString(e));
@@ -1059,24 +1105,35 @@ extern "C" int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* mod
     // true extents of each coefficient block (trailing zero planes cut); the union over replicates when batched
     const size_t ntab = model->coef_batched ? (size_t)B : 1;
     const int used_rows = (model->trans_kind == MFS_ND_TRANS_GAUSSIAN) ? MFS_ND3_GAUSS_TERMS : MFS_ND3_ROWS;
-    for (int k = 0; k < MFS_ND3_ROWS; ++k) {
-        int ea = 0, eb = 0, ec = 0;
-        for (size_t r = 0; r < ntab && k < used_rows; ++r) {
-            const double* blk = model->coef + (r * MFS_ND3_ROWS + k) * DDD;
-            for (size_t i = 0; i < D; ++i)
-                for (size_t j = 0; j < D; ++j)
-                    for (size_t l = 0; l < D; ++l)
-                        if (blk[(i * D + j) * D + l] != 0.0) {
-                            if ((int)i + 1 > ea) ea = (int)i + 1;
-                            if ((int)j + 1 > eb) eb = (int)j + 1;
-                            if ((int)l + 1 > ec) ec = (int)l + 1;
-                        }
-        }
-        a.ext[k] = (ea == 0) ? 0 : (ea | (eb << 8) | (ec << 16));
-    }
+    for (int k = 0; k < MFS_ND3_ROWS; ++k)
+        a.ext[k] = (k < used_rows) ? nd3_block_extents(model->coef + (size_t)k * DDD, D, ntab, MFS_ND3_ROWS * DDD) : 0;
     a.coef = p->d_coef; a.lik = p->d_lik; a.inds = p->d_inds;
+    mfs::FilterNd3Joint& jt = p->joint;
+    memset(&jt, 0, sizeof(jt));
+    if (joint) {
+        jt.n = joint->n_joint; jt.E = joint->extent; jt.batched = joint->batched ? 1 : 0;
+        for (int f = 0; f < joint->n_joint; ++f) {
+            jt.kind[f] = joint->kind[f]; jt.link[f] = joint->link[f]; jt.ycol[f] = joint->ycol[f];
+            for (int w = 0; w < 2; ++w)
+                jt.ext[f][w] = nd3_block_extents(joint->coef + (size_t)f * jblk + (size_t)w * E * E * E, E, njb, jtab);
+        }
+        jt.coef = p->d_jcoef; jt.par = p->d_jpar;
+    }
     *plan = p;
     return MFS_OK;
+}
+
+extern "C" int mfs_plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* model, int mode, int N, int T, int B, int z,
+                                   const int32_t* multi_indices, const int32_t* inds, int stable, int device) {
+    return plan_nd3_create(plan, model, nullptr, mode, N, T, B, z, multi_indices, inds, stable, device);
+}
+
+extern "C" int mfs_plan_nd3_create_joint(mfs_plan_nd3** plan, const mfs_model_nd3* model, const mfs_joint_nd3* joint, int mode,
+                                         int N, int T, int B, int z, const int32_t* multi_indices, const int32_t* inds,
+                                         int stable, int device) {
+    if (plan) *plan = nullptr;
+    if (!joint) return fail(MFS_EINVAL, "joint is NULL (a model without joint factors goes through mfs_plan_nd3_create)");
+    return plan_nd3_create(plan, model, joint, mode, N, T, B, z, multi_indices, inds, stable, device);
 }
 
 extern "C" int mfs_plan_nd3_run(mfs_plan_nd3* p, const double* d_m0, int m0_batched, const double* d_mean0,
@@ -1095,7 +1152,9 @@ extern "C" int mfs_plan_nd3_run(mfs_plan_nd3* p, const double* d_m0, int m0_batc
     a.out_scale = (p->mode == MFS_MODE_SCALED) ? d_out_scales : nullptr;
     a.out_nell = d_out_nell; a.out_first_nan = d_out_first_nan;
     const mfs::Nd3Entry& ke = mfs::g_nd3_table[p->N];
-    hipError_t e = (p->trans_kind == MFS_ND_TRANS_GAUSSIAN ? ke.launch_gauss : ke.launch)(a, p->B, (hipStream_t)stream);
+    const bool gauss = p->trans_kind == MFS_ND_TRANS_GAUSSIAN;
+    hipError_t e = p->joint.n ? (gauss ? ke.joint_gauss : ke.joint)(a, p->joint, p->B, (hipStream_t)stream)
+                              : (gauss ? ke.launch_gauss : ke.launch)(a, p->B, (hipStream_t)stream);
     if (e != hipSuccess) return fail(MFS_EHIP, "d = 3 kernel launch: %s", hipGetErrorString(e));
     return MFS_OK;
 }
@@ -1113,13 +1172,13 @@ extern "C" int mfs_plan_nd3_geometry(const mfs_plan_nd3* p, int* threads_per_fil
     return MFS_OK;
 }
 
-extern "C" int mfs_filter_nd3(const mfs_model_nd3* model, int mode, int N, int T, int B, int z,
-                              const int32_t* multi_indices, const int32_t* inds, const double* m0, int m0_batched,
-                              const double* mean0, const double* scale0, const double* ys, int stable,
-                              double* out_moments, double* out_means, double* out_scales, double* out_nell,
-                              int32_t* out_first_nan, int device, void* stream) {
+static int filter_nd3(const mfs_model_nd3* model, const mfs_joint_nd3* joint, int mode, int N, int T, int B, int z,
+                      const int32_t* multi_indices, const int32_t* inds, const double* m0, int m0_batched,
+                      const double* mean0, const double* scale0, const double* ys, int stable,
+                      double* out_moments, double* out_means, double* out_scales, double* out_nell,
+                      int32_t* out_first_nan, int device, void* stream) {
     mfs_plan_nd3* plan = nullptr;
-    int rc = mfs_plan_nd3_create(&plan, model, mode, N, T, B, z, multi_indices, inds, stable, device);
+    int rc = plan_nd3_create(&plan, model, joint, mode, N, T, B, z, multi_indices, inds, stable, device);
     if (rc != MFS_OK) return rc;
     struct Guard { mfs_plan_nd3* p; ~Guard() { destroy_plan_nd3(p, true); } } guard{plan};   // (every exit below is quiesced)
     if (!m0 || !out_nell || (T > 0 && B > 0 && !ys)) return fail(MFS_EINVAL, "NULL buffer");
@@ -1170,6 +1229,25 @@ extern "C" int mfs_filter_nd3(const mfs_model_nd3* model, int mode, int N, int T
     if (rc != MFS_OK) return rc;
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_nd3: %s", hipGetErrorString(e));
     return MFS_OK;
+}
+
+extern "C" int mfs_filter_nd3(const mfs_model_nd3* model, int mode, int N, int T, int B, int z,
+                              const int32_t* multi_indices, const int32_t* inds, const double* m0, int m0_batched,
+                              const double* mean0, const double* scale0, const double* ys, int stable,
+                              double* out_moments, double* out_means, double* out_scales, double* out_nell,
+                              int32_t* out_first_nan, int device, void* stream) {
+    return filter_nd3(model, nullptr, mode, N, T, B, z, multi_indices, inds, m0, m0_batched, mean0, scale0, ys, stable,
+                      out_moments, out_means, out_scales, out_nell, out_first_nan, device, stream);
+}
+
+extern "C" int mfs_filter_nd3_joint(const mfs_model_nd3* model, const mfs_joint_nd3* joint, int mode, int N, int T, int B, int z,
+                                    const int32_t* multi_indices, const int32_t* inds, const double* m0, int m0_batched,
+                                    const double* mean0, const double* scale0, const double* ys, int stable,
+                                    double* out_moments, double* out_means, double* out_scales, double* out_nell,
+                                    int32_t* out_first_nan, int device, void* stream) {
+    if (!joint) return fail(MFS_EINVAL, "joint is NULL (a model without joint factors goes through mfs_filter_nd3)");
+    return filter_nd3(model, joint, mode, N, T, B, z, multi_indices, inds, m0, m0_batched, mean0, scale0, ys, stable,
+                      out_moments, out_means, out_scales, out_nell, out_first_nan, device, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,10 @@
 //               Normal closures: the 3-D Stein recursion M(a) = m_k M(a - e_k) + sum_j (a - e_k)_j S_kj M(a - e_k - e_j), k the
 //               first nonzero index of a, per node from M(0) = W.
 //   update      the likelihood is a product of single-component factors: lik_k(x_k) tabulated on the s eigenvalues of each
-//               component, the node value a product of three table entries.
+//               component, the node value a product of three table entries.  Joint factors (J = 1 instantiations, FilterNd3Joint):
+//               kind(y; u(x)) with u = p, sqrt(p), atan2(p, q) or atan2(p, sqrt(q)) of trivariate polynomials, evaluated at the
+//               node from its coordinates and multiplied into the node weight in each of the three update passes (recomputed per
+//               pass: s^3 values do not fit in LDS at N = 4).  J = 0 instantiations carry none of it.
 // A replicate whose rule fails (non-positive pivot, non-finite K) or whose moments turn non-finite is NaN-poisoned from that
 // step on; out_first_nan reports the step.
 #pragma once
@@ -51,6 +54,15 @@ struct FilterNd3Args {
     double* out_scale;        // [B][T][3] or null
     double* out_nell;         // [B]
     int32_t* out_first_nan;   // [B] or null
+};
+
+// joint likelihood factors (mfs_joint_nd3): a second kernel argument of the J = 1 instantiations only
+struct FilterNd3Joint {
+    int n, E, batched;
+    int kind[MFS_ND3_MAX_JOINT], link[MFS_ND3_MAX_JOINT], ycol[MFS_ND3_MAX_JOINT];
+    int ext[MFS_ND3_MAX_JOINT][2];   // true extents of p and q, packed as FilterNd3Args::ext
+    const double* coef;              // [n][2][E][E][E] (or [B][...])
+    const double* par;               // [n] (or [B][n]): Gaussian variance
 };
 
 // graded-lexicographic multi-indices in three variables (multi_indices.py:139-177): by total degree, each degree in ascending
@@ -134,6 +146,32 @@ __device__ __forceinline__ double nd3_poly(const double* __restrict__ c, const i
         r = fma(r, x0, s1);
     }
     return r;
+}
+
+// one joint factor at a node: the link u of p and q, then the kind applied to u with the arithmetic of likelihood_nd.
+// sqrt of a negative value is NaN; a non-finite u gives NaN, which poisons the replicate through p(y).
+__device__ __forceinline__ double nd3_joint_factor(const int kind, const int link, const double* __restrict__ c, const int E,
+                                                   const int extp, const int extq, const double par, const double y,
+                                                   const double x0, const double x1, const double x2) {
+    const double p = nd3_poly(c, E, extp, x0, x1, x2);
+    double u = p;
+    if (link == MFS_ND3_LINK_SQRT) {
+        u = sqrt(p);
+    } else if (link != MFS_ND3_LINK_POLY) {
+        const double q = nd3_poly(c + E * E * E, E, extq, x0, x1, x2);
+        u = atan2(p, (link == MFS_ND3_LINK_ATAN2_SQRT) ? sqrt(q) : q);
+    }
+    if (!__builtin_isfinite(u)) return __builtin_nan("");
+    if (kind == MFS_LIK_BERNOULLI_LOGISTIC) {
+        const double pr = rcp_sat(1.0 + fast_exp<true>(-u));
+        return (y > 0.5) ? pr : 1.0 - pr;
+    }
+    if (kind == MFS_LIK_POISSON_SOFTPLUS) {
+        const double rate = fast_log<true>(1.0 + fast_exp<true>(u));
+        return fast_exp<true>(y * fast_log<true>(rate) - rate - log_factorial(y));
+    }
+    const double r = y - u;
+    return fast_exp<true>(-0.5 * r * r * rcp_nr(par)) * rsq_nr(6.283185307179586476925 * par);
 }
 
 // The quadrature rule of the moments in LDS (oMom) around the centre / scale in misc (mode): on return the node coordinates
@@ -374,8 +412,8 @@ __device__ __forceinline__ void nd3_monomials(double* __restrict__ colp, const i
     });
 }
 
-template <int N, int TK>
-__global__ __launch_bounds__(256, 1) void filternd3_kernel(const FilterNd3Args a) {
+template <int N, int TK, int J>
+__device__ __forceinline__ void filternd3_body(const FilterNd3Args& a, const FilterNd3Joint& jt) {
     using L = Nd3Tile<N>;
     constexpr int S = L::S, Z = L::Z, TS = L::TS;
     extern __shared__ double Sm[];
@@ -503,8 +541,30 @@ __global__ __launch_bounds__(256, 1) void filternd3_kernel(const FilterNd3Args a
                     Sm[L::oL + u] = l;
                 }
                 __syncthreads();
+                // joint factors: measurements and parameters of this step are uniform; the node value is recomputed in each pass
+                double jy[MFS_ND3_MAX_JOINT], jpar[MFS_ND3_MAX_JOINT];
+                const double* jcoef = nullptr;
+                if constexpr (J) {
+                    jcoef = jt.coef + (jt.batched ? (size_t)b * jt.n * 2 * jt.E * jt.E * jt.E : 0);
+#pragma unroll
+                    for (int f = 0; f < MFS_ND3_MAX_JOINT; ++f) {
+                        jy[f] = (f < jt.n) ? a.ys[((size_t)b * a.T + t) * a.ny + jt.ycol[f]] : 0.0;
+                        jpar[f] = (f < jt.n) ? jt.par[(jt.batched ? (size_t)b * jt.n : 0) + f] : 1.0;
+                    }
+                }
+                auto node_lik = [&](int i, int j, int k, double x0, double x1, double x2) {
+                    double l = Sm[L::oL + i] * Sm[L::oL + S + j] * Sm[L::oL + 2 * S + k];
+                    if constexpr (J) {
+#pragma unroll
+                        for (int f = 0; f < MFS_ND3_MAX_JOINT; ++f)
+                            if (f < jt.n)
+                                l *= nd3_joint_factor(jt.kind[f], jt.link[f], jcoef + f * 2 * jt.E * jt.E * jt.E, jt.E, jt.ext[f][0],
+                                                      jt.ext[f][1], jpar[f], jy[f], x0, x1, x2);
+                    }
+                    return l;
+                };
                 nd3_pass<N, 4>(Sm, misc + kM3Acc, [&](double* colp, int i, int j, int k, double W, double x0, double x1, double x2) {
-                    const double wl = W * (Sm[L::oL + i] * Sm[L::oL + S + j] * Sm[L::oL + 2 * S + k]);
+                    const double wl = W * node_lik(i, j, k, x0, x1, x2);
                     colp[0] = wl; colp[TS] = wl * x0; colp[2 * TS] = wl * x1; colp[3 * TS] = wl * x2;
                 });
                 const double pdf = misc[kM3Acc];
@@ -512,7 +572,7 @@ __global__ __launch_bounds__(256, 1) void filternd3_kernel(const FilterNd3Args a
                 double sc0 = 1.0, sc1 = 1.0, sc2 = 1.0;
                 if (mode == MFS_MODE_SCALED) {
                     nd3_pass<N, 3>(Sm, misc + kM3Acc + 4, [&](double* colp, int i, int j, int k, double W, double x0, double x1, double x2) {
-                        const double wl = W * (Sm[L::oL + i] * Sm[L::oL + S + j] * Sm[L::oL + 2 * S + k]);
+                        const double wl = W * node_lik(i, j, k, x0, x1, x2);
                         colp[0] = wl * (x0 - mu0) * (x0 - mu0);
                         colp[TS] = wl * (x1 - mu1) * (x1 - mu1);
                         colp[2 * TS] = wl * (x2 - mu2) * (x2 - mu2);
@@ -522,7 +582,7 @@ __global__ __launch_bounds__(256, 1) void filternd3_kernel(const FilterNd3Args a
                 const bool raw = (mode == MFS_MODE_RAW);
                 const double c0 = raw ? 0.0 : mu0, c1 = raw ? 0.0 : mu1, c2 = raw ? 0.0 : mu2;
                 nd3_pass<N, Z>(Sm, Sm + L::oMom, [&](double* colp, int i, int j, int k, double W, double x0, double x1, double x2) {
-                    colp[0] = W * (Sm[L::oL + i] * Sm[L::oL + S + j] * Sm[L::oL + 2 * S + k]);
+                    colp[0] = W * node_lik(i, j, k, x0, x1, x2);
                     nd3_monomials<Z>(colp, TS, (x0 - c0) / sc0, (x1 - c1) / sc1, (x2 - c2) / sc2);
                 });
                 for (int q = tid; q < Z; q += 256) {
@@ -561,6 +621,17 @@ __global__ __launch_bounds__(256, 1) void filternd3_kernel(const FilterNd3Args a
         a.out_nell[b] = poisoned ? __builtin_nan("") : nell;
         if (a.out_first_nan) a.out_first_nan[b] = first_nan;
     }
+}
+
+template <int N, int TK>
+__global__ __launch_bounds__(256, 1) void filternd3_kernel(const FilterNd3Args a) {
+    filternd3_body<N, TK, 0>(a, FilterNd3Joint{});
+}
+
+// the same step loop with joint likelihood factors in the update
+template <int N, int TK>
+__global__ __launch_bounds__(256, 1) void filternd3_joint_kernel(const FilterNd3Args a, const FilterNd3Joint jt) {
+    filternd3_body<N, TK, 1>(a, jt);
 }
 
 }  // namespace mfs

@@ -3,14 +3,17 @@
 Same names, positional order and return tuples as the reference (mfs/multi_dims/filtering.py:283-288, 210-217,
 33-41); both closure signatures ('multi-index' for sde_cond_moments_tme, 'index' for the Normal closures, :245-249).
 d = 2 runs on `filternd_kernel` (mfs_amd/csrc/filternd_kernel.hpp), d = 3 on `filternd3_kernel` (filternd3_kernel.hpp, N = 2..4,
-TME order <= 2 operator tables or a Normal closure, likelihood factors of one component each); d = 1 is routed to the 1-D kernels (the reference
+TME order <= 2 operator tables or a Normal closure, likelihood factors of one component each and / or joint factors of all
+three components); d = 1 is routed to the 1-D kernels (the reference
 guarantees the d = 1 N-D path equals the 1-D path, tests/test_filtering.py:304-329).  Extensions over the reference:
 `ys` may carry a leading replicate axis -- (B, T) for scalar measurements, (B, T, ny) for vector ones -- initial
 moments may be (z,) shared or (B, z), model parameters may be per-replicate.  No CPU fallback.
 
 The measurement likelihood must be a product of factors, each a function of ONE state component and one measurement
 column: `bernoulli.pmf(y, logistic(x[0]))` (mfs/multi_dims/ss_models.py:63-67) or
-`math.prod(norm.pdf(y, x, sd))` on vector y, x (reference tests/test_filtering.py:44-46).
+`math.prod(norm.pdf(y, x, sd))` on vector y, x (reference tests/test_filtering.py:44-46).  At d = 3 a factor may also read
+all three components: `norm_pdf(y, x[0] * x[1], sd)`, `norm_pdf(y[0], sym.sqrt(p), sd)`, `norm_pdf(y[1], sym.arctan2(p, q), sd)`
+with p, q polynomials of per-variable degree <= 3 (include/mfs_hip.h, mfs_joint_nd3); up to 3 of them multiply the others.
 """
 import ctypes as C
 from typing import Callable, Tuple
@@ -73,9 +76,15 @@ def _trace_likelihood(fn, d):
             f'measurement_cond_pdf returned {type(spec).__name__} when traced; use mfs_amd.stats.bernoulli_pmf / '
             'poisson_pmf / norm_pdf with mfs_amd.sym.exp / log (mfs_amd has no CPU path for arbitrary callables)')
     factors = spec.factors
+    joint = [f for f in factors if isinstance(f, sym.JointLikelihoodSpec)]
+    if joint and d != 3:
+        raise sym.NotDeviceDescribable('joint polynomial likelihood factors run at d = 3 only')
+    if len(joint) > _lib.ND3_MAX_JOINT:
+        raise sym.NotDeviceDescribable(f'{len(joint)} joint likelihood factors; the device takes at most {_lib.ND3_MAX_JOINT}')
     most = _lib.ND3_MAX_FACTORS if d == 3 else _lib.ND_MAX_FACTORS
-    if not 1 <= len(factors) <= most:
-        raise sym.NotDeviceDescribable(f'{len(factors)} likelihood factors; the device takes 1..{most}')
+    single = len(factors) - len(joint)
+    if not (0 if joint else 1) <= single <= most:
+        raise sym.NotDeviceDescribable(f'{single} likelihood factors; the device takes 1..{most}')
     return factors
 
 
@@ -149,8 +158,34 @@ def _lik_params(factors, B):
     return lp, lik_batched
 
 
-def _model_struct3(tables, factors, B=1):
-    """mfs_model_nd3 of a d = 3 transition family and likelihood (include/mfs_hip.h)."""
+def _joint_struct3(joints, B=1):
+    """mfs_joint_nd3 of the joint factors of a d = 3 likelihood (include/mfs_hip.h)."""
+    batched = any(f.coef.ndim > 4 for f in joints)
+    for f in joints:
+        if f.coef.ndim > 4 and f.coef.shape[0] != B:
+            raise ValueError(f'joint likelihood factors are batched over {f.coef.shape[0]} replicates, the filter batch is {B}')
+    E = max(f.coef.shape[-1] for f in joints)
+    if E > _lib.ND3_JOINT_MAX_EXTENT:
+        raise sym.NotDeviceDescribable(f'joint polynomial extent {E} exceeds MFS_ND3_JOINT_MAX_EXTENT = '
+                                       f'{_lib.ND3_JOINT_MAX_EXTENT}')
+    lead = (B,) if batched else ()
+    coef, par = np.zeros(lead + (len(joints), 2, E, E, E)), np.zeros(lead + (len(joints),))
+    j = _lib.MfsJointNd3()
+    j.n_joint, j.extent, j.batched = len(joints), E, int(batched)
+    for i, f in enumerate(joints):
+        e = f.coef.shape[-1]
+        coef[..., i, :, :e, :e, :e] = f.coef
+        par[..., i] = f.params[..., 0]
+        j.kind[i], j.link[i], j.ycol[i] = _lib.LIK[f.kind], _lib.ND3_LINK[f.link], int(f.ycol)
+    coef, par = np.ascontiguousarray(coef), np.ascontiguousarray(par)
+    j.coef = coef.ctypes.data_as(_lib.c_double_p)
+    j.par = par.ctypes.data_as(_lib.c_double_p)
+    return j, (coef, par)
+
+
+def _model_struct3(tables, factors, B=1, ny=None):
+    """mfs_model_nd3 of a d = 3 transition family and the single-component factors of its likelihood (include/mfs_hip.h);
+    `ny` when joint factors (_joint_struct3) read further measurement columns."""
     if isinstance(factors, sym.LikelihoodSpec):
         factors = [factors]
     for f in factors:
@@ -179,7 +214,7 @@ def _model_struct3(tables, factors, B=1):
     m = _lib.MfsModelNd3()
     m.trans_kind, m.n_terms, m.extent = kind, n_terms, D
     m.n_factors = len(factors)
-    m.ny = max(f.ycol for f in factors) + 1
+    m.ny = max(f.ycol for f in factors) + 1 if ny is None else ny
     for i, f in enumerate(factors):
         m.fac_kind[i], m.fac_component[i], m.fac_ycol[i] = _lib.LIK[f.kind], int(f.component), int(f.ycol)
         m.fac_n_par[i] = int(np.asarray(f.params).shape[-1])
@@ -246,14 +281,19 @@ def _run_nd(mode, tables, factors, ys, moments_partial_order, ms0, mean0, stable
         if N is None:
             raise sym.NotDeviceDescribable(f'the device d = 3 path supports {_lib.ND3_MIN_N} <= N <= {_lib.ND3_MAX_N} '
                                            f'(got s = {s})')
-        if len(factors) > _lib.ND3_MAX_FACTORS:
+        if len([f for f in factors if not isinstance(f, sym.JointLikelihoodSpec)]) > _lib.ND3_MAX_FACTORS:
             raise sym.NotDeviceDescribable(f'{len(factors)} likelihood factors; the device takes 1..{_lib.ND3_MAX_FACTORS}')
     else:
         N = next((n for n in range(2, 8) if n * (n + 1) // 2 == s), None)
         if d != 2 or N is None:
             raise sym.NotDeviceDescribable(f'the device N-D path supports d <= 3 with 2 <= N <= 7 at d = 2, 2 <= N <= 4 '
                                            f'at d = 3 (got d = {d}, s = {s})')
+    joints = [f for f in factors if isinstance(f, sym.JointLikelihoodSpec)]
+    if joints and d != 3:
+        raise sym.NotDeviceDescribable('joint polynomial likelihood factors run at d = 3 only')
     ny = max(f.ycol for f in factors) + 1
+    if joints and ny > _lib.ND3_JOINT_MAX_NY:
+        raise sym.NotDeviceDescribable(f'{ny} measurement columns; the device takes at most {_lib.ND3_JOINT_MAX_NY}')
     ys3, squeeze = _split_ys(ys, ny)
     B, T = ys3.shape[:2]
     batched = ms0.ndim == 2
@@ -266,8 +306,13 @@ def _run_nd(mode, tables, factors, ys, moments_partial_order, ms0, mean0, stable
     if mode == 'scaled':
         scale_a = np.ascontiguousarray(np.broadcast_to(np.asarray(scale0, dtype=np.float64),
                                                        ((B, d) if batched else (d,))))
-    model, keep = (_model_struct3 if d == 3 else _model_struct)(tables, factors, B)
-    if squeeze and (model.coef_batched or model.lik_batched):
+    joint = None
+    if joints:
+        model, keep = _model_struct3(tables, [f for f in factors if f not in joints], B, ny=ny)
+        joint, keep_joint = _joint_struct3(joints, B)
+    else:
+        model, keep = (_model_struct3 if d == 3 else _model_struct)(tables, factors, B)
+    if squeeze and (model.coef_batched or model.lik_batched or (joint is not None and joint.batched)):
         raise ValueError('per-replicate model parameters need ys with a leading replicate axis')
     mi32 = np.ascontiguousarray(multi_indices, dtype=np.int32)
     inds32 = np.ascontiguousarray(inds, dtype=np.int32)
@@ -276,11 +321,16 @@ def _run_nd(mode, tables, factors, ys, moments_partial_order, ms0, mean0, stable
     out_scale = _lib.pinned_empty((B, T, d), device=device) if mode == 'scaled' else None
     out_nell, out_fn = np.empty((B,)), np.empty((B,), dtype=np.int32)
     entry = _lib.lib().mfs_filter_nd3 if d == 3 else _lib.lib().mfs_filter_nd
-    _lib.check(entry(C.byref(model), _lib.MODE[mode], N, T, B, z, _lib.ptr(mi32), _lib.ptr(inds32),
+    head = (C.byref(model),)
+    if joint is not None:
+        entry, head = _lib.lib().mfs_filter_nd3_joint, (C.byref(model), C.byref(joint))
+    _lib.check(entry(*head, _lib.MODE[mode], N, T, B, z, _lib.ptr(mi32), _lib.ptr(inds32),
                                         _lib.ptr(ms0), int(batched), _lib.ptr(mean_a), _lib.ptr(scale_a), _lib.ptr(ys3),
                                         int(bool(stable)), _lib.ptr(out_m), _lib.ptr(out_mean), _lib.ptr(out_scale),
                                         _lib.ptr(out_nell), _lib.ptr(out_fn), device, None))
     del keep
+    if joint is not None:
+        del keep_joint
     if squeeze:
         out_m, out_nell, out_fn = out_m[0], out_nell[0], out_fn[0]
         out_mean = None if out_mean is None else out_mean[0]

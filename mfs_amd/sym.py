@@ -7,6 +7,9 @@ with the placeholder objects below and reduce to small coefficient tables that t
 
   drift / dispersion / conditional mean / variance : polynomials in u, u = x or u = tanh(x)
   measurement models : Bernoulli(logistic(poly_3(x))), Poisson(softplus(l x)), Normal(l0 x + l1, var)
+  d = 3 measurement models, additionally: the same three laws of u = p, sqrt(p), arctan2(p, q) or arctan2(p, sqrt(q)), with
+                       p, q polynomials of all three state components (products and sums of different components trace to a
+                       `tme_poly_nd.PolyND`; per-variable degree <= 3)
 
 Coefficients may carry a leading batch axis (per-replicate parameters), e.g. `drift(x, p)` with `p.shape == (B,)`.
 Anything outside this class raises `NotDeviceDescribable` -- there is no CPU fallback.
@@ -16,7 +19,7 @@ import numbers
 import numpy as np
 
 __all__ = ['Poly', 'X', 'Y', 'ORDER', 'MEAN', 'SCALE', 'tanh', 'exp', 'log', 'sqrt', 'NotDeviceDescribable',
-           'LikelihoodSpec', 'as_poly', 'is_symbolic']
+           'LikelihoodSpec', 'JointLikelihoodSpec', 'arctan2', 'as_poly', 'is_symbolic']
 
 
 class NotDeviceDescribable(TypeError):
@@ -94,6 +97,54 @@ def _pad(a, deg):
     return np.concatenate([a, pad], axis=-1)
 
 
+JOINT_DIM = 3            # joint polynomial likelihood factors exist on the d = 3 path only
+JOINT_MAX_EXTENT = 4     # MFS_ND3_JOINT_MAX_EXTENT: per-variable extent (degree + 1) of a joint factor's polynomials
+_JOINT_LIMIT = ('the device takes u = p, sqrt(p), arctan2(p, q) or arctan2(p, sqrt(q)) with p, q polynomials of the state '
+                f'components of per-variable degree <= {JOINT_MAX_EXTENT - 1}')
+
+
+class _Comp(int):
+    """Index of a tagged state component that also knows the state dimension d."""
+
+    def __new__(cls, k, d):
+        self = super().__new__(cls, k)
+        self.d = d
+        return self
+
+
+def _polynd():
+    from mfs_amd.tme_poly_nd import PolyND   # (tme_poly_nd imports this module)
+    return PolyND
+
+
+def _is_joint_poly(v):
+    return type(v).__name__ == 'PolyND' and isinstance(v, _polynd())
+
+
+def to_joint_poly(v, d=JOINT_DIM):
+    """A tagged single-component Poly, a PolyND or a number as a PolyND in the d state components."""
+    PolyND = _polynd()
+    if isinstance(v, PolyND):
+        return v
+    if isinstance(v, Poly):
+        if v.coef.ndim != 1:
+            raise NotDeviceDescribable('per-replicate coefficients inside a joint likelihood factor: trace one measurement '
+                                       'model per replicate and stack them with mfs_amd.stats.batch_likelihoods')
+        if v.is_const():
+            return PolyND(np.float64(v.coef[0]), d)
+        if v.umap != 'x' or v.comp is None:
+            raise NotDeviceDescribable('a joint likelihood factor is polynomial in the tagged state components x[k]')
+        shape = [1] * d
+        shape[int(v.comp)] = v.coef.shape[0]
+        return PolyND(v.coef.reshape(shape))
+    if isinstance(v, (numbers.Real, np.floating, np.integer)) or (isinstance(v, np.ndarray) and v.ndim == 0):
+        return PolyND(np.float64(v), d)
+    if isinstance(v, np.ndarray):
+        raise NotDeviceDescribable('per-replicate coefficients inside a joint likelihood factor: trace one measurement '
+                                   'model per replicate and stack them with mfs_amd.stats.batch_likelihoods')
+    raise NotDeviceDescribable(f'{type(v).__name__} cannot enter a joint likelihood polynomial; ' + _JOINT_LIMIT)
+
+
 class Poly:
     """sum_j coef[..., j] u^j with u = x ('x'), u = tanh x ('tanh') or a constant (umap None)."""
     __array_priority__ = 1000
@@ -124,8 +175,15 @@ class Poly:
     def _merge_comp(a, b):
         if a.comp is not None and b.comp is not None and a.comp != b.comp:
             raise NotDeviceDescribable('a likelihood factor may depend on one state component only '
-                                       '(write the likelihood as a product of per-component factors)')
+                                       '(write the likelihood as a product of per-component factors); polynomials of '
+                                       f'several components are joint factors, which run at d = {JOINT_DIM} only')
         return a.comp if a.comp is not None else b.comp
+
+    @staticmethod
+    def _joint(a, b):
+        """True when a and b read different components of a d = 3 state: their sum / product is a trivariate PolyND."""
+        return (a.comp is not None and b.comp is not None and a.comp != b.comp
+                and getattr(a.comp, 'd', None) == JOINT_DIM and getattr(b.comp, 'd', None) == JOINT_DIM)
 
     @staticmethod
     def _merge_umap(a, b):
@@ -148,7 +206,11 @@ class Poly:
 
     # -- ring operations
     def __add__(self, o):
+        if _is_joint_poly(o):
+            return o + self
         o = Poly.lift(o)
+        if Poly._joint(self, o):
+            return to_joint_poly(self) + to_joint_poly(o)
         deg = max(self.degree, o.degree)
         return Poly(_pad(self.coef, deg) + _pad(o.coef, deg), Poly._merge_umap(self, o), Poly._merge_comp(self, o))
 
@@ -158,13 +220,17 @@ class Poly:
         return Poly(-self.coef, self.umap, self.comp)
 
     def __sub__(self, o):
-        return self + (-Poly.lift(o))
+        return self + (-(o if _is_joint_poly(o) else Poly.lift(o)))
 
     def __rsub__(self, o):
         return Poly.lift(o) + (-self)
 
     def __mul__(self, o):
+        if _is_joint_poly(o):
+            return o * self
         o = Poly.lift(o)
+        if Poly._joint(self, o):
+            return to_joint_poly(self) * to_joint_poly(o)
         umap = Poly._merge_umap(self, o)
         a, b = self.coef, o.coef
         shape = np.broadcast_shapes(a.shape[:-1], b.shape[:-1])
@@ -226,7 +292,7 @@ def state_vector(d: int) -> np.ndarray:
     """Object array of the d state components, each tagged with its index (N-D likelihood tracing)."""
     xs = np.empty((d,), dtype=object)
     for k in range(d):
-        xs[k] = Poly(np.array([0., 1.]), 'x', comp=k)
+        xs[k] = Poly(np.array([0., 1.]), 'x', comp=_Comp(k, d))
     return xs
 
 
@@ -273,20 +339,55 @@ class _Bearing(_Expr):  # arctan2(x[1], x[0]) of the two tagged state components
     pass
 
 
+class _JointLink(_Expr):
+    """u(x) of a d = 3 joint likelihood factor: link in {'sqrt', 'atan2', 'atan2_sqrt'} of the PolyND p (and q); `neg` marks
+    -u, which only exists on the way to logistic(u) = 1 / (1 + exp(-u))."""
+
+    def __init__(self, link, p, q=None, neg=False):
+        self.link, self.p, self.q, self.neg = link, p, q, neg
+
+    def __neg__(self):
+        return _JointLink(self.link, self.p, self.q, not self.neg)
+
+    def _refuse(self, *_a):
+        raise NotDeviceDescribable('sqrt(.) / arctan2(.) of state polynomials cannot enter further arithmetic: ' + _JOINT_LIMIT)
+
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = __pow__ = _refuse
+
+
+def _joint_dim(v):
+    """The state dimension a traced polynomial expression belongs to (None: not a tagged state expression)."""
+    if _is_joint_poly(v):
+        return v.d
+    if isinstance(v, Poly) and v.comp is not None:
+        return getattr(v.comp, 'd', None)
+    return None
+
+
 def arctan2(x1, x0):
     """numpy.arctan2 on numbers; on the traced state components x[1], x[0] (in that order, as
-    /root/reference/examples/2d_bearing_only.ipynb cell 7 writes it) the bearing of the state."""
+    /root/reference/examples/2d_bearing_only.ipynb cell 7 writes it) the bearing of the state.  At d = 3, of two polynomials
+    of the state components, or of a polynomial and the sqrt of one: the link of a joint likelihood factor."""
     if isinstance(x1, Poly) or isinstance(x0, Poly):
         ok = all(isinstance(v, Poly) and v.umap in (None, 'x') and v.degree == 1 and np.all(_pad(v.coef, 1) == [0., 1.])
                  for v in (x1, x0))
-        if not ok or x1.comp != 1 or x0.comp != 0:
-            raise NotDeviceDescribable('arctan2: the device takes arctan2(x[1], x[0]) of the plain state components')
-        return _Bearing()
+        if ok and x1.comp == 1 and x0.comp == 0:
+            return _Bearing()
+    if any(is_symbolic(v) or _is_joint_poly(v) for v in (x1, x0)):
+        if isinstance(x1, _JointLink) or (isinstance(x0, _JointLink) and (x0.link != 'sqrt' or x0.neg)):
+            raise NotDeviceDescribable('arctan2 of this composition: ' + _JOINT_LIMIT)
+        dims = {_joint_dim(v) for v in (x1, x0.p if isinstance(x0, _JointLink) else x0)} - {None}
+        if dims != {JOINT_DIM}:
+            raise NotDeviceDescribable('arctan2: the device takes arctan2(x[1], x[0]) of the plain state components; '
+                                       f'arctan2 of polynomials is a joint factor, at d = {JOINT_DIM} only')
+        if isinstance(x0, _JointLink):
+            return _JointLink('atan2_sqrt', to_joint_poly(x1), x0.p)
+        return _JointLink('atan2', to_joint_poly(x1), to_joint_poly(x0))
     return np.arctan2(x1, x0)
 
 
 def is_symbolic(v):
-    return isinstance(v, (Poly, _Expr, _Placeholder))
+    return isinstance(v, (Poly, _Expr, _Placeholder)) or _is_joint_poly(v)
 
 
 def tanh(v):
@@ -299,7 +400,7 @@ def tanh(v):
 
 
 def exp(v):
-    if isinstance(v, Poly):
+    if isinstance(v, (Poly, _JointLink)) or _is_joint_poly(v):
         return _Exp(v)
     return np.exp(v)
 
@@ -313,8 +414,12 @@ def log(v):
 
 
 def sqrt(v):
+    """numpy.sqrt on numbers; at d = 3, of a polynomial of the state components: the range link of a joint factor."""
+    if _joint_dim(v) == JOINT_DIM:
+        return _JointLink('sqrt', to_joint_poly(v))
     if is_symbolic(v):
-        raise NotDeviceDescribable('sqrt of a symbolic expression')
+        raise NotDeviceDescribable('sqrt of a symbolic expression: only sqrt(p) of a polynomial p of the state components, '
+                                   f'at d = {JOINT_DIM}; ' + _JOINT_LIMIT)
     return np.sqrt(v)
 
 
@@ -358,6 +463,49 @@ class LikelihoodSpec:
 
     def __repr__(self):
         return f'LikelihoodSpec({self.kind}, params shape {self.params.shape}, x[{self.component}], y[{self.ycol}])'
+
+
+class JointLikelihoodSpec(LikelihoodSpec):
+    """A d = 3 factor of all three state components (mfs_joint_nd3): kind(y; u(x), par) with u = link(p, q).  coef is
+    (..., 2, E, E, E): block 0 is p, block 1 is q (zeros without one), entry [a][b][c] multiplies x0^a x1^b x2^c; params
+    (..., 1) the Gaussian variance (0 for the other kinds)."""
+    LINKS = {'poly': 0, 'sqrt': 1, 'atan2': 2, 'atan2_sqrt': 3}
+    ALL = 3   # .component of a joint factor
+
+    def __init__(self, kind, link, coef, par=0., ycol=0):
+        assert link in self.LINKS and kind != 'bearing_gaussian'
+        par = np.asarray(par, dtype=np.float64)
+        super().__init__(kind, par[..., None], component=self.ALL, ycol=ycol)
+        self.link = link
+        self.coef = np.asarray(coef, dtype=np.float64)
+
+    def __repr__(self):
+        return f'JointLikelihoodSpec({self.kind}, {self.link}, extent {self.coef.shape[-1]}, y[{self.ycol}])'
+
+
+def joint_spec(kind, u, par, ycol):
+    """JointLikelihoodSpec of `kind` applied to the traced u: a PolyND (link 'poly') or a _JointLink."""
+    if isinstance(u, _JointLink):
+        if u.neg:
+            raise NotDeviceDescribable('the negative of sqrt(.) / arctan2(.) as a likelihood argument: ' + _JOINT_LIMIT)
+        link, polys = u.link, [u.p, u.q]
+    else:
+        link, polys = 'poly', [to_joint_poly(u), None]
+    polys = [None if p is None else p.trimmed() for p in polys]
+    if any(p is not None and p.d != JOINT_DIM for p in polys):
+        raise NotDeviceDescribable(f'joint likelihood factors run at d = {JOINT_DIM} only')
+    E = max(max(p.coef.shape) for p in polys if p is not None)
+    if E > JOINT_MAX_EXTENT:
+        raise NotDeviceDescribable(f'a joint likelihood polynomial of per-variable degree {E - 1} exceeds the device limit '
+                                   f'MFS_ND3_JOINT_MAX_EXTENT - 1 = {JOINT_MAX_EXTENT - 1}')
+    coef = np.zeros((2, E, E, E))
+    for w, p in enumerate(polys):
+        if p is not None:
+            coef[(w,) + tuple(slice(0, n) for n in p.coef.shape)] = p.coef
+    if np.ndim(par) != 0:
+        raise NotDeviceDescribable('per-replicate noise levels of a joint likelihood factor: trace one measurement model per '
+                                   'replicate and stack them with mfs_amd.stats.batch_likelihoods')
+    return JointLikelihoodSpec(kind, link, coef, par, ycol)
 
 
 class LikelihoodProduct:

@@ -22,6 +22,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
+from mfs_amd import sym
 from mfs_amd.sym import NotDeviceDescribable
 
 
@@ -53,6 +54,8 @@ class PolyND:
             return o
         if isinstance(o, (int, float, np.floating, np.integer)):
             return PolyND(np.float64(o), self.d)
+        if isinstance(o, sym.Poly):      # a tagged state component of a traced likelihood (sym.state_vector)
+            return sym.to_joint_poly(o, self.d)
         raise NotDeviceDescribable(f'{type(o).__name__} cannot enter a polynomial drift / dispersion expression')
 
     @staticmethod
