@@ -181,6 +181,15 @@ int mfs_plan_1d_destroy(mfs_plan_1d* plan);
 /* launch geometry actually used (for DESIGN.md / the bench JSON): lanes per filter, filters per block, grid size */
 int mfs_plan_1d_geometry(const mfs_plan_1d* plan, int* lanes_per_filter, int* filters_per_block, int* grid,
                          int* lds_bytes_per_block);
+/* which build of the 1-D filter kernel the plan launches, decided at plan creation.  The specialised one-wave build keeps
+ * the model's coefficient table in registers and runs the two halves of a step as straight-line code; it exists for the
+ * orders with a one-wave build (N = 14..16), operator tables of 2 / 4 / 6 terms and normal closures of polynomial degree
+ * <= 3, and computes bit for bit what the generic build computes (MFS_FAST_BUILD=generic keeps the generic one). */
+#define MFS_BUILD_DENSE 0
+#define MFS_BUILD_FAST 1
+#define MFS_BUILD_FAST_ONE_WAVE 2
+#define MFS_BUILD_FAST_ONE_WAVE_SPEC 3
+int mfs_plan_1d_kernel_build(const mfs_plan_1d* plan, int* build);
 
 /*
  * ---- negative log-likelihood and its gradient, forward mode inside the time loop ------------------------------------

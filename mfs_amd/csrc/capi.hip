@@ -22,6 +22,7 @@ Filter1dFastLaunch g_fast_filter[MFS_MAX_N + 1][4];
 Filter1dFastLaunch g_fast_filter_wide[MFS_MAX_N + 1][4];
 Filter1dFastLaunch g_fast_filter_ext[MFS_MAX_N + 1][4];
 Filter1dFastLaunch g_fast_filter_ext_wide[MFS_MAX_N + 1][4];
+Filter1dFastLaunch g_fast_filter_spec[MFS_MAX_N + 1][kSpecShapes];   // [N][spec_shape_index]: filter1d_spec_inst.hip
 int g_fast_ext_shift[MFS_MAX_N + 1][4];
 Quad1dLaunch g_quad_ext[MFS_MAX_N + 1][4];
 int g_quad_ext_lds[MFS_MAX_N + 1][4];
@@ -114,6 +115,7 @@ struct mfs_plan_1d {
     int slot, G, fpb, grid, lds_bytes, lds_doubles;
     bool single_wave_per_simd = false;
     bool ext = false;               // fast path, extended variant (stable = 1 or an odd moment count)
+    mfs::Filter1dFastLaunch spec = nullptr;   // specialised one-wave build for this model's table shape, if there is one
     double* d_coef = nullptr;
     double* d_lik = nullptr;
     double* c_mom = nullptr;
@@ -252,6 +254,15 @@ int mfs_plan_1d_create(mfs_plan_1d** plan, const mfs_model_1d* model, int mode, 
                                    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
                                    p->grid <= 4 * cus);
     }
+    // One wave per SIMD, plain kernel, default lane count, and a table shape that has a specialised build (table in
+    // registers, straight-line halves: filter1d_fast.hpp): decided here, once per plan.  MFS_FAST_BUILD=generic keeps the
+    // generic one-wave build (A/B switch, like MFS_PREDICT_RULE).
+    if (p->single_wave_per_simd && !p->ext && ((model->degree + 4) & ~3) <= mfs::kSpecTop &&
+        p->G == ((N + 1 <= 16) ? 16 : 32)) {
+        const int shape = mfs::spec_shape_index((model->trans_kind == MFS_TRANS_OPERATOR) ? model->n_terms : -1);
+        const char* e = getenv("MFS_FAST_BUILD");
+        if (shape >= 0 && !(e && strcmp(e, "generic") == 0)) p->spec = mfs::g_fast_filter_spec[N][shape];   // null for N outside 14..16
+    }
 
     const size_t ncoef = (size_t)(model->coef_batched ? B : 1) * model->n_rows * (model->degree + 1);
     const size_t nlik = (size_t)(model->lik_batched ? B : 1) * model->n_lik;
@@ -288,8 +299,17 @@ int mfs_plan_1d_geometry(const mfs_plan_1d* p, int* lanes_per_filter, int* filte
     return MFS_OK;
 }
 
+int mfs_plan_1d_kernel_build(const mfs_plan_1d* p, int* build) {
+    if (!p || !build) return fail(MFS_EINVAL, "plan or build is NULL");
+    const bool wide = p->slot >= 3 && p->single_wave_per_simd &&
+                      (p->ext ? mfs::g_fast_filter_ext_wide : mfs::g_fast_filter_wide)[p->N][p->slot - 3] != nullptr;
+    *build = (p->slot < 3) ? MFS_BUILD_DENSE : p->spec ? MFS_BUILD_FAST_ONE_WAVE_SPEC : wide ? MFS_BUILD_FAST_ONE_WAVE : MFS_BUILD_FAST;
+    return MFS_OK;
+}
+
 static hipError_t launch_filter(mfs_plan_1d* p, const mfs::Filter1dArgs& a, hipStream_t s) {
     if (p->slot >= 3) {
+        if (p->spec) return p->spec(a, p->grid, p->lds_doubles, s);
         const mfs::Filter1dFastLaunch wide = (p->ext ? mfs::g_fast_filter_ext_wide : mfs::g_fast_filter_wide)[p->N][p->slot - 3];
         const mfs::Filter1dFastLaunch narrow = (p->ext ? mfs::g_fast_filter_ext : mfs::g_fast_filter)[p->N][p->slot - 3];
         return (wide && p->single_wave_per_simd ? wide : narrow)(a, p->grid, p->lds_doubles, s);

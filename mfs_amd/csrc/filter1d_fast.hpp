@@ -37,7 +37,7 @@ namespace mfs {
 
 #ifdef MFS_1D_STAMPS
 // diagnostic build only (scratch/): cycles per phase accumulated by lane 0 of block 0
-__device__ unsigned long long g_1d_stamps[16];
+__device__ unsigned long long g_1d_stamps[32];
 #define F1_STAMP(slot) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long now_ = clock64(); g_1d_stamps[slot] += now_ - t_last_; t_last_ = now_; } } while (0)
 #define F1_STAMP_BEGIN unsigned long long t_last_ = clock64()
 #else
@@ -258,6 +258,9 @@ __device__ __forceinline__ void horner_rows(const double* __restrict__ table, co
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = 0.0;
     for (int jb = top - 4; jb >= 0; jb -= 4) {
+#ifdef MFS_1D_STAMPS
+        const unsigned long long t_blk_ = clock64();
+#endif
         const double* t = table + jb * kCoefRows;
         double cj[4][R];
 #pragma unroll
@@ -265,11 +268,27 @@ __device__ __forceinline__ void horner_rows(const double* __restrict__ table, co
 #pragma unroll
             for (int r = 0; r < R; ++r) cj[q][r] = t[q * kCoefRows + r];
         __builtin_amdgcn_sched_barrier(0);
+#ifdef MFS_1D_STAMPS
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // slot 14: issue of the block's reads + their latency
+        if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[14] += clock64() - t_blk_;
+#endif
 #pragma unroll
         for (int q = 3; q >= 0; --q)
 #pragma unroll
             for (int r = 0; r < R; ++r) acc[r] = fma(acc[r], u, cj[q][r]);
     }
+}
+
+// The same recurrences on a table held in registers (the specialised one-wave builds of the filter kernel): TOPD padded
+// degrees, R live rows, the operations of horner_rows on those rows in the same order.
+template <int TOPD, int R>
+__device__ __forceinline__ void horner_regs(const double (&tab)[TOPD][R], const double u, double (&acc)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = 0.0;
+#pragma unroll
+    for (int q = TOPD - 1; q >= 0; --q)
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = fma(acc[r], u, tab[q][r]);
 }
 
 __device__ __forceinline__ double rcp_nr(const double v) {
@@ -624,7 +643,7 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
         Vr[j] = fma(sy, delta, sy);
     });
 
-    F1_STAMP(1);
+    F1_STAMP(recentre ? 16 : 1);   // (recentre = the update half)
     double lam = 0.0, w = 0.0;
     double a[N], b2[N];              // the Jacobi matrix of the rule: diagonal and squared sub-diagonal (group-uniform)
     bool use_atoms = atoms, twisted = false;
@@ -863,8 +882,27 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
 // EXT = the extended variant: stable = 1 (LDL^T completion where a pivot is not > 0, see quadrature_fast) and odd moment
 // counts (`extra`: one more moment per step, formed in the update and never read by a rule, filtering.py:65-66).  A separate
 // instantiation, so that the plain kernel's registers and instruction stream are untouched.
-template <int N, int G, int WPB, int OCC, bool EXT = false>
+// SPEC = the specialised one-wave builds (OCC = 1 leaves ~240 of the 512 registers idle), chosen by the plan from the model's
+// table shape: k > 0 = operator table with k terms, -1 = normal closure, both with at most kSpecTop padded degrees; 0 = the
+// generic build.  A specialised build (i) keeps the live rows of the coefficient table -- time-invariant for the whole
+// launch -- in registers, so the Horner pass of the predict half reads no LDS and evaluates no dead row, and (ii) runs the
+// two halves of a step as two straight-line bodies, each compiled for its half: with the posterior-atoms rule the predict
+// half's elimination keeps only what the poison decision needs (the pivots; no sub-diagonal broadcasts, no pivot
+// reciprocals for the Jacobi matrix).  The arithmetic that feeds an output is the generic build's, operation for operation.
+// (A/B switches of the specialised builds, each measured against the full specialisation on the headline:
+//  MFS_SPEC_AB_TABLE 0 = the table in registers, 1 = the LDS Horner pass; MFS_SPEC_AB_HALVES 0 = two straight-line halves,
+//  1 = the run-time loop over the halves.  DESIGN.md section 6.  The dead rows need no switch: with the number of terms a
+//  compile-time constant the compiler drops their loads and multiply-adds on either table route.)
+#ifndef MFS_SPEC_AB_TABLE
+#define MFS_SPEC_AB_TABLE 0
+#endif
+#ifndef MFS_SPEC_AB_HALVES
+#define MFS_SPEC_AB_HALVES 0
+#endif
+template <int N, int G, int WPB, int OCC, bool EXT = false, int SPEC = 0>
 __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filter1dArgs a, const int lds_doubles) {
+    static_assert(SPEC == 0 || (!EXT && OCC == 1), "specialised builds: plain kernel, one wave per SIMD");
+    static_assert(SPEC >= -1 && SPEC <= MFS_MAX_TERMS, "table shape");
     using L = FastTile<N, G>;
     constexpr int M2 = L::M2, TLD = L::TLD;
     constexpr int kShift = EXT ? L::kExtShift : 0;
@@ -914,6 +952,20 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
         first_nan = a.c_first_nan[b];
     }
     wave_sync();
+    // the table shape a specialised build knows at compile time
+    const int trans_kind = (SPEC > 0) ? MFS_TRANS_OPERATOR : (SPEC < 0) ? MFS_TRANS_GAUSSIAN : a.trans_kind;
+    const int n_terms = (SPEC > 0) ? SPEC : a.n_terms;
+    constexpr bool kRegTable = (SPEC != 0) && (MFS_SPEC_AB_TABLE == 0);
+    // live rows: the operator terms + the variance row (LDS row MFS_MAX_TERMS), or mean and variance
+    constexpr int SR = (SPEC > 0) ? SPEC + 1 : 2;
+    constexpr int kVarReg = (SPEC > 0) ? SPEC : -1;     // the register row that holds LDS row MFS_MAX_TERMS
+    double tabr[kSpecTop][SR];
+    if constexpr (kRegTable) {
+#pragma unroll
+        for (int q = 0; q < kSpecTop; ++q)
+#pragma unroll
+            for (int r = 0; r < SR; ++r) tabr[q][r] = coef[q * kCoefRows + ((r == kVarReg) ? MFS_MAX_TERMS : r)];
+    }
     const double* yrow = a.ys + (size_t)b * a.T;
     bool dead = (first_nan >= 0);
     const double qnan = __builtin_nan("");
@@ -957,8 +1009,9 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
         if (!dead) {
             int bad = 0;
             double gB = qnan;
-#pragma nounroll
-            for (int half = 0; half < 2; ++half) {
+            // one half of the step; `half` and `atoms_ok` are run-time values in the generic build and compile-time constants
+            // in the specialised ones
+            auto half_step = [&](const auto half, const auto atoms_ok) __attribute__((always_inline)) {
                 double x, w;
                 double lam_io = (half == 0) ? gA : gB;
 #ifdef MFS_1D_STAMPS
@@ -966,7 +1019,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
 #endif
                 // predict half: the rule of the posterior moments is the posterior's own atoms (see quadrature_fast); the
                 // reference's recomputation stays available as an A/B switch
-                const bool atoms = (half == 0) & have_atoms & (a.recompute_rule == 0);
+                const bool atoms = (half == 0) && (bool)atoms_ok;
 #ifdef MFS_EXT_DEBUG
                 quadrature_fast<N, G, EXT>(mom, l, grp, mean, scale, x, w, lam_io, half == 1, atoms, gW, S, a.stable, dbg_dense);
 #else
@@ -980,12 +1033,23 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                 const double u = (a.umap == MFS_U_TANH) ? fast_tanh(x) : x;
                 double c = 0.0, inv_sc = 1.0, py = 1.0, ipy = 1.0;
                 if (half == 0) {
+                    F1_STAMP(13);
                     // ---- prediction (filtering.py:76-79 / 144-148 / 221-225)
                     // every row of the model table at this lane's node, in one pass over the degrees
                     double rows[MFS_MAX_TERMS + 1];
-                    horner_rows<MFS_MAX_TERMS + 1>(coef, a.degree, u, rows);
+                    if constexpr (kRegTable) {
+                        double live[SR];
+                        horner_regs<kSpecTop, SR>(tabr, u, live);
+#pragma unroll
+                        for (int r = 0; r <= MFS_MAX_TERMS; ++r) rows[r] = 0.0;
+#pragma unroll
+                        for (int r = 0; r < SR; ++r) rows[(r == kVarReg) ? MFS_MAX_TERMS : r] = live[r];
+                    } else {
+                        horner_rows<MFS_MAX_TERMS + 1>(coef, a.degree, u, rows);
+                    }
+                    F1_STAMP(15);
                     double mu, var;
-                    if (a.trans_kind == MFS_TRANS_OPERATOR) {
+                    if (trans_kind == MFS_TRANS_OPERATOR) {
                         mu = x + rows[0];
                         var = rows[MFS_MAX_TERMS];
                     } else {
@@ -1000,12 +1064,13 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                             inv_sc = 1.0 / scale;
                         }
                     }
+                    F1_STAMP(18);
                     double* row = TAB + l * TLD;   // spare lanes own spare rows: every store below is unconditional
-                    if (a.trans_kind == MFS_TRANS_OPERATOR) {
+                    if (trans_kind == MFS_TRANS_OPERATOR) {
                         // E[(X'-c)^n | x] = sum_k Q_k(u) n!/(n-k)! (x-c)^(n-k) = sum_k (k! Q_k) C(n,k) dx^(n-k);
                         // E_k(n) = C(n,k) dx^(n-k) advances in n by Pascal's rule E_k(n+1) = dx E_k(n) + E_{k-1}(n)
                         // (moments.py:141-179).  Unrolled for the number of operator terms the model really has.
-                        switch (a.n_terms) {
+                        switch (n_terms) {
                             case 2: operator_moments<2, M2>(rows, x - c, w, inv_sc, node, row); break;
                             case 4: operator_moments<4, M2>(rows, x - c, w, inv_sc, node, row); break;
                             case 6: operator_moments<6, M2>(rows, x - c, w, inv_sc, node, row); break;
@@ -1033,6 +1098,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                     const double wl = node ? w * likelihood_fast(a.lik_kind, lp, lfac, y, x) : 0.0;
                     py = gsum<G>(wl);
                     ipy = rcp_nr(py);
+                    F1_STAMP(17);
                     if (a.mode != MFS_MODE_RAW) {
                         mean = gsum<G>(wl * x) * ipy;
                         c = mean;
@@ -1085,10 +1151,19 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                     out0 = acc0; out1 = acc1;     // (with an odd count out1 of lane 2N - G is the order-2N moment: written out, never carried)
                 }
                 wave_sync();
-                F1_STAMP(7);
+                F1_STAMP((half == 0) ? 7 : 8);
 #ifdef MFS_1D_STAMPS
                 if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[9] += 1;
 #endif
+            };
+            if constexpr (SPEC != 0 && MFS_SPEC_AB_HALVES == 0) {
+                if (have_atoms & (a.recompute_rule == 0)) half_step(std::integral_constant<int, 0>{}, std::true_type{});
+                else half_step(std::integral_constant<int, 0>{}, std::false_type{});   // the first step of a run; MFS_PREDICT_RULE=recompute
+                half_step(std::integral_constant<int, 1>{}, std::false_type{});
+            } else {
+                const bool atoms_ok = have_atoms & (a.recompute_rule == 0);
+#pragma nounroll
+                for (int half = 0; half < 2; ++half) half_step(half, atoms_ok);
             }
             bad |= (int)(!finite(nell) || !finite(mean) || !finite(scale));
             if (gany<G>(bad != 0, grp)) { dead = true; first_nan = t; }

@@ -606,5 +606,11 @@ struct KernelEntry {
 // [6] fast path with G = 8 (N <= 7: eight filters per wavefront)
 constexpr int kSlots = 7;
 using Filter1dFastLaunch = hipError_t (*)(const Filter1dArgs&, int grid, int lds_doubles_per_filter, hipStream_t);
+// specialised one-wave builds of the fast kernel (filter1d_fast.hpp, SPEC): tables of at most kSpecTop padded degrees, in
+// kSpecShapes row shapes
+constexpr int kSpecTop = 4;
+constexpr int kSpecShapes = 4;
+// slot of a table shape among them (-1 = normal closure, 2 / 4 / 6 = operator terms), or -1 if the shape has no such build
+constexpr int spec_shape_index(const int spec) { return (spec == -1) ? 0 : (spec == 2) ? 1 : (spec == 4) ? 2 : (spec == 6) ? 3 : -1; }
 
 }  // namespace mfs

@@ -1,0 +1,37 @@
+// filter1d_spec_inst.hip -- the specialised one-wave-per-SIMD builds of the fast 1-D kernel (SPEC template parameter of
+// filter1d_fast_kernel: coefficient table in registers, live rows only, straight-line halves) for one quadrature order
+// MFS_SPEC_N in 14..16, the only orders that have a one-wave build.  One translation unit per order so that `make -j`
+// compiles them next to the order ranges of filter1d_inst.hip.
+#include "filter1d_fast.hpp"
+#include "launch_util.hpp"
+
+#ifndef MFS_SPEC_N
+#error "compile with -DMFS_SPEC_N=14..16"
+#endif
+
+namespace mfs {
+
+extern Filter1dFastLaunch g_fast_filter_spec[MFS_MAX_N + 1][kSpecShapes];  // defined in capi.hip
+
+template <int N, int G, int SPEC>
+hipError_t launch_filter_spec(const Filter1dArgs& a, int grid, int lds_doubles, hipStream_t s) {
+    if (hipError_t e = ensure_dynamic_lds<&filter1d_fast_kernel<N, G, 1, 1, false, SPEC>>(); e != hipSuccess) return e;
+    hipLaunchKernelGGL((filter1d_fast_kernel<N, G, 1, 1, false, SPEC>), dim3(grid), dim3(64), (64 / G) * lds_doubles * 8, s, a,
+                       lds_doubles);
+    return hipGetLastError();
+}
+
+struct SpecRegistrar {
+    SpecRegistrar() {
+        constexpr int N = MFS_SPEC_N;
+        static_assert(N >= 14 && N <= 16, "orders with a one-wave build");
+        constexpr int G = (N + 1 <= 16) ? 16 : 32;   // the default lane count of the order, as for g_fast_filter_wide
+        g_fast_filter_spec[N][spec_shape_index(-1)] = &launch_filter_spec<N, G, -1>;
+        g_fast_filter_spec[N][spec_shape_index(2)] = &launch_filter_spec<N, G, 2>;
+        g_fast_filter_spec[N][spec_shape_index(4)] = &launch_filter_spec<N, G, 4>;
+        g_fast_filter_spec[N][spec_shape_index(6)] = &launch_filter_spec<N, G, 6>;
+    }
+};
+static SpecRegistrar spec_registrar_instance;
+
+}  // namespace mfs

@@ -18,10 +18,11 @@ cp "$(ls "$RAW"/kt/*/*kernel_stats.csv | head -1)" "$ROOT/$OUT/kernel_stats.csv"
 i=0
 for PMC in "FETCH_SIZE" "WRITE_SIZE" \
            "SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INSTS_SALU SQ_INSTS_LDS" \
-           "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
+           "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
+           "SQC_ICACHE_REQ SQC_ICACHE_MISSES"; do
     i=$((i + 1))
     rocprofv3 --pmc $PMC --output-format csv -d "$RAW/pmc$i" -- $BENCH > /dev/null
 done
-python3 "$ROOT/tools/pmc_summary.py" "$KERNEL" "$WORKLOAD" "$ROOT/$OUT/pmc.json" "$RAW"/pmc1 "$RAW"/pmc2 "$RAW"/pmc3 "$RAW"/pmc4 > /dev/null
+python3 "$ROOT/tools/pmc_summary.py" "$KERNEL" "$WORKLOAD" "$ROOT/$OUT/pmc.json" "$RAW"/pmc1 "$RAW"/pmc2 "$RAW"/pmc3 "$RAW"/pmc4 "$RAW"/pmc5 > /dev/null
 head -4 "$ROOT/$OUT/kernel_stats.csv"
 cat "$ROOT/$OUT/pmc.json"
