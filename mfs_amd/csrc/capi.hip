@@ -14,32 +14,12 @@
 #include "filternd_kernel.hpp"
 #include "filternd3_kernel.hpp"
 #include "filter1d_grad.hpp"
-#include "pool.hpp"
+#include "registry.hpp"
+#include "staging.hpp"
 
 namespace mfs {
-KernelEntry g_table[MFS_MAX_N + 1][kSlots];  // filled by the static registrars in filter1d_inst.hip
-Filter1dFastLaunch g_fast_filter[MFS_MAX_N + 1][4];
-Filter1dFastLaunch g_fast_filter_wide[MFS_MAX_N + 1][4];
-Filter1dFastLaunch g_fast_filter_ext[MFS_MAX_N + 1][4];
-Filter1dFastLaunch g_fast_filter_ext_wide[MFS_MAX_N + 1][4];
-Filter1dFastLaunch g_fast_filter_spec[MFS_MAX_N + 1][kSpecShapes];   // [N][spec_shape_index]: filter1d_spec_inst.hip
-int g_fast_ext_shift[MFS_MAX_N + 1][4];
-Quad1dLaunch g_quad_ext[MFS_MAX_N + 1][4];
-int g_quad_ext_lds[MFS_MAX_N + 1][4];
-using Cf1dLaunch = hipError_t (*)(const Cf1dArgs&, int grid, int lds, hipStream_t);
-Cf1dLaunch g_cf[MFS_MAX_N + 1][4];
-using FilterNdLaunch = hipError_t (*)(const FilterNdArgs&, int grid, hipStream_t);
-struct NdEntry { FilterNdLaunch launch, launch_gauss, launch_hi, launch_joint; int S, Z, lds_bytes, carry_doubles; };
-extern NdEntry g_nd_table[8];  // filternd_inst.hip
-using FilterNd3Launch = hipError_t (*)(const FilterNd3Args&, int grid, hipStream_t);
-using FilterNd3JointLaunch = hipError_t (*)(const FilterNd3Args&, const FilterNd3Joint&, int grid, hipStream_t);
-struct Nd3Entry { FilterNd3Launch launch, launch_gauss; int S, Z, lds_bytes; FilterNd3JointLaunch joint, joint_gauss; };
-extern Nd3Entry g_nd3_table[MFS_ND3_MAX_N + 1];  // filternd3_inst.hip
-hipError_t launch_elementary(int which, int n, const double* d_x, double* d_out, hipStream_t s);
-extern Filter1dGradLaunch g_grad_table[17][5];  // filter1d_grad_inst.hip: [N <= 16][P <= 4]
-}
-
-namespace {
+KernelEntry g_table[MFS_MAX_N + 1][kSlots];
+FastEntry g_fast[MFS_MAX_N + 1][4];
 
 thread_local std::string g_err;
 
@@ -52,6 +32,11 @@ int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
+}  // namespace mfs
+
+namespace {
+
+using mfs::fail;
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -99,7 +84,7 @@ int pick_slot(int N, int stable, int odd_tail = 0) {
         else if (want == 16 && N <= 16) gi = 0;
         return gi;
     }
-    int gi = (N + 1 <= 8) ? 3 : (N + 1 <= 16) ? 0 : (N + 1 <= 32) ? 1 : 2;
+    int gi = mfs::default_group(N);
     if (want == 64) gi = 2;
     else if (want == 32 && N + 1 <= 32) gi = 1;
     else if (want == 16 && N + 1 <= 16) gi = 0;
@@ -107,15 +92,25 @@ int pick_slot(int N, int stable, int odd_tail = 0) {
     return 3 + gi;
 }
 
+// what every run needs of its data pointers, device or host (ys only where there is a measurement to read)
+int check_run_pointers(int mode, const double* m0, const double* mean0, const double* scale0, const double* ys,
+                       const double* out_nell, int T, int B) {
+    if (!m0 || !out_nell || (T > 0 && B > 0 && !ys)) return fail(MFS_EINVAL, "m0 / ys / out_nell must not be NULL");
+    if (mode != MFS_MODE_RAW && !mean0) return fail(MFS_EINVAL, "mean0 is required in central and scaled modes");
+    if (mode == MFS_MODE_SCALED && !scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    return MFS_OK;
+}
+
 }  // namespace
 
 struct mfs_plan_1d {
     mfs_model_1d model;  // device pointers inside
     int mode, N, T, B, stable, chunk, device, extra;
-    int slot, G, fpb, grid, lds_bytes, lds_doubles;
-    bool single_wave_per_simd = false;
-    bool ext = false;               // fast path, extended variant (stable = 1 or an odd moment count)
-    mfs::Filter1dFastLaunch spec = nullptr;   // specialised one-wave build for this model's table shape, if there is one
+    int G, fpb, grid, lds_bytes, lds_doubles;
+    // the kernel build the plan runs, resolved once at creation (resolve_launch): its launcher, the launcher's LDS argument
+    // (bytes per block for the dense path, doubles per filter for the fast one) and its MFS_BUILD_* code
+    mfs::Filter1dLaunch launch = nullptr;
+    int launch_lds = 0, build = MFS_BUILD_DENSE;
     double* d_coef = nullptr;
     double* d_lik = nullptr;
     double* c_mom = nullptr;
@@ -135,7 +130,7 @@ struct mfs_plan_1d {
 extern "C" {
 
 int mfs_version(void) { return MFS_ABI_VERSION; }
-const char* mfs_last_error(void) { return g_err.c_str(); }
+const char* mfs_last_error(void) { return mfs::g_err.c_str(); }
 
 int mfs_device_count(int* count) {
     if (!count) return fail(MFS_EINVAL, "count is NULL");
@@ -216,6 +211,31 @@ int mfs_plan_1d_destroy(mfs_plan_1d* p) {
     return MFS_OK;
 }
 
+// The one place that picks the kernel build of a 1-D plan.  Dense slot: its LDS-tile kernel.  Fast slot: blocks are single
+// waves, so with at most one per SIMD (grid <= 4 x compute units) the wide-register one-wave builds cost nothing -- the
+// specialised one (table in registers, straight-line halves: filter1d_fast.hpp) where the plain kernel's table shape has
+// one, else the generic one where the order has one; otherwise the two-wave build.  MFS_FAST_BUILD=generic skips the
+// specialised builds (A/B switch, like MFS_PREDICT_RULE).
+static void resolve_launch(mfs_plan_1d* p, int slot, bool ext) {
+    if (slot < 3) {
+        p->launch = mfs::g_table[p->N][slot].filter; p->launch_lds = p->lds_bytes; p->build = MFS_BUILD_DENSE;
+        return;
+    }
+    const mfs::FastEntry& fe = mfs::g_fast[p->N][slot - 3];
+    int cus = 0;   // (hipDeviceGetAttribute: one integer, not the whole property structure, per plan)
+    const bool one_wave = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess &&
+                          p->grid <= 4 * cus;
+    mfs::Filter1dFastLaunch spec = nullptr, wide = one_wave ? (ext ? fe.ext_wide : fe.wide) : nullptr;
+    if (one_wave && !ext && ((p->model.degree + 4) & ~3) <= mfs::kSpecTop) {
+        const int shape = mfs::spec_shape_index((p->model.trans_kind == MFS_TRANS_OPERATOR) ? p->model.n_terms : -1);
+        const char* e = getenv("MFS_FAST_BUILD");
+        if (shape >= 0 && !(e && strcmp(e, "generic") == 0)) spec = fe.spec[shape];   // null but for the default group of N = 14..16
+    }
+    p->launch = spec ? spec : wide ? wide : ext ? fe.ext : fe.filter;
+    p->launch_lds = p->lds_doubles;
+    p->build = spec ? MFS_BUILD_FAST_ONE_WAVE_SPEC : wide ? MFS_BUILD_FAST_ONE_WAVE : MFS_BUILD_FAST;
+}
+
 int mfs_plan_1d_create(mfs_plan_1d** plan, const mfs_model_1d* model, int mode, int N, int T, int B, int stable,
                        int chunk, int device) {
     if (!plan) return fail(MFS_EINVAL, "plan is NULL");
@@ -236,33 +256,18 @@ int mfs_plan_1d_create(mfs_plan_1d** plan, const mfs_model_1d* model, int mode, 
     p->model = *model;
     p->mode = mode; p->N = N; p->T = T; p->B = B; p->stable = stable; p->device = device; p->extra = extra;
     p->chunk = (chunk == 0 || chunk > T) ? T : chunk;
-    p->slot = slot;
     p->G = ke.lanes_per_filter;
     p->fpb = ke.waves_per_block * (64 / p->G);
     p->grid = (B + p->fpb - 1) / p->fpb;
     p->lds_doubles = ke.lds_doubles_per_filter;
     if (slot >= 3) p->lds_doubles += ((model->degree + 4) & ~3) * 10;  // fast path: + model table [ceil4(degree + 1)][kCoefRows]
-    p->ext = slot >= 3 && (stable != 0 || extra != 0);
-    if (p->ext) {
-        if (!mfs::g_fast_filter_ext[N][slot - 3]) { delete p; return fail(MFS_EUNSUPPORTED, "no extended kernel for N = %d", N); }
-        p->lds_doubles += mfs::g_fast_ext_shift[N][slot - 3];
+    const bool ext = slot >= 3 && (stable != 0 || extra != 0);   // fast path, extended variant
+    if (ext) {
+        if (!mfs::g_fast[N][slot - 3].ext) { delete p; return fail(MFS_EUNSUPPORTED, "no extended kernel for N = %d", N); }
+        p->lds_doubles += mfs::g_fast[N][slot - 3].ext_shift;
     }
     p->lds_bytes = p->fpb * p->lds_doubles * 8;
-    {   // blocks of the fast path are single waves: with at most one per SIMD the wide-register variant costs nothing
-        int cus = 0;   // (hipDeviceGetAttribute: one integer, not the whole property structure, per plan)
-        p->single_wave_per_simd = (slot >= 3 &&
-                                   hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
-                                   p->grid <= 4 * cus);
-    }
-    // One wave per SIMD, plain kernel, default lane count, and a table shape that has a specialised build (table in
-    // registers, straight-line halves: filter1d_fast.hpp): decided here, once per plan.  MFS_FAST_BUILD=generic keeps the
-    // generic one-wave build (A/B switch, like MFS_PREDICT_RULE).
-    if (p->single_wave_per_simd && !p->ext && ((model->degree + 4) & ~3) <= mfs::kSpecTop &&
-        p->G == ((N + 1 <= 16) ? 16 : 32)) {
-        const int shape = mfs::spec_shape_index((model->trans_kind == MFS_TRANS_OPERATOR) ? model->n_terms : -1);
-        const char* e = getenv("MFS_FAST_BUILD");
-        if (shape >= 0 && !(e && strcmp(e, "generic") == 0)) p->spec = mfs::g_fast_filter_spec[N][shape];   // null for N outside 14..16
-    }
+    resolve_launch(p, slot, ext);
 
     const size_t ncoef = (size_t)(model->coef_batched ? B : 1) * model->n_rows * (model->degree + 1);
     const size_t nlik = (size_t)(model->lik_batched ? B : 1) * model->n_lik;
@@ -301,36 +306,19 @@ int mfs_plan_1d_geometry(const mfs_plan_1d* p, int* lanes_per_filter, int* filte
 
 int mfs_plan_1d_kernel_build(const mfs_plan_1d* p, int* build) {
     if (!p || !build) return fail(MFS_EINVAL, "plan or build is NULL");
-    const bool wide = p->slot >= 3 && p->single_wave_per_simd &&
-                      (p->ext ? mfs::g_fast_filter_ext_wide : mfs::g_fast_filter_wide)[p->N][p->slot - 3] != nullptr;
-    *build = (p->slot < 3) ? MFS_BUILD_DENSE : p->spec ? MFS_BUILD_FAST_ONE_WAVE_SPEC : wide ? MFS_BUILD_FAST_ONE_WAVE : MFS_BUILD_FAST;
+    *build = p->build;
     return MFS_OK;
-}
-
-static hipError_t launch_filter(mfs_plan_1d* p, const mfs::Filter1dArgs& a, hipStream_t s) {
-    if (p->slot >= 3) {
-        if (p->spec) return p->spec(a, p->grid, p->lds_doubles, s);
-        const mfs::Filter1dFastLaunch wide = (p->ext ? mfs::g_fast_filter_ext_wide : mfs::g_fast_filter_wide)[p->N][p->slot - 3];
-        const mfs::Filter1dFastLaunch narrow = (p->ext ? mfs::g_fast_filter_ext : mfs::g_fast_filter)[p->N][p->slot - 3];
-        return (wide && p->single_wave_per_simd ? wide : narrow)(a, p->grid, p->lds_doubles, s);
-    }
-    return mfs::g_table[p->N][p->slot].filter(a, p->grid, p->lds_bytes, s);
 }
 
 static int enqueue_chunks(mfs_plan_1d* p, const mfs::Filter1dArgs& base, hipStream_t s) {
     mfs::Filter1dArgs a = base;
-    if (p->T == 0) {  // empty measurement sequence: nell = 0, nothing else to write
-        a.t_begin = 0; a.t_end = 0;
-        hipError_t e = launch_filter(p, a, s);
-        if (e != hipSuccess) return fail(MFS_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-        return MFS_OK;
-    }
-    for (int t0 = 0; t0 < p->T; t0 += p->chunk) {
+    int t0 = 0;
+    do {  // (an empty measurement sequence still takes its one launch: nell = 0, nothing else to write)
         a.t_begin = t0;
         a.t_end = (t0 + p->chunk < p->T) ? t0 + p->chunk : p->T;
-        hipError_t e = launch_filter(p, a, s);
+        hipError_t e = p->launch(a, p->grid, p->launch_lds, s);
         if (e != hipSuccess) return fail(MFS_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    }
+    } while ((t0 += p->chunk) < p->T);
     return MFS_OK;
 }
 
@@ -360,9 +348,8 @@ int mfs_plan_1d_run(mfs_plan_1d* p, const double* d_m0, int m0_batched, const do
                     const double* d_scale0, const double* d_ys, double* d_out_moments, double* d_out_means,
                     double* d_out_scales, double* d_out_nell, int32_t* d_out_first_nan, void* stream) {
     if (!p) return fail(MFS_EINVAL, "plan is NULL");
-    if (!d_m0 || !d_out_nell || (p->T > 0 && !d_ys)) return fail(MFS_EINVAL, "m0 / ys / out_nell must not be NULL");
-    if (p->mode != MFS_MODE_RAW && !d_mean0) return fail(MFS_EINVAL, "mean0 is required in central / scaled mode");
-    if (p->mode == MFS_MODE_SCALED && !d_scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    // (checked before the empty batch returns: this entry point asks for ys whenever T > 0)
+    if (int rc = check_run_pointers(p->mode, d_m0, d_mean0, d_scale0, d_ys, d_out_nell, p->T, 1)) return rc;
     if (p->B == 0) return MFS_OK;
     HIP_TRY(hipSetDevice(p->device));
     const int nchunks = (p->T + p->chunk - 1) / (p->chunk > 0 ? p->chunk : 1);
@@ -396,9 +383,6 @@ int mfs_plan_1d_run(mfs_plan_1d* p, const double* d_m0, int m0_batched, const do
 // ---------------------------------------------------------------------------------------------------------------
 // host-pointer convenience path
 // ---------------------------------------------------------------------------------------------------------------
-// How many T-chunks the host entry splits a run into when the moments are streamed out: the kernel of chunk k + 1 runs
-// while chunk k's slice of out_moments travels to the host (2-D copy: B rows of chunk x 2N doubles).  MFS_HOST_CHUNKS
-// overrides (1 = one launch, copies afterwards).
 // hipMemcpy2DAsync takes a pitch: a row of T x (moments per step) x 8 bytes beyond the runtime's limit (runs of ~1e6 steps and
 // more) would fail the whole call, so such runs go out in one linear copy instead (no copy / compute overlap)
 static bool pitch_ok(size_t pitch_bytes, int device) {
@@ -407,97 +391,66 @@ static bool pitch_ok(size_t pitch_bytes, int device) {
     return pitch_bytes <= (size_t)maxp;
 }
 
-static int host_chunks(size_t moment_bytes, int T) {
-    int n = (int)(moment_bytes / ((size_t)32 << 20));
+// How many T-chunks a host entry splits a run into when the moments ([B][T][width] doubles) are streamed out
+// (mfs::run_streaming_out): one per 32 MB of them, at most 16.  MFS_HOST_CHUNKS overrides (1 = one launch, copies afterwards).
+static int host_chunks(int device, int T, int B, size_t width, bool out_moments) {
+    if (B <= 0 || T <= 0 || !pitch_ok((size_t)T * width * 8, device)) return 1;
+    int n = out_moments ? (int)((size_t)B * T * width * 8 / ((size_t)32 << 20)) : 0;
     if (const char* e = getenv("MFS_HOST_CHUNKS")) n = atoi(e);
     if (n > 16) n = 16;
     if (n > T) n = T;
     return n < 1 ? 1 : n;
 }
 
+// Device staging comes from the library's pool, streams / events from its context cache (mfs::Staging): no hipMalloc,
+// hipFree, hipStreamCreate or hipEventCreate on a steady-state call (SURVEY.md section 8b "Ownership").
 int mfs_filter_1d(const mfs_model_1d* model, int mode, int N, int T, int B, const double* m0, int m0_batched,
                   const double* mean0, const double* scale0, const double* ys, int stable, double* out_moments,
                   double* out_means, double* out_scales, double* out_nell, int32_t* out_first_nan, int device,
                   void* stream) {
-    if (!m0 || !out_nell || (T > 0 && B > 0 && !ys)) return fail(MFS_EINVAL, "m0 / ys / out_nell must not be NULL");
     const int extra = (mode & MFS_MODE_ODD_TAIL) ? 1 : 0, full_mode = mode;
     mode &= 0xff;
-    if (mode != MFS_MODE_RAW && !mean0) return fail(MFS_EINVAL, "mean0 is required in central / scaled mode");
-    if (mode == MFS_MODE_SCALED && !scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    if (int rc = check_run_pointers(mode, m0, mean0, scale0, ys, out_nell, T, B)) return rc;
     const size_t M2 = 2 * (size_t)N + extra, nb = m0_batched ? B : 1;     // doubles per moment row
-    const size_t mom_bytes = out_moments ? (size_t)B * T * M2 * 8 : 0;
-    const int nchunks = (B > 0 && T > 0 && !extra && pitch_ok((size_t)T * M2 * 8, device)) ? host_chunks(mom_bytes, T) : 1;
+    const int nchunks = extra ? 1 : host_chunks(device, T, B, M2, out_moments != nullptr);
     const int chunk = (nchunks > 1) ? (T + nchunks - 1) / nchunks : 0;
     mfs_plan_1d* p = nullptr;
     if (int rc = mfs_plan_1d_create(&p, model, full_mode, N, T, B, stable, chunk, device)) return rc;
     struct PlanGuard { mfs_plan_1d* p; ~PlanGuard() { destroy_plan_1d(p, true); } } guard{p};  // (every exit below is quiesced)
     if (B == 0) return MFS_OK;
 
-    // device staging from the library's pool, streams / events from its context cache: no hipMalloc, hipFree,
-    // hipStreamCreate or hipEventCreate on a steady-state call (SURVEY.md section 8b "Ownership")
-    mfs::Lease lease(device);
-    mfs::CallContext* cx = nullptr;
+    mfs::Staging st(device, stream, true);
     double *d_m0 = nullptr, *d_mean0 = nullptr, *d_scale0 = nullptr, *d_ys = nullptr, *d_mom = nullptr,
            *d_means = nullptr, *d_scales = nullptr, *d_nell = nullptr;
     int32_t* d_fn = nullptr;
-    hipError_t e = lease.context(&cx);
-    auto alloc = [&](auto** d, size_t bytes) { if (e == hipSuccess) e = lease.device_block(d, bytes); };
-    alloc(&d_m0, nb * M2 * 8);
-    alloc(&d_mean0, nb * 8);
-    alloc(&d_scale0, nb * 8);
-    alloc(&d_ys, (size_t)B * T * 8);
-    if (out_moments) alloc(&d_mom, mom_bytes);
-    if (out_means && mode != MFS_MODE_RAW) alloc(&d_means, (size_t)B * T * 8);
-    if (out_scales && mode == MFS_MODE_SCALED) alloc(&d_scales, (size_t)B * T * 8);
-    alloc(&d_nell, (size_t)B * 8);
-    alloc(&d_fn, (size_t)B * 4);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_1d staging: %s", hipGetErrorString(e));
-    hipStream_t s = stream ? (hipStream_t)stream : cx->compute;
-    auto h2d = [&](void* d, const void* h, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
-    };
-    h2d(d_m0, m0, nb * M2 * 8);
-    if (mean0) h2d(d_mean0, mean0, nb * 8);
-    if (scale0) h2d(d_scale0, scale0, nb * 8);
-    h2d(d_ys, ys, (size_t)B * T * 8);
+    st.alloc(&d_m0, nb * M2 * 8);
+    st.alloc(&d_mean0, nb * 8);
+    st.alloc(&d_scale0, nb * 8);
+    st.alloc(&d_ys, (size_t)B * T * 8);
+    if (out_moments) st.alloc(&d_mom, (size_t)B * T * M2 * 8);
+    if (out_means && mode != MFS_MODE_RAW) st.alloc(&d_means, (size_t)B * T * 8);
+    if (out_scales && mode == MFS_MODE_SCALED) st.alloc(&d_scales, (size_t)B * T * 8);
+    st.alloc(&d_nell, (size_t)B * 8);
+    st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_m0, m0, nb * M2 * 8);
+    if (mean0) st.h2d(d_mean0, mean0, nb * 8);
+    if (scale0) st.h2d(d_scale0, scale0, nb * 8);
+    st.h2d(d_ys, ys, (size_t)B * T * 8);
 
-    int rc = MFS_OK;
-    if (e == hipSuccess) {
-        mfs::Filter1dArgs a = plan_args(p, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn);
-        if (nchunks <= 1) {
-            rc = enqueue_chunks(p, a, s);
-            if (rc == MFS_OK && out_moments && T > 0) e = hipMemcpyAsync(out_moments, d_mom, mom_bytes, hipMemcpyDeviceToHost, s);
-        } else {
-            // chunk launches on `s`; after each one an event releases that chunk's slice of the moments to the copy
-            // stream -- same chunking, same carry and therefore the same bits as the plan's graph of chunk launches
-            const size_t pitch = (size_t)T * M2 * 8;
-            for (int k = 0, t0 = 0; t0 < T && rc == MFS_OK && e == hipSuccess; ++k, t0 += chunk) {
-                a.t_begin = t0;
-                a.t_end = (t0 + chunk < T) ? t0 + chunk : T;
-                e = launch_filter(p, a, s);
-                if (e != hipSuccess) { rc = fail(MFS_EHIP, "kernel launch failed: %s", hipGetErrorString(e)); break; }
-                e = hipEventRecord(cx->ev[k], s);
-                if (e == hipSuccess) e = hipStreamWaitEvent(cx->copy, cx->ev[k], 0);
-                if (e == hipSuccess && out_moments)
-                    e = hipMemcpy2DAsync(out_moments + (size_t)t0 * M2, pitch, d_mom + (size_t)t0 * M2, pitch,
-                                         (size_t)(a.t_end - t0) * M2 * 8, (size_t)B, hipMemcpyDeviceToHost, cx->copy);
-            }
-        }
+    // same chunking, same carry and therefore the same bits as the plan's graph of chunk launches
+    mfs::Filter1dArgs a = plan_args(p, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn);
+    const int rc = mfs::run_streaming_out(st, T, B, nchunks, M2, out_moments, d_mom, [&](int t0, int t1) {
+        a.t_begin = t0; a.t_end = t1;
+        const hipError_t e = p->launch(a, p->grid, p->launch_lds, st.s);
+        return (e == hipSuccess) ? MFS_OK : fail(MFS_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    });
+    if (rc == MFS_OK) {
+        st.d2h(out_means, d_means, (size_t)B * T * 8);
+        st.d2h(out_scales, d_scales, (size_t)B * T * 8);
+        st.d2h(out_nell, d_nell, (size_t)B * 8);
+        st.d2h(out_first_nan, d_fn, (size_t)B * 4);
     }
-    auto d2h = [&](void* h, const void* d, size_t bytes) {
-        if (rc == MFS_OK && e == hipSuccess && h && d && bytes) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
-    };
-    d2h(out_means, d_means, (size_t)B * T * 8);
-    d2h(out_scales, d_scales, (size_t)B * T * 8);
-    d2h(out_nell, d_nell, (size_t)B * 8);
-    d2h(out_first_nan, d_fn, (size_t)B * 4);
-    // quiesce both streams whatever happened above: the pool blocks go back when `lease` and `guard` unwind
-    const hipError_t e1 = hipStreamSynchronize(s), e2 = hipStreamSynchronize(cx->copy);
-    if (rc != MFS_OK) return rc;
-    if (e == hipSuccess) e = (e1 != hipSuccess) ? e1 : e2;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_1d: %s", hipGetErrorString(e));
-    return MFS_OK;
+    return st.finish("mfs_filter_1d", rc);
 }
 
 int mfs_filter_1d_grad(const mfs_model_1d* model, const double* dcoef, const double* dlik, int n_par, int mode, int N,
@@ -506,40 +459,34 @@ int mfs_filter_1d_grad(const mfs_model_1d* model, const double* dcoef, const dou
                        void* stream) {
     if (int rc = check_model(model, mode)) return rc;
     if (mode & MFS_MODE_ODD_TAIL) return fail(MFS_EUNSUPPORTED, "the gradient entry point takes 2N moments");
-    if (n_par < 1 || n_par > 4) return fail(MFS_EUNSUPPORTED, "n_par = %d outside [1, 4]", n_par);
-    if (N < 2 || N > 16) return fail(MFS_EUNSUPPORTED, "N = %d outside [2, 16] for the gradient kernel", N);
+    if (n_par < 1 || n_par > mfs::kGradMaxP) return fail(MFS_EUNSUPPORTED, "n_par = %d outside [1, %d]", n_par, mfs::kGradMaxP);
+    if (N < 2 || N > mfs::kGradMaxN)
+        return fail(MFS_EUNSUPPORTED, "N = %d outside [2, %d] for the gradient kernel", N, mfs::kGradMaxN);
     if (T < 0 || B < 0) return fail(MFS_EINVAL, "negative T or B");
-    if (!dcoef || !dlik || !m0 || !out_nell || !out_grad || (T > 0 && B > 0 && !ys)) return fail(MFS_EINVAL, "NULL buffer");
-    if (mode != MFS_MODE_RAW && !mean0) return fail(MFS_EINVAL, "mean0 is required in central / scaled mode");
-    if (mode == MFS_MODE_SCALED && !scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    if (!dcoef || !dlik || !out_grad) return fail(MFS_EINVAL, "NULL buffer");
+    if (int rc = check_run_pointers(mode, m0, mean0, scale0, ys, out_nell, T, B)) return rc;
     if (B == 0) return MFS_OK;
     mfs::Filter1dGradLaunch launch = mfs::g_grad_table[N][n_par];
     if (!launch) return fail(MFS_EUNSUPPORTED, "no gradient kernel compiled for N = %d, n_par = %d", N, n_par);
     HIP_TRY(hipSetDevice(device));
-    mfs::Lease lease(device);
-    mfs::CallContext* cx = nullptr;
-    hipError_t e = lease.context(&cx);
-    if (e != hipSuccess) return fail(MFS_EHIP, "mfs_filter_1d_grad: %s", hipGetErrorString(e));
-    hipStream_t s = stream ? (hipStream_t)stream : cx->compute;
+    mfs::Staging st(device, stream, true);
     const size_t J1 = (size_t)model->degree + 1, ncoef = (size_t)model->n_rows * J1;
     const size_t nbc = model->coef_batched ? B : 1, nbl = model->lik_batched ? B : 1, nb = m0_batched ? B : 1, M2 = 2 * (size_t)N;
     double *d_coef = nullptr, *d_dcoef = nullptr, *d_lik = nullptr, *d_dlik = nullptr, *d_m0 = nullptr, *d_mean0 = nullptr,
            *d_scale0 = nullptr, *d_ys = nullptr, *d_nell = nullptr, *d_grad = nullptr;
     int32_t* d_fn = nullptr;
-    auto alloc = [&](auto** d, size_t bytes) { if (e == hipSuccess) e = lease.device_block(d, bytes); };
-    auto h2d = [&](void* d, const void* h, size_t bytes) {
-        if (e == hipSuccess && bytes && h) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
-    };
-    alloc(&d_coef, nbc * ncoef * 8); alloc(&d_dcoef, nbc * n_par * ncoef * 8);
-    alloc(&d_lik, nbl * model->n_lik * 8); alloc(&d_dlik, nbl * n_par * model->n_lik * 8);
-    alloc(&d_m0, nb * M2 * 8); alloc(&d_mean0, nb * 8); alloc(&d_scale0, nb * 8);
-    alloc(&d_ys, (size_t)B * T * 8); alloc(&d_nell, (size_t)B * 8); alloc(&d_grad, (size_t)B * n_par * 8);
-    alloc(&d_fn, (size_t)B * 4);
-    h2d(d_coef, model->coef, nbc * ncoef * 8); h2d(d_dcoef, dcoef, nbc * n_par * ncoef * 8);
-    h2d(d_lik, model->lik, nbl * model->n_lik * 8); h2d(d_dlik, dlik, nbl * n_par * model->n_lik * 8);
-    h2d(d_m0, m0, nb * M2 * 8); h2d(d_mean0, mean0, nb * 8); h2d(d_scale0, scale0, nb * 8);
-    h2d(d_ys, ys, (size_t)B * T * 8);
-    if (e == hipSuccess) {
+    st.alloc(&d_coef, nbc * ncoef * 8); st.alloc(&d_dcoef, nbc * n_par * ncoef * 8);
+    st.alloc(&d_lik, nbl * model->n_lik * 8); st.alloc(&d_dlik, nbl * n_par * model->n_lik * 8);
+    st.alloc(&d_m0, nb * M2 * 8); st.alloc(&d_mean0, nb * 8); st.alloc(&d_scale0, nb * 8);
+    st.alloc(&d_ys, (size_t)B * T * 8); st.alloc(&d_nell, (size_t)B * 8); st.alloc(&d_grad, (size_t)B * n_par * 8);
+    st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_coef, model->coef, nbc * ncoef * 8); st.h2d(d_dcoef, dcoef, nbc * n_par * ncoef * 8);
+    st.h2d(d_lik, model->lik, nbl * model->n_lik * 8); st.h2d(d_dlik, dlik, nbl * n_par * model->n_lik * 8);
+    st.h2d(d_m0, m0, nb * M2 * 8);
+    if (mean0) st.h2d(d_mean0, mean0, nb * 8);
+    if (scale0) st.h2d(d_scale0, scale0, nb * 8);
+    st.h2d(d_ys, ys, (size_t)B * T * 8);
+    if (st.err == hipSuccess) {
         mfs::Filter1dGradArgs ga;
         memset(&ga, 0, sizeof(ga));
         mfs::Filter1dArgs& a = ga.f;
@@ -550,16 +497,10 @@ int mfs_filter_1d_grad(const mfs_model_1d* model, const double* dcoef, const dou
         a.m0 = d_m0; a.m0_batched = m0_batched; a.mean0 = d_mean0; a.scale0 = d_scale0; a.ys = d_ys;
         a.out_nell = d_nell; a.out_first_nan = d_fn;
         ga.n_par = n_par; ga.dcoef = d_dcoef; ga.dlik = d_dlik; ga.out_grad = d_grad;
-        e = launch(ga, B, s);      // (the launcher knows its lanes per filter)
+        st.err = launch(ga, B, st.s);      // (the launcher knows its lanes per filter)
     }
-    auto d2h = [&](void* h, const void* d, size_t bytes) {
-        if (e == hipSuccess && h && bytes) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
-    };
-    d2h(out_nell, d_nell, (size_t)B * 8); d2h(out_grad, d_grad, (size_t)B * n_par * 8); d2h(out_first_nan, d_fn, (size_t)B * 4);
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_1d_grad: %s", hipGetErrorString(e));
-    return MFS_OK;
+    st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_grad, d_grad, (size_t)B * n_par * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
+    return st.finish("mfs_filter_1d_grad", MFS_OK);
 }
 
 int mfs_quadrature_1d(int N, int B, const double* ms, const double* mean, const double* scale, int stable,
@@ -572,34 +513,29 @@ int mfs_quadrature_1d(int N, int B, const double* ms, const double* mean, const 
     const mfs::KernelEntry& ke = mfs::g_table[N][slot];
     if (!ke.quad) return fail(MFS_EUNSUPPORTED, "no kernel compiled for N = %d", N);
     HIP_TRY(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
     const int G = ke.lanes_per_filter;
     const int fpb = ke.waves_per_block * (64 / G);
-    const bool ext = slot >= 3 && stable != 0;     // the completed rule of stable = 1 needs the extended tile
-    if (ext && !mfs::g_quad_ext[N][slot - 3]) return fail(MFS_EUNSUPPORTED, "no extended quadrature kernel for N = %d", N);
-    const int quad_lds = fpb * (ext ? mfs::g_quad_ext_lds[N][slot - 3] : slot >= 3 ? 2 * N : ke.lds_doubles_per_filter) * 8;
+    // the completed rule of stable = 1 needs the extended tile
+    const mfs::FastEntry* ext = (slot >= 3 && stable != 0) ? &mfs::g_fast[N][slot - 3] : nullptr;
+    if (ext && !ext->quad_ext) return fail(MFS_EUNSUPPORTED, "no extended quadrature kernel for N = %d", N);
+    const int quad_lds = fpb * (ext ? ext->quad_ext_lds : slot >= 3 ? 2 * N : ke.lds_doubles_per_filter) * 8;
     double *d_ms = nullptr, *d_mean = nullptr, *d_scale = nullptr, *d_w = nullptr, *d_x = nullptr;
-    mfs::Lease lease(device);
-    hipError_t e = hipSuccess;
-    auto alloc = [&](double** d, size_t bytes) { if (e == hipSuccess) e = lease.device_block(d, bytes); };
-    alloc(&d_ms, (size_t)B * 2 * N * 8);
-    alloc(&d_w, (size_t)B * N * 8);
-    alloc(&d_x, (size_t)B * N * 8);
-    if (mean) alloc(&d_mean, (size_t)B * 8);
-    if (scale) alloc(&d_scale, (size_t)B * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ms, ms, (size_t)B * 2 * N * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && mean) e = hipMemcpyAsync(d_mean, mean, (size_t)B * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && scale) e = hipMemcpyAsync(d_scale, scale, (size_t)B * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
+    mfs::Staging st(device, stream, false);   // on the caller's stream, null included
+    st.alloc(&d_ms, (size_t)B * 2 * N * 8);
+    st.alloc(&d_w, (size_t)B * N * 8);
+    st.alloc(&d_x, (size_t)B * N * 8);
+    if (mean) st.alloc(&d_mean, (size_t)B * 8);
+    if (scale) st.alloc(&d_scale, (size_t)B * 8);
+    st.h2d(d_ms, ms, (size_t)B * 2 * N * 8);
+    if (mean) st.h2d(d_mean, mean, (size_t)B * 8);
+    if (scale) st.h2d(d_scale, scale, (size_t)B * 8);
+    if (st.err == hipSuccess) {
         mfs::Quad1dArgs a{B, stable, d_ms, d_mean, d_scale, d_w, d_x};
-        e = (ext ? mfs::g_quad_ext[N][slot - 3] : ke.quad)(a, (B + fpb - 1) / fpb, quad_lds, s);
+        st.err = (ext ? ext->quad_ext : ke.quad)(a, (B + fpb - 1) / fpb, quad_lds, st.s);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_weights, d_w, (size_t)B * N * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_nodes, d_x, (size_t)B * N * 8, hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);   // always: the blocks go back to the pool on return
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(MFS_EHIP, "mfs_quadrature_1d: %s", hipGetErrorString(e));
-    return MFS_OK;
+    st.d2h(out_weights, d_w, (size_t)B * N * 8);
+    st.d2h(out_nodes, d_x, (size_t)B * N * 8);
+    return st.finish("mfs_quadrature_1d", MFS_OK);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -729,20 +665,55 @@ int mfs_memcpy_d2d(void* dst, const void* src, uint64_t bytes, void* stream) {
 // ---------------------------------------------------------------------------------------------------------------
 // N-D filter (d = 2)
 // ---------------------------------------------------------------------------------------------------------------
-struct mfs_plan_nd {
-    int mode, N, T, B, stable, device, trans_kind, ny;
-    bool hi_terms = false;    // operator table with |kappa| > 4 terms (TME order 3): the 29-row layout and its kernel
-    mfs::FilterNdArgs args;   // model part filled at create (device pointers), data pointers per run
+// what the d = 2 and d = 3 plans share: the run's shape and the device copies of the model tables
+struct NdPlanBase {
+    int mode, N, T, B, device;
     double* d_coef = nullptr;
     double* d_lik = nullptr;
     int32_t* d_inds = nullptr;
 };
 
-static void destroy_plan_nd(mfs_plan_nd* p, bool quiesced) {
+struct mfs_plan_nd : NdPlanBase {
+    mfs::FilterNdLaunch launch = nullptr;   // the kernel family of the model, resolved at creation
+    mfs::FilterNdArgs args;   // model part filled at create (device pointers), data pointers per run
+};
+
+// pool blocks for the coefficient, likelihood-parameter and Gram / Hankel index tables, and their upload
+static hipError_t upload_nd_tables(NdPlanBase* p, const double* coef, size_t ncoef, const double* lik, size_t nlik,
+                                   const int32_t* inds, size_t ninds) {
+    mfs::BlockPool<false>& pool = mfs::device_state(p->device).device;
+    hipError_t e = pool.acquire((void**)&p->d_coef, ncoef * 8);
+    if (e == hipSuccess) e = pool.acquire((void**)&p->d_lik, nlik * 8);
+    if (e == hipSuccess) e = pool.acquire((void**)&p->d_inds, ninds * 4);
+    if (e == hipSuccess && ncoef) e = hipMemcpy(p->d_coef, coef, ncoef * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nlik) e = hipMemcpy(p->d_lik, lik, nlik * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_inds, inds, ninds * 4, hipMemcpyHostToDevice);
+    return e;
+}
+
+// the part of the kernel arguments that both model structs describe alike (Args: FilterNdArgs / FilterNd3Args)
+template <typename Args, typename Model>
+static void fill_nd_args(Args& a, const NdPlanBase* p, const Model* model) {
+    memset(&a, 0, sizeof(a));
+    a.mode = p->mode; a.T = p->T; a.B = p->B;
+    a.D = model->extent; a.n_factors = model->n_factors; a.ny = model->ny;
+    for (int f = 0; f < model->n_factors; ++f) {
+        a.fac_kind[f] = model->fac_kind[f]; a.fac_comp[f] = model->fac_component[f]; a.fac_ycol[f] = model->fac_ycol[f];
+    }
+    a.coef_batched = model->coef_batched; a.lik_batched = model->lik_batched;
+    a.coef = p->d_coef; a.lik = p->d_lik; a.inds = p->d_inds;
+}
+
+static mfs::BlockPool<false>& release_nd_tables(NdPlanBase* p, bool quiesced) {
     hipSetDevice(p->device);
     if (!quiesced) hipDeviceSynchronize();   // pool blocks must be idle when they go back (what hipFree did implicitly)
     mfs::BlockPool<false>& pool = mfs::device_state(p->device).device;
     pool.release(p->d_coef); pool.release(p->d_lik); pool.release(p->d_inds);
+    return pool;
+}
+
+static void destroy_plan_nd(mfs_plan_nd* p, bool quiesced) {
+    release_nd_tables(p, quiesced);
     delete p;
 }
 
@@ -754,7 +725,7 @@ extern "C" int mfs_plan_nd_create(mfs_plan_nd** plan, const mfs_model_nd* model,
     if (model->d != 2) return fail(MFS_EUNSUPPORTED, "the device N-D path supports d = 2 (got %d)", model->d);
     if (mode != MFS_MODE_RAW && mode != MFS_MODE_CENTRAL && mode != MFS_MODE_SCALED)
         return fail(MFS_EINVAL, "unknown moment mode %d", mode);
-    if (N < 2 || N > 7) return fail(MFS_EUNSUPPORTED, "N = %d outside [2, 7] for d = 2", N);
+    if (N < 2 || N > mfs::kNdMaxN) return fail(MFS_EUNSUPPORTED, "N = %d outside [2, %d] for d = 2", N, mfs::kNdMaxN);
     const mfs::NdEntry& ke = mfs::g_nd_table[N];
     if (!ke.launch) return fail(MFS_EUNSUPPORTED, "no N-D kernel compiled for N = %d", N);
     if (model->trans_kind != MFS_ND_TRANS_OPERATOR && model->trans_kind != MFS_ND_TRANS_GAUSSIAN)
@@ -805,31 +776,23 @@ extern "C" int mfs_plan_nd_create(mfs_plan_nd** plan, const mfs_model_nd* model,
     HIP_TRY(hipSetDevice(device));
     mfs_plan_nd* p = new (std::nothrow) mfs_plan_nd();
     if (!p) return fail(MFS_ENOMEM, "out of host memory");
-    p->mode = mode; p->N = N; p->T = T; p->B = B; p->stable = stable; p->device = device;
-    p->trans_kind = model->trans_kind; p->ny = model->ny; p->hi_terms = (model->trans_kind == MFS_ND_TRANS_OPERATOR && model->n_terms > MFS_ND_TERMS);
+    p->mode = mode; p->N = N; p->T = T; p->B = B; p->device = device;
+    // the kernel family: Normal closure; operator table with |kappa| > 4 terms (TME order 3: the 29-row layout); operator
+    // table with the node tables of a joint likelihood; operator table
+    const bool joint = model->n_factors == 1 && model->fac_component[0] == 2;
+    p->launch = (model->trans_kind == MFS_ND_TRANS_GAUSSIAN) ? ke.launch_gauss
+                : (model->n_terms > MFS_ND_TERMS) ? ke.launch_hi : joint ? ke.launch_joint : ke.launch;
     const size_t S = ke.S, DD = (size_t)model->extent * model->extent;
     const size_t ncoef = (size_t)(model->coef_batched ? B : 1) * n_rows * DD;
     const size_t nlik = (size_t)(model->lik_batched ? B : 1) * model->n_factors * MFS_MAX_LIK;
-    mfs::BlockPool<false>& pool = mfs::device_state(device).device;
-    hipError_t e = pool.acquire((void**)&p->d_coef, ncoef * 8);
-    if (e == hipSuccess) e = pool.acquire((void**)&p->d_lik, nlik * 8);
-    if (e == hipSuccess) e = pool.acquire((void**)&p->d_inds, 3 * S * S * 4);
-    if (e == hipSuccess && ncoef) e = hipMemcpy(p->d_coef, model->coef, ncoef * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nlik) e = hipMemcpy(p->d_lik, model->lik, nlik * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_inds, inds, 3 * S * S * 4, hipMemcpyHostToDevice);
+    const hipError_t e = upload_nd_tables(p, model->coef, ncoef, model->lik, nlik, inds, 3 * S * S);
     if (e != hipSuccess) {
         destroy_plan_nd(p, true);
         return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_plan_nd_create: %s", hipGetErrorString(e));
     }
     mfs::FilterNdArgs& a = p->args;
-    memset(&a, 0, sizeof(a));
-    a.mode = mode; a.T = T; a.B = B; a.stable = stable;
-    a.n_terms_used = model->n_terms; a.D = model->extent;
-    a.n_factors = model->n_factors; a.ny = model->ny;
-    for (int f = 0; f < model->n_factors; ++f) {
-        a.fac_kind[f] = model->fac_kind[f]; a.fac_comp[f] = model->fac_component[f]; a.fac_ycol[f] = model->fac_ycol[f];
-    }
-    a.coef_batched = model->coef_batched; a.lik_batched = model->lik_batched;
+    fill_nd_args(a, p, model);
+    a.stable = stable; a.n_terms_used = model->n_terms;
     // stable = 1: the completion on the register front end (a.stable = 1); MFS_ND_STABLE=dense keeps the LDS-tile form (2)
     if (stable) { const char* e = getenv("MFS_ND_STABLE"); a.stable = (e && strcmp(e, "dense") == 0) ? 2 : 1; }
     if (const char* e = getenv("MFS_ND_UPDATE")) {   // A/B switches, like MFS_SOLVER
@@ -848,7 +811,6 @@ extern "C" int mfs_plan_nd_create(mfs_plan_nd** plan, const mfs_model_nd* model,
         }
         a.ext[k] = (ea == 0) ? 0 : (ea | (eb << 8));
     }
-    a.coef = p->d_coef; a.lik = p->d_lik; a.inds = p->d_inds;
     *plan = p;
     return MFS_OK;
 }
@@ -865,10 +827,7 @@ static int plan_nd_launch(mfs_plan_nd* p, const double* d_m0, int m0_batched, co
     a.out_scale = (p->mode == MFS_MODE_SCALED) ? d_out_scales : nullptr;
     a.out_nell = d_out_nell; a.out_first_nan = d_out_first_nan;
     a.t_begin = t0; a.t_end = t1; a.carry = carry;
-    const mfs::NdEntry& ke = mfs::g_nd_table[p->N];
-    const bool joint = a.n_factors == 1 && a.fac_comp[0] == 2;
-    hipError_t e = (p->trans_kind == MFS_ND_TRANS_GAUSSIAN ? ke.launch_gauss : p->hi_terms ? ke.launch_hi
-                    : joint ? ke.launch_joint : ke.launch)(a, p->B, stream);
+    const hipError_t e = p->launch(a, p->B, stream);
     if (e != hipSuccess) return fail(MFS_EHIP, "N-D kernel launch: %s", hipGetErrorString(e));
     return MFS_OK;
 }
@@ -878,9 +837,7 @@ extern "C" int mfs_plan_nd_run(mfs_plan_nd* p, const double* d_m0, int m0_batche
                                double* d_out_scales, double* d_out_nell, int32_t* d_out_first_nan, void* stream) {
     if (!p) return fail(MFS_EINVAL, "plan is NULL");
     if (p->B == 0) return MFS_OK;
-    if (!d_m0 || !d_out_nell || (p->T > 0 && !d_ys)) return fail(MFS_EINVAL, "NULL buffer");
-    if (p->mode != MFS_MODE_RAW && !d_mean0) return fail(MFS_EINVAL, "mean0 is required in central and scaled modes");
-    if (p->mode == MFS_MODE_SCALED && !d_scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    if (int rc = check_run_pointers(p->mode, d_m0, d_mean0, d_scale0, d_ys, d_out_nell, p->T, p->B)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     return plan_nd_launch(p, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_out_moments, d_out_means, d_out_scales, d_out_nell,
                           d_out_first_nan, 0, p->T, nullptr, (hipStream_t)stream);
@@ -908,98 +865,59 @@ extern "C" int mfs_filter_nd(const mfs_model_nd* model, int mode, int N, int T, 
     int rc = mfs_plan_nd_create(&plan, model, mode, N, T, B, z, multi_indices, inds, stable, device);
     if (rc != MFS_OK) return rc;
     struct Guard { mfs_plan_nd* p; ~Guard() { destroy_plan_nd(p, true); } } guard{plan};   // (every exit below is quiesced)
-    if (!m0 || !out_nell || (T > 0 && B > 0 && !ys)) return fail(MFS_EINVAL, "NULL buffer");
-    if (mode != MFS_MODE_RAW && !mean0) return fail(MFS_EINVAL, "mean0 is required in central and scaled modes");
-    if (mode == MFS_MODE_SCALED && !scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    if ((rc = check_run_pointers(mode, m0, mean0, scale0, ys, out_nell, T, B))) return rc;
     if (B == 0) return MFS_OK;
     const size_t Z = (size_t)z, nb = m0_batched ? B : 1, ny = (size_t)model->ny;
     double *d_m0 = nullptr, *d_mean0 = nullptr, *d_ys = nullptr, *d_mom = nullptr, *d_means = nullptr, *d_nell = nullptr,
            *d_scale0 = nullptr, *d_scales = nullptr;
     int32_t* d_fn = nullptr;
-    mfs::Lease lease(device);
-    mfs::CallContext* cx = nullptr;
-    hipError_t e = lease.context(&cx);
-    if (e != hipSuccess) return fail(MFS_EHIP, "mfs_filter_nd: %s", hipGetErrorString(e));
-    hipStream_t s = stream ? (hipStream_t)stream : cx->compute;
-    auto alloc = [&](auto** d, size_t bytes) { if (e == hipSuccess) e = lease.device_block(d, bytes); };
-    auto h2d = [&](void* d, const void* h, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
-    };
-    auto d2h = [&](void* h, const void* d, size_t bytes) {
-        if (e == hipSuccess && h && d && bytes) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
-    };
-    alloc(&d_m0, nb * Z * 8);
-    alloc(&d_mean0, nb * 2 * 8);
-    alloc(&d_scale0, nb * 2 * 8);
-    alloc(&d_ys, (size_t)B * T * ny * 8);
-    if (out_moments) alloc(&d_mom, (size_t)B * T * Z * 8);
-    if (out_means && mode != MFS_MODE_RAW) alloc(&d_means, (size_t)B * T * 2 * 8);
-    if (out_scales && mode == MFS_MODE_SCALED) alloc(&d_scales, (size_t)B * T * 2 * 8);
-    alloc(&d_nell, (size_t)B * 8);
-    alloc(&d_fn, (size_t)B * 4);
-    h2d(d_m0, m0, nb * Z * 8);
-    if (mean0) h2d(d_mean0, mean0, nb * 2 * 8);
-    if (scale0 && mode == MFS_MODE_SCALED) h2d(d_scale0, scale0, nb * 2 * 8);
-    h2d(d_ys, ys, (size_t)B * T * ny * 8);
-    // with the moments streamed out, T is cut into chunks: chunk k's slice travels to the host (2-D copy: B rows of
-    // chunk x z doubles) on the copy stream while the kernel of chunk k + 1 runs; the per-replicate state crosses the
-    // launches through a carry block, so the bits are those of the single launch
-    const size_t mom_bytes = out_moments ? (size_t)B * T * Z * 8 : 0;
-    const int nchunks = (T > 0 && pitch_ok((size_t)T * Z * 8, device)) ? host_chunks(mom_bytes, T) : 1;
-    const int chunk = (nchunks > 1) ? (T + nchunks - 1) / nchunks : T;
+    mfs::Staging st(device, stream, true);
+    st.alloc(&d_m0, nb * Z * 8);
+    st.alloc(&d_mean0, nb * 2 * 8);
+    st.alloc(&d_scale0, nb * 2 * 8);
+    st.alloc(&d_ys, (size_t)B * T * ny * 8);
+    if (out_moments) st.alloc(&d_mom, (size_t)B * T * Z * 8);
+    if (out_means && mode != MFS_MODE_RAW) st.alloc(&d_means, (size_t)B * T * 2 * 8);
+    if (out_scales && mode == MFS_MODE_SCALED) st.alloc(&d_scales, (size_t)B * T * 2 * 8);
+    st.alloc(&d_nell, (size_t)B * 8);
+    st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_m0, m0, nb * Z * 8);
+    if (mean0) st.h2d(d_mean0, mean0, nb * 2 * 8);
+    if (scale0 && mode == MFS_MODE_SCALED) st.h2d(d_scale0, scale0, nb * 2 * 8);
+    st.h2d(d_ys, ys, (size_t)B * T * ny * 8);
+    // with the moments streamed out in chunks, the per-replicate state crosses the launches through a carry block, so the
+    // bits are those of the single launch
+    const int nchunks = host_chunks(device, T, B, Z, out_moments != nullptr);
     double* d_carry = nullptr;
-    if (nchunks > 1) alloc(&d_carry, (size_t)B * mfs::g_nd_table[N].carry_doubles * 8);
-    if (e == hipSuccess) {
-        if (nchunks <= 1) {
-            rc = mfs_plan_nd_run(plan, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn, s);
-            if (rc == MFS_OK) d2h(out_moments, d_mom, mom_bytes);
-        } else {
-            const size_t pitch = (size_t)T * Z * 8;
-            for (int k = 0, t0 = 0; t0 < T && rc == MFS_OK && e == hipSuccess; ++k, t0 += chunk) {
-                const int t1 = (t0 + chunk < T) ? t0 + chunk : T;
-                rc = plan_nd_launch(plan, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn,
-                                    t0, t1, d_carry, s);
-                if (rc != MFS_OK) break;
-                e = hipEventRecord(cx->ev[k], s);
-                if (e == hipSuccess) e = hipStreamWaitEvent(cx->copy, cx->ev[k], 0);
-                if (e == hipSuccess && out_moments)
-                    e = hipMemcpy2DAsync(out_moments + (size_t)t0 * Z, pitch, d_mom + (size_t)t0 * Z, pitch,
-                                         (size_t)(t1 - t0) * Z * 8, (size_t)B, hipMemcpyDeviceToHost, cx->copy);
-            }
-        }
-    }
+    if (nchunks > 1) st.alloc(&d_carry, (size_t)B * mfs::g_nd_table[N].carry_doubles * 8);
+    rc = mfs::run_streaming_out(st, T, B, nchunks, Z, out_moments, d_mom, [&](int t0, int t1) {
+        return plan_nd_launch(plan, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn, t0, t1,
+                              d_carry, st.s);
+    });
     if (rc == MFS_OK) {
-        d2h(out_means, d_means, (size_t)B * T * 2 * 8);
-        d2h(out_scales, d_scales, (size_t)B * T * 2 * 8);
-        d2h(out_nell, d_nell, (size_t)B * 8);
-        d2h(out_first_nan, d_fn, (size_t)B * 4);
+        st.d2h(out_means, d_means, (size_t)B * T * 2 * 8);
+        st.d2h(out_scales, d_scales, (size_t)B * T * 2 * 8);
+        st.d2h(out_nell, d_nell, (size_t)B * 8);
+        st.d2h(out_first_nan, d_fn, (size_t)B * 4);
     }
-    const hipError_t es = hipStreamSynchronize(s), ec = hipStreamSynchronize(cx->copy);   // always: the pool blocks go back on return
-    if (e == hipSuccess) e = (es != hipSuccess) ? es : ec;
-    if (rc != MFS_OK) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_nd: %s", hipGetErrorString(e));
-    return MFS_OK;
+    return st.finish("mfs_filter_nd", rc);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // N-D filter, d = 3
 // ---------------------------------------------------------------------------------------------------------------
-struct mfs_plan_nd3 {
-    int mode, N, T, B, stable, device, trans_kind, ny;
+struct mfs_plan_nd3 : NdPlanBase {
+    // the kernel of the model, resolved at creation: `launch_joint` (with `joint`) if it has joint factors, else `launch`
+    mfs::FilterNd3Launch launch = nullptr;
+    mfs::FilterNd3JointLaunch launch_joint = nullptr;
     mfs::FilterNd3Args args;  // model part filled at create (device pointers), data pointers per run
-    mfs::FilterNd3Joint joint;  // n = 0: no joint factors, the plain kernels
-    double* d_coef = nullptr;
-    double* d_lik = nullptr;
-    int32_t* d_inds = nullptr;
+    mfs::FilterNd3Joint joint;
     double* d_jcoef = nullptr;
     double* d_jpar = nullptr;
 };
 
 static void destroy_plan_nd3(mfs_plan_nd3* p, bool quiesced) {
-    hipSetDevice(p->device);
-    if (!quiesced) hipDeviceSynchronize();
-    mfs::BlockPool<false>& pool = mfs::device_state(p->device).device;
-    pool.release(p->d_coef); pool.release(p->d_lik); pool.release(p->d_inds);
+    mfs::BlockPool<false>& pool = release_nd_tables(p, quiesced);
     pool.release(p->d_jcoef); pool.release(p->d_jpar);
     delete p;
 }
@@ -1087,19 +1005,15 @@ static int plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* model, cons
     HIP_TRY(hipSetDevice(device));
     mfs_plan_nd3* p = new (std::nothrow) mfs_plan_nd3();
     if (!p) return fail(MFS_ENOMEM, "out of host memory");
-    p->mode = mode; p->N = N; p->T = T; p->B = B; p->stable = stable; p->device = device;
-    p->trans_kind = model->trans_kind; p->ny = model->ny;
+    p->mode = mode; p->N = N; p->T = T; p->B = B; p->device = device;
+    const bool gauss = model->trans_kind == MFS_ND_TRANS_GAUSSIAN;
+    if (joint) p->launch_joint = gauss ? ke.joint_gauss : ke.joint;
+    else p->launch = gauss ? ke.launch_gauss : ke.launch;
     const size_t D = (size_t)model->extent, DDD = D * D * D;
     const size_t ncoef = (size_t)(model->coef_batched ? B : 1) * MFS_ND3_ROWS * DDD;
     const size_t nlik = (size_t)(model->lik_batched ? B : 1) * model->n_factors * MFS_MAX_LIK;
-    const size_t ninds = (size_t)4 * S * S;
+    hipError_t e = upload_nd_tables(p, model->coef, ncoef, model->lik, nlik, inds, (size_t)4 * S * S);
     mfs::BlockPool<false>& pool = mfs::device_state(device).device;
-    hipError_t e = pool.acquire((void**)&p->d_coef, ncoef * 8);
-    if (e == hipSuccess) e = pool.acquire((void**)&p->d_lik, nlik * 8);
-    if (e == hipSuccess) e = pool.acquire((void**)&p->d_inds, ninds * 4);
-    if (e == hipSuccess && ncoef) e = hipMemcpy(p->d_coef, model->coef, ncoef * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nlik) e = hipMemcpy(p->d_lik, model->lik, nlik * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_inds, inds, ninds * 4, hipMemcpyHostToDevice);
     const size_t E = joint ? (size_t)joint->extent : 0, jblk = 2 * E * E * E, jtab = joint ? (size_t)joint->n_joint * jblk : 0;
     const size_t njb = (joint && joint->batched) ? (size_t)B : 1;
     if (joint) {
@@ -1114,20 +1028,13 @@ static int plan_nd3_create(mfs_plan_nd3** plan, const mfs_model_nd3* model, cons
         return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_plan_nd3_create: %s", hipGetErrorString(e));
     }
     mfs::FilterNd3Args& a = p->args;
-    memset(&a, 0, sizeof(a));
-    a.mode = mode; a.T = T; a.B = B; a.stable = stable ? 1 : 0;
-    a.trans_kind = model->trans_kind; a.D = model->extent;
-    a.n_factors = model->n_factors; a.ny = model->ny;
-    for (int f = 0; f < model->n_factors; ++f) {
-        a.fac_kind[f] = model->fac_kind[f]; a.fac_comp[f] = model->fac_component[f]; a.fac_ycol[f] = model->fac_ycol[f];
-    }
-    a.coef_batched = model->coef_batched; a.lik_batched = model->lik_batched;
+    fill_nd_args(a, p, model);
+    a.stable = stable ? 1 : 0; a.trans_kind = model->trans_kind;
     // true extents of each coefficient block (trailing zero planes cut); the union over replicates when batched
     const size_t ntab = model->coef_batched ? (size_t)B : 1;
-    const int used_rows = (model->trans_kind == MFS_ND_TRANS_GAUSSIAN) ? MFS_ND3_GAUSS_TERMS : MFS_ND3_ROWS;
+    const int used_rows = gauss ? MFS_ND3_GAUSS_TERMS : MFS_ND3_ROWS;
     for (int k = 0; k < MFS_ND3_ROWS; ++k)
         a.ext[k] = (k < used_rows) ? nd3_block_extents(model->coef + (size_t)k * DDD, D, ntab, MFS_ND3_ROWS * DDD) : 0;
-    a.coef = p->d_coef; a.lik = p->d_lik; a.inds = p->d_inds;
     mfs::FilterNd3Joint& jt = p->joint;
     memset(&jt, 0, sizeof(jt));
     if (joint) {
@@ -1161,9 +1068,7 @@ extern "C" int mfs_plan_nd3_run(mfs_plan_nd3* p, const double* d_m0, int m0_batc
                                 double* d_out_scales, double* d_out_nell, int32_t* d_out_first_nan, void* stream) {
     if (!p) return fail(MFS_EINVAL, "plan is NULL");
     if (p->B == 0) return MFS_OK;
-    if (!d_m0 || !d_out_nell || (p->T > 0 && !d_ys)) return fail(MFS_EINVAL, "NULL buffer");
-    if (p->mode != MFS_MODE_RAW && !d_mean0) return fail(MFS_EINVAL, "mean0 is required in central and scaled modes");
-    if (p->mode == MFS_MODE_SCALED && !d_scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    if (int rc = check_run_pointers(p->mode, d_m0, d_mean0, d_scale0, d_ys, d_out_nell, p->T, p->B)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     mfs::FilterNd3Args a = p->args;
     a.m0 = d_m0; a.m0_batched = m0_batched; a.mean0 = d_mean0; a.scale0 = d_scale0; a.ys = d_ys;
@@ -1171,10 +1076,8 @@ extern "C" int mfs_plan_nd3_run(mfs_plan_nd3* p, const double* d_m0, int m0_batc
     a.out_mean = (p->mode != MFS_MODE_RAW) ? d_out_means : nullptr;
     a.out_scale = (p->mode == MFS_MODE_SCALED) ? d_out_scales : nullptr;
     a.out_nell = d_out_nell; a.out_first_nan = d_out_first_nan;
-    const mfs::Nd3Entry& ke = mfs::g_nd3_table[p->N];
-    const bool gauss = p->trans_kind == MFS_ND_TRANS_GAUSSIAN;
-    hipError_t e = p->joint.n ? (gauss ? ke.joint_gauss : ke.joint)(a, p->joint, p->B, (hipStream_t)stream)
-                              : (gauss ? ke.launch_gauss : ke.launch)(a, p->B, (hipStream_t)stream);
+    const hipError_t e = p->launch_joint ? p->launch_joint(a, p->joint, p->B, (hipStream_t)stream)
+                                         : p->launch(a, p->B, (hipStream_t)stream);
     if (e != hipSuccess) return fail(MFS_EHIP, "d = 3 kernel launch: %s", hipGetErrorString(e));
     return MFS_OK;
 }
@@ -1201,54 +1104,37 @@ static int filter_nd3(const mfs_model_nd3* model, const mfs_joint_nd3* joint, in
     int rc = plan_nd3_create(&plan, model, joint, mode, N, T, B, z, multi_indices, inds, stable, device);
     if (rc != MFS_OK) return rc;
     struct Guard { mfs_plan_nd3* p; ~Guard() { destroy_plan_nd3(p, true); } } guard{plan};   // (every exit below is quiesced)
-    if (!m0 || !out_nell || (T > 0 && B > 0 && !ys)) return fail(MFS_EINVAL, "NULL buffer");
-    if (mode != MFS_MODE_RAW && !mean0) return fail(MFS_EINVAL, "mean0 is required in central and scaled modes");
-    if (mode == MFS_MODE_SCALED && !scale0) return fail(MFS_EINVAL, "scale0 is required in scaled mode");
+    if ((rc = check_run_pointers(mode, m0, mean0, scale0, ys, out_nell, T, B))) return rc;
     if (B == 0) return MFS_OK;
     const size_t Z = (size_t)z, nb = m0_batched ? B : 1, ny = (size_t)model->ny;
     double *d_m0 = nullptr, *d_mean0 = nullptr, *d_scale0 = nullptr, *d_ys = nullptr, *d_mom = nullptr, *d_means = nullptr,
            *d_scales = nullptr, *d_nell = nullptr;
     int32_t* d_fn = nullptr;
-    mfs::Lease lease(device);
-    mfs::CallContext* cx = nullptr;
-    hipError_t e = lease.context(&cx);
-    if (e != hipSuccess) return fail(MFS_EHIP, "mfs_filter_nd3: %s", hipGetErrorString(e));
-    hipStream_t s = stream ? (hipStream_t)stream : cx->compute;
-    auto alloc = [&](auto** d, size_t bytes) { if (e == hipSuccess) e = lease.device_block(d, bytes); };
-    auto h2d = [&](void* d, const void* h, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
-    };
-    auto d2h = [&](void* h, const void* d, size_t bytes) {
-        if (e == hipSuccess && h && d && bytes) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
-    };
-    alloc(&d_m0, nb * Z * 8);
-    alloc(&d_mean0, nb * 3 * 8);
-    alloc(&d_scale0, nb * 3 * 8);
-    alloc(&d_ys, (size_t)B * T * ny * 8 + 8);
-    if (out_moments) alloc(&d_mom, (size_t)B * T * Z * 8 + 8);
-    if (out_means && mode != MFS_MODE_RAW) alloc(&d_means, (size_t)B * T * 3 * 8 + 8);
-    if (out_scales && mode == MFS_MODE_SCALED) alloc(&d_scales, (size_t)B * T * 3 * 8 + 8);
-    alloc(&d_nell, (size_t)B * 8);
-    alloc(&d_fn, (size_t)B * 4);
-    h2d(d_m0, m0, nb * Z * 8);
-    if (mean0 && mode != MFS_MODE_RAW) h2d(d_mean0, mean0, nb * 3 * 8);
-    if (scale0 && mode == MFS_MODE_SCALED) h2d(d_scale0, scale0, nb * 3 * 8);
-    h2d(d_ys, ys, (size_t)B * T * ny * 8);
-    if (e == hipSuccess) {
-        rc = mfs_plan_nd3_run(plan, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn, s);
+    mfs::Staging st(device, stream, true);
+    st.alloc(&d_m0, nb * Z * 8);
+    st.alloc(&d_mean0, nb * 3 * 8);
+    st.alloc(&d_scale0, nb * 3 * 8);
+    st.alloc(&d_ys, (size_t)B * T * ny * 8 + 8);
+    if (out_moments) st.alloc(&d_mom, (size_t)B * T * Z * 8 + 8);
+    if (out_means && mode != MFS_MODE_RAW) st.alloc(&d_means, (size_t)B * T * 3 * 8 + 8);
+    if (out_scales && mode == MFS_MODE_SCALED) st.alloc(&d_scales, (size_t)B * T * 3 * 8 + 8);
+    st.alloc(&d_nell, (size_t)B * 8);
+    st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_m0, m0, nb * Z * 8);
+    if (mean0 && mode != MFS_MODE_RAW) st.h2d(d_mean0, mean0, nb * 3 * 8);
+    if (scale0 && mode == MFS_MODE_SCALED) st.h2d(d_scale0, scale0, nb * 3 * 8);
+    st.h2d(d_ys, ys, (size_t)B * T * ny * 8);
+    if (st.err == hipSuccess) {
+        rc = mfs_plan_nd3_run(plan, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn, st.s);
         if (rc == MFS_OK) {
-            d2h(out_moments, d_mom, (size_t)B * T * Z * 8);
-            d2h(out_means, d_means, (size_t)B * T * 3 * 8);
-            d2h(out_scales, d_scales, (size_t)B * T * 3 * 8);
-            d2h(out_nell, d_nell, (size_t)B * 8);
-            d2h(out_first_nan, d_fn, (size_t)B * 4);
+            st.d2h(out_moments, d_mom, (size_t)B * T * Z * 8);
+            st.d2h(out_means, d_means, (size_t)B * T * 3 * 8);
+            st.d2h(out_scales, d_scales, (size_t)B * T * 3 * 8);
+            st.d2h(out_nell, d_nell, (size_t)B * 8);
+            st.d2h(out_first_nan, d_fn, (size_t)B * 4);
         }
     }
-    const hipError_t es = hipStreamSynchronize(s);   // always: the pool blocks go back on return
-    if (e == hipSuccess) e = es;
-    if (rc != MFS_OK) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_filter_nd3: %s", hipGetErrorString(e));
-    return MFS_OK;
+    return st.finish("mfs_filter_nd3", rc);
 }
 
 extern "C" int mfs_filter_nd3(const mfs_model_nd3* model, int mode, int N, int T, int B, int z,
@@ -1280,15 +1166,14 @@ extern "C" int mfs_elementary(int which, int n, const double* x, double* out, in
     if (!x || !out) return fail(MFS_EINVAL, "NULL buffer");
     HIP_TRY(hipSetDevice(device));
     double *d_x = nullptr, *d_o = nullptr;
-    mfs::Lease lease(device);
-    hipError_t e = lease.device_block(&d_x, (size_t)n * 8);
-    if (e == hipSuccess) e = lease.device_block(&d_o, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMemcpy(d_x, x, (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = mfs::launch_elementary(which, n, d_x, d_o, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, d_o, (size_t)n * 8, hipMemcpyDeviceToHost);
+    mfs::Staging st(device, nullptr, false);   // null stream; this diagnostic copies synchronously
+    st.alloc(&d_x, (size_t)n * 8);
+    st.alloc(&d_o, (size_t)n * 8);
+    if (st.err == hipSuccess) st.err = hipMemcpy(d_x, x, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (st.err == hipSuccess) st.err = mfs::launch_elementary(which, n, d_x, d_o, nullptr);
+    if (st.err == hipSuccess) st.err = hipMemcpy(out, d_o, (size_t)n * 8, hipMemcpyDeviceToHost);
     (void)hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(MFS_EHIP, "mfs_elementary: %s", hipGetErrorString(e));
-    return MFS_OK;
+    return st.finish("mfs_elementary", MFS_OK);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1300,32 +1185,26 @@ extern "C" int mfs_characteristic_1d(int N, int count, const double* ms, const d
     if (count < 0 || nz < 0) return fail(MFS_EINVAL, "negative count or nz");
     if (count == 0 || nz == 0) return MFS_OK;
     if (!ms || !zs || !out) return fail(MFS_EINVAL, "NULL buffer");
-    const int gi = (N + 1 <= 8) ? 3 : (N + 1 <= 16) ? 0 : (N + 1 <= 32) ? 1 : 2;
-    mfs::Cf1dLaunch launch = mfs::g_cf[N][gi];
+    const int gi = mfs::default_group(N);
+    mfs::Cf1dLaunch launch = mfs::g_fast[N][gi].cf;
     if (!launch) return fail(MFS_EUNSUPPORTED, "no kernel compiled for N = %d", N);
     HIP_TRY(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    const int G = (gi == 3) ? 8 : (gi == 0) ? 16 : (gi == 1) ? 32 : 64, fpb = 64 / G;
+    const int fpb = 64 / mfs::group_lanes(gi);
     double *d_ms = nullptr, *d_mean = nullptr, *d_scale = nullptr, *d_zs = nullptr, *d_out = nullptr;
-    hipError_t e = hipSuccess;
-    mfs::Lease lease(device);
-    auto alloc = [&](void** d, size_t bytes) { if (e == hipSuccess) e = lease.device_block((char**)d, bytes); };
-    alloc((void**)&d_ms, (size_t)count * 2 * N * 8);
-    alloc((void**)&d_zs, (size_t)nz * 8);
-    alloc((void**)&d_out, (size_t)count * nz * 16);
-    if (mean) alloc((void**)&d_mean, (size_t)count * 8);
-    if (scale) alloc((void**)&d_scale, (size_t)count * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ms, ms, (size_t)count * 2 * N * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_zs, zs, (size_t)nz * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && mean) e = hipMemcpyAsync(d_mean, mean, (size_t)count * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && scale) e = hipMemcpyAsync(d_scale, scale, (size_t)count * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
+    mfs::Staging st(device, stream, false);   // on the caller's stream, null included
+    st.alloc(&d_ms, (size_t)count * 2 * N * 8);
+    st.alloc(&d_zs, (size_t)nz * 8);
+    st.alloc(&d_out, (size_t)count * nz * 16);
+    if (mean) st.alloc(&d_mean, (size_t)count * 8);
+    if (scale) st.alloc(&d_scale, (size_t)count * 8);
+    st.h2d(d_ms, ms, (size_t)count * 2 * N * 8);
+    st.h2d(d_zs, zs, (size_t)nz * 8);
+    if (mean) st.h2d(d_mean, mean, (size_t)count * 8);
+    if (scale) st.h2d(d_scale, scale, (size_t)count * 8);
+    if (st.err == hipSuccess) {
         mfs::Cf1dArgs a{count, nz, d_ms, d_mean, d_scale, d_zs, d_out};
-        e = launch(a, (count + fpb - 1) / fpb, fpb * 2 * N * 8, s);
+        st.err = launch(a, (count + fpb - 1) / fpb, fpb * 2 * N * 8, st.s);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)count * nz * 16, hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);   // always: the pool blocks go back on return
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFS_ENOMEM : MFS_EHIP, "mfs_characteristic_1d: %s", hipGetErrorString(e));
-    return MFS_OK;
+    st.d2h(out, d_out, (size_t)count * nz * 16);
+    return st.finish("mfs_characteristic_1d", MFS_OK);
 }

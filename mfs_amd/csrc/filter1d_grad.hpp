@@ -561,6 +561,4 @@ __global__ __launch_bounds__(64, (grad_occ<N, P>())) void filter1d_grad_kernel(c
     }
 }
 
-using Filter1dGradLaunch = hipError_t (*)(const Filter1dGradArgs&, int n_filters, hipStream_t);
-
 }  // namespace mfs

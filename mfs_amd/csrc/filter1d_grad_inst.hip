@@ -3,10 +3,10 @@
 #include <cstdio>
 #include "filter1d_grad.hpp"
 #include "launch_util.hpp"
+#include "registry.hpp"
 
 namespace mfs {
 
-constexpr int kGradMaxN = 16, kGradMaxP = 4;
 Filter1dGradLaunch g_grad_table[kGradMaxN + 1][kGradMaxP + 1];
 
 // lanes per filter: lane l < N owns root l and the moment sums stride over the group, so N <= 8 runs on 8 lanes -- eight filters

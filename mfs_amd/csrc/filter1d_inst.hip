@@ -2,23 +2,13 @@
 // range so that `make -j` compiles them in parallel) and registers their launchers.
 #include "filter1d_fast.hpp"
 #include "launch_util.hpp"
+#include "registry.hpp"
 
 #ifndef MFS_NLO
 #error "compile with -DMFS_NLO=.. -DMFS_NHI=.."
 #endif
 
 namespace mfs {
-
-extern KernelEntry g_table[MFS_MAX_N + 1][kSlots];  // defined in capi.hip
-extern Filter1dFastLaunch g_fast_filter[MFS_MAX_N + 1][4];
-extern Filter1dFastLaunch g_fast_filter_wide[MFS_MAX_N + 1][4];  // nullptr where the default budget does not spill
-extern Filter1dFastLaunch g_fast_filter_ext[MFS_MAX_N + 1][4];       // extended variant (stable = 1, odd moment counts); default lane count only
-extern Filter1dFastLaunch g_fast_filter_ext_wide[MFS_MAX_N + 1][4];
-extern Quad1dLaunch g_quad_ext[MFS_MAX_N + 1][4];                     // quadrature entry with stable = 1
-extern int g_quad_ext_lds[MFS_MAX_N + 1][4];                         // its LDS doubles per filter
-extern int g_fast_ext_shift[MFS_MAX_N + 1][4];                      // extra LDS doubles per filter of the extended variant
-using Cf1dLaunch = hipError_t (*)(const Cf1dArgs&, int grid, int lds, hipStream_t);
-extern Cf1dLaunch g_cf[MFS_MAX_N + 1][4];
 
 constexpr int kBlockLdsBudget = 64 * 1024;
 
@@ -84,7 +74,8 @@ hipError_t launch_cf_fast(const Cf1dArgs& a, int grid, int lds, hipStream_t s) {
 
 template <int N, int G>
 void reg_fast(int gi) {
-    g_cf[N][gi] = &launch_cf_fast<N, G>;
+    FastEntry& f = g_fast[N][gi];
+    f.cf = &launch_cf_fast<N, G>;
     KernelEntry& e = g_table[N][3 + gi];  // gi: 0..2 = G 16 / 32 / 64, 3 = G 8
     // (A/B switch.  Three waves per SIMD for N <= 8 -- the config-4 shard's kernel -- is a 168-register build that spills 66
     //  registers: 59-62 ms against 54.6 at two waves, round 3.)
@@ -92,17 +83,19 @@ void reg_fast(int gi) {
 #define MFS_FAST_OCC_SMALL 2
 #endif
     constexpr int occ = (N <= 8) ? MFS_FAST_OCC_SMALL : (N <= 16) ? 2 : 1;
-    g_fast_filter[N][gi] = &launch_filter_fast<N, G, occ>;
+    f.filter = &launch_filter_fast<N, G, occ>;
     // stable = 1 / odd moment counts: the extended variant, for the default lane count of the order (others: dense path)
-    if constexpr (G == ((N + 1 <= 8) ? 8 : (N + 1 <= 16) ? 16 : (N + 1 <= 32) ? 32 : 64)) {
-        g_fast_filter_ext[N][gi] = &launch_filter_fast<N, G, occ, true>;
-        g_fast_ext_shift[N][gi] = FastTile<N, G>::kExtShift;
-        g_quad_ext[N][gi] = &launch_quad_fast_ext<N, G>;
-        g_quad_ext_lds[N][gi] = FastTile<N, G>::oLik + FastTile<N, G>::kExtShift;
-        if constexpr (N >= 14 && N <= 16) g_fast_filter_ext_wide[N][gi] = &launch_filter_fast<N, G, 1, true>;
+    if constexpr (G == group_lanes(default_group(N))) {
+        f.ext = &launch_filter_fast<N, G, occ, true>;
+        f.ext_shift = FastTile<N, G>::kExtShift;
+        f.quad_ext = &launch_quad_fast_ext<N, G>;
+        f.quad_ext_lds = FastTile<N, G>::oLik + FastTile<N, G>::kExtShift;
+        // one-wave-per-SIMD register budget for the orders that spill at two
+        if constexpr (N >= 14 && N <= 16) {
+            f.ext_wide = &launch_filter_fast<N, G, 1, true>;
+            f.wide = &launch_filter_fast<N, G, 1>;
+        }
     }
-    // one-wave-per-SIMD register budget for the orders that spill at two (their default lane count only)
-    if constexpr (N >= 14 && N <= 16 && G == ((N + 1 <= 16) ? 16 : 32)) g_fast_filter_wide[N][gi] = &launch_filter_fast<N, G, 1>;
     e.filter = nullptr;
     e.quad = &launch_quad_fast<N, G>;
     e.lds_doubles_per_filter = FastTile<N, G>::fixedDoubles;

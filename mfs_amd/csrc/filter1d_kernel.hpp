@@ -590,27 +590,8 @@ __global__ __launch_bounds__(WPB * 64) void quadrature1d_kernel(const Quad1dArgs
     }
 }
 
-// launcher signature shared by the per-N translation units
-using Filter1dLaunch = hipError_t (*)(const Filter1dArgs&, int grid, int lds_bytes, hipStream_t);
-using Quad1dLaunch = hipError_t (*)(const Quad1dArgs&, int grid, int lds_bytes, hipStream_t);
-
-struct KernelEntry {
-    Filter1dLaunch filter;
-    Quad1dLaunch quad;
-    int lds_doubles_per_filter;  // dense: complete; fast: fixed part, the model table is added at launch
-    int waves_per_block;
-    int lanes_per_filter;
-};
-
-// registry slots per N: [0..2] dense path with G = 16 / 32 / 64, [3..5] fast path with G = 16 / 32 / 64,
-// [6] fast path with G = 8 (N <= 7: eight filters per wavefront)
-constexpr int kSlots = 7;
-using Filter1dFastLaunch = hipError_t (*)(const Filter1dArgs&, int grid, int lds_doubles_per_filter, hipStream_t);
-// specialised one-wave builds of the fast kernel (filter1d_fast.hpp, SPEC): tables of at most kSpecTop padded degrees, in
-// kSpecShapes row shapes
+// specialised one-wave builds of the fast kernel (filter1d_fast.hpp, SPEC): tables of at most kSpecTop padded degrees (their
+// launcher types and tables, like every other, are declared in registry.hpp)
 constexpr int kSpecTop = 4;
-constexpr int kSpecShapes = 4;
-// slot of a table shape among them (-1 = normal closure, 2 / 4 / 6 = operator terms), or -1 if the shape has no such build
-constexpr int spec_shape_index(const int spec) { return (spec == -1) ? 0 : (spec == 2) ? 1 : (spec == 4) ? 2 : (spec == 6) ? 3 : -1; }
 
 }  // namespace mfs

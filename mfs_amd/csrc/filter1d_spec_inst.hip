@@ -4,14 +4,13 @@
 // compiles them next to the order ranges of filter1d_inst.hip.
 #include "filter1d_fast.hpp"
 #include "launch_util.hpp"
+#include "registry.hpp"
 
 #ifndef MFS_SPEC_N
 #error "compile with -DMFS_SPEC_N=14..16"
 #endif
 
 namespace mfs {
-
-extern Filter1dFastLaunch g_fast_filter_spec[MFS_MAX_N + 1][kSpecShapes];  // defined in capi.hip
 
 template <int N, int G, int SPEC>
 hipError_t launch_filter_spec(const Filter1dArgs& a, int grid, int lds_doubles, hipStream_t s) {
@@ -25,11 +24,12 @@ struct SpecRegistrar {
     SpecRegistrar() {
         constexpr int N = MFS_SPEC_N;
         static_assert(N >= 14 && N <= 16, "orders with a one-wave build");
-        constexpr int G = (N + 1 <= 16) ? 16 : 32;   // the default lane count of the order, as for g_fast_filter_wide
-        g_fast_filter_spec[N][spec_shape_index(-1)] = &launch_filter_spec<N, G, -1>;
-        g_fast_filter_spec[N][spec_shape_index(2)] = &launch_filter_spec<N, G, 2>;
-        g_fast_filter_spec[N][spec_shape_index(4)] = &launch_filter_spec<N, G, 4>;
-        g_fast_filter_spec[N][spec_shape_index(6)] = &launch_filter_spec<N, G, 6>;
+        constexpr int gi = default_group(N), G = group_lanes(gi);   // the default lane count of the order, as for FastEntry::wide
+        Filter1dFastLaunch* spec = g_fast[N][gi].spec;
+        spec[spec_shape_index(-1)] = &launch_filter_spec<N, G, -1>;
+        spec[spec_shape_index(2)] = &launch_filter_spec<N, G, 2>;
+        spec[spec_shape_index(4)] = &launch_filter_spec<N, G, 4>;
+        spec[spec_shape_index(6)] = &launch_filter_spec<N, G, 6>;
     }
 };
 static SpecRegistrar spec_registrar_instance;

@@ -2,12 +2,10 @@
 // TK = 1 Normal closure), without and with joint likelihood factors, and registers their launchers.
 #include "filternd3_kernel.hpp"
 #include "launch_util.hpp"
+#include "registry.hpp"
 
 namespace mfs {
 
-using FilterNd3Launch = hipError_t (*)(const FilterNd3Args&, int grid, hipStream_t);
-using FilterNd3JointLaunch = hipError_t (*)(const FilterNd3Args&, const FilterNd3Joint&, int grid, hipStream_t);
-struct Nd3Entry { FilterNd3Launch launch, launch_gauss; int S, Z, lds_bytes; FilterNd3JointLaunch joint, joint_gauss; };
 Nd3Entry g_nd3_table[MFS_ND3_MAX_N + 1];
 
 template <int N, int TK>

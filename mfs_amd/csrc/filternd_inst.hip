@@ -2,12 +2,11 @@
 // (TK = 0 operator table with |kappa| <= 4, TK = 3 the same with the node tables of a joint likelihood, TK = 2 with |kappa| <= 6, TK = 1 Normal closure), and registers their launchers.
 #include "filternd_kernel.hpp"
 #include "launch_util.hpp"
+#include "registry.hpp"
 
 namespace mfs {
 
-using FilterNdLaunch = hipError_t (*)(const FilterNdArgs&, int grid, hipStream_t);
-struct NdEntry { FilterNdLaunch launch, launch_gauss, launch_hi, launch_joint; int S, Z, lds_bytes, carry_doubles; };
-NdEntry g_nd_table[8];
+NdEntry g_nd_table[kNdMaxN + 1];
 
 template <int N, int TK>
 hipError_t launch_nd(const FilterNdArgs& a, int grid, hipStream_t s) {
@@ -26,7 +25,7 @@ void reg_nd() {
     g_nd_table[N] = NdEntry{&launch_nd<N, 0>, &launch_nd<N, 1>, &launch_nd<N, 2>, joint, NdTile<N, 0>::S, NdTile<N, 0>::Z,
                             (d0 > d1 ? (d0 > d2 ? d0 : d2) : (d1 > d2 ? d1 : d2)) * 8, NdTile<N, 0>::kCarry};
     static_assert(NdTile<N, 0>::kCarry == NdTile<N, 1>::kCarry && NdTile<N, 0>::kCarry == NdTile<N, 2>::kCarry, "one carry layout");
-    if constexpr (N < 7) reg_nd<N + 1>();
+    if constexpr (N < kNdMaxN) reg_nd<N + 1>();
 }
 
 // diagnostic: the kernels' own elementary functions on an array (tests bound their error against libm)

@@ -1,0 +1,78 @@
+// registry.hpp -- every launcher type and launcher table of the library, declared once.  The *_inst.hip translation units
+// fill the tables from static registrars; capi.hip reads them.  A null launcher means "not compiled / does not exist".
+// Host-only: the argument structs are only named here (their definitions live with the kernels).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/mfs_hip.h"
+
+namespace mfs {
+
+struct Filter1dArgs;
+struct Quad1dArgs;
+struct Cf1dArgs;
+struct Filter1dGradArgs;
+struct FilterNdArgs;
+struct FilterNd3Args;
+struct FilterNd3Joint;
+
+// ---- 1-D: dense (LDS-tile) and fast (register-resident) paths
+using Filter1dLaunch = hipError_t (*)(const Filter1dArgs&, int grid, int lds_bytes, hipStream_t);
+using Quad1dLaunch = hipError_t (*)(const Quad1dArgs&, int grid, int lds_bytes, hipStream_t);
+using Filter1dFastLaunch = hipError_t (*)(const Filter1dArgs&, int grid, int lds_doubles_per_filter, hipStream_t);
+using Cf1dLaunch = hipError_t (*)(const Cf1dArgs&, int grid, int lds, hipStream_t);
+
+struct KernelEntry {
+    Filter1dLaunch filter;       // dense slots only
+    Quad1dLaunch quad;
+    int lds_doubles_per_filter;  // dense: complete; fast: fixed part, the model table is added at launch
+    int waves_per_block;
+    int lanes_per_filter;
+};
+
+// slots per N: [0..2] dense path with G = 16 / 32 / 64, [3 + gi] fast path of lane group gi
+constexpr int kSlots = 7;
+extern KernelEntry g_table[MFS_MAX_N + 1][kSlots];   // defined in capi.hip, filled by filter1d_inst.hip
+
+// lane groups of the fast path: gi 0..2 = 16 / 32 / 64 lanes per filter, gi 3 = 8 lanes (eight filters per wavefront)
+constexpr int group_lanes(const int gi) { return (gi == 3) ? 8 : 16 << gi; }
+// the default group of an order: the smallest that holds the N + 1 rows of the extended Hankel matrix
+constexpr int default_group(const int N) { return (N + 1 <= 8) ? 3 : (N + 1 <= 16) ? 0 : (N + 1 <= 32) ? 1 : 2; }
+
+// specialised one-wave builds of the fast kernel (filter1d_fast.hpp, SPEC): kSpecShapes table shapes
+constexpr int kSpecShapes = 4;
+// slot of a table shape among them (-1 = normal closure, 2 / 4 / 6 = operator terms), or -1 if the shape has no such build
+constexpr int spec_shape_index(const int spec) { return (spec == -1) ? 0 : (spec == 2) ? 1 : (spec == 4) ? 2 : (spec == 6) ? 3 : -1; }
+
+// what the fast path has for one (N, lane group) beside its g_table slot
+struct FastEntry {
+    Filter1dFastLaunch filter;             // the plain build
+    Filter1dFastLaunch wide;               // one-wave-per-SIMD register budget (the orders that spill at two; default group only)
+    Filter1dFastLaunch ext, ext_wide;      // extended variant (stable = 1, odd moment counts; default group only)
+    Filter1dFastLaunch spec[kSpecShapes];  // [spec_shape_index]: specialised one-wave builds (default group of N = 14..16)
+    Quad1dLaunch quad_ext;                 // quadrature entry with stable = 1
+    Cf1dLaunch cf;                         // characteristic function
+    int ext_shift;                         // extra LDS doubles per filter of the extended variant
+    int quad_ext_lds;                      // LDS doubles per filter of quad_ext
+};
+extern FastEntry g_fast[MFS_MAX_N + 1][4];   // defined in capi.hip, filled by filter1d_inst.hip (spec: filter1d_spec_inst.hip)
+
+// ---- 1-D gradient: [N][n_par]
+using Filter1dGradLaunch = hipError_t (*)(const Filter1dGradArgs&, int n_filters, hipStream_t);
+constexpr int kGradMaxN = 16, kGradMaxP = 4;
+extern Filter1dGradLaunch g_grad_table[kGradMaxN + 1][kGradMaxP + 1];   // defined in filter1d_grad_inst.hip
+
+// ---- N-D, d = 2: [N]
+using FilterNdLaunch = hipError_t (*)(const FilterNdArgs&, int grid, hipStream_t);
+struct NdEntry { FilterNdLaunch launch, launch_gauss, launch_hi, launch_joint; int S, Z, lds_bytes, carry_doubles; };
+constexpr int kNdMaxN = 7;
+extern NdEntry g_nd_table[kNdMaxN + 1];   // defined in filternd_inst.hip
+hipError_t launch_elementary(int which, int n, const double* d_x, double* d_out, hipStream_t s);   // filternd_inst.hip
+
+// ---- N-D, d = 3: [N]
+using FilterNd3Launch = hipError_t (*)(const FilterNd3Args&, int grid, hipStream_t);
+using FilterNd3JointLaunch = hipError_t (*)(const FilterNd3Args&, const FilterNd3Joint&, int grid, hipStream_t);
+struct Nd3Entry { FilterNd3Launch launch, launch_gauss; int S, Z, lds_bytes; FilterNd3JointLaunch joint, joint_gauss; };
+extern Nd3Entry g_nd3_table[MFS_ND3_MAX_N + 1];   // defined in filternd3_inst.hip
+
+}  // namespace mfs
