@@ -184,12 +184,23 @@ int mfs_plan_1d_geometry(const mfs_plan_1d* plan, int* lanes_per_filter, int* fi
 /* which build of the 1-D filter kernel the plan launches, decided at plan creation.  The specialised one-wave build keeps
  * the model's coefficient table in registers and runs the two halves of a step as straight-line code; it exists for the
  * orders with a one-wave build (N = 14..16), operator tables of 2 / 4 / 6 terms and normal closures of polynomial degree
- * <= 3, and computes bit for bit what the generic build computes (MFS_FAST_BUILD=generic keeps the generic one). */
+ * <= 3, and computes bit for bit what the generic build computes (MFS_FAST_BUILD=generic keeps the generic one).  A
+ * specialised build that also has the model's step switches compiled in (mfs_plan_1d_kernel_traits below) reports the same
+ * code, MFS_BUILD_FAST_ONE_WAVE_SPEC. */
 #define MFS_BUILD_DENSE 0
 #define MFS_BUILD_FAST 1
 #define MFS_BUILD_FAST_ONE_WAVE 2
 #define MFS_BUILD_FAST_ONE_WAVE_SPEC 3
 int mfs_plan_1d_kernel_build(const mfs_plan_1d* plan, int* build);
+/* the step traits of the plan's kernel build.  MFS_TRAITS_RUNTIME: moment mode, u-map and likelihood law are run-time values
+ * of the launch (every build but the ones below).  Otherwise the plan runs a specialised one-wave build with the three
+ * compiled in, the likelihood parameters in registers and the output stores decided before the time loop; it exists for the
+ * combinations named here, central mode only, and computes bit for bit what the run-time-traits build computes
+ * (MFS_FAST_TRAITS=runtime, read at plan creation, keeps that one). */
+#define MFS_TRAITS_RUNTIME 0
+#define MFS_TRAITS_CENTRAL_TANH_BERNOULLI 1      /* operator table of 6 terms (TME-3) or normal closure */
+#define MFS_TRAITS_CENTRAL_IDENTITY_GAUSSIAN 2   /* normal closure */
+int mfs_plan_1d_kernel_traits(const mfs_plan_1d* plan, int* traits);
 
 /*
  * ---- negative log-likelihood and its gradient, forward mode inside the time loop ------------------------------------

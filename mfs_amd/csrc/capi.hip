@@ -110,7 +110,7 @@ struct mfs_plan_1d {
     // the kernel build the plan runs, resolved once at creation (resolve_launch): its launcher, the launcher's LDS argument
     // (bytes per block for the dense path, doubles per filter for the fast one) and its MFS_BUILD_* code
     mfs::Filter1dLaunch launch = nullptr;
-    int launch_lds = 0, build = MFS_BUILD_DENSE;
+    int launch_lds = 0, build = MFS_BUILD_DENSE, traits = MFS_TRAITS_RUNTIME;
     double* d_coef = nullptr;
     double* d_lik = nullptr;
     double* c_mom = nullptr;
@@ -215,7 +215,9 @@ int mfs_plan_1d_destroy(mfs_plan_1d* p) {
 // waves, so with at most one per SIMD (grid <= 4 x compute units) the wide-register one-wave builds cost nothing -- the
 // specialised one (table in registers, straight-line halves: filter1d_fast.hpp) where the plain kernel's table shape has
 // one, else the generic one where the order has one; otherwise the two-wave build.  MFS_FAST_BUILD=generic skips the
-// specialised builds (A/B switch, like MFS_PREDICT_RULE).
+// specialised builds (A/B switch, like MFS_PREDICT_RULE).  A specialised build exists a second time with the model's step
+// switches compiled in (StepTraits) for a few (table shape, mode, u-map, law) combinations: the plan takes it where its model
+// is one of them, MFS_FAST_TRAITS=runtime keeps the run-time-traits build.
 static void resolve_launch(mfs_plan_1d* p, int slot, bool ext) {
     if (slot < 3) {
         p->launch = mfs::g_table[p->N][slot].filter; p->launch_lds = p->lds_bytes; p->build = MFS_BUILD_DENSE;
@@ -230,6 +232,12 @@ static void resolve_launch(mfs_plan_1d* p, int slot, bool ext) {
         const int shape = mfs::spec_shape_index((p->model.trans_kind == MFS_TRANS_OPERATOR) ? p->model.n_terms : -1);
         const char* e = getenv("MFS_FAST_BUILD");
         if (shape >= 0 && !(e && strcmp(e, "generic") == 0)) spec = fe.spec[shape];   // null but for the default group of N = 14..16
+        const int ti = mfs::traits_index(p->mode, p->model.umap, p->model.lik_kind);
+        const char* et = getenv("MFS_FAST_TRAITS");
+        if (spec && ti != MFS_TRAITS_RUNTIME && !(et && strcmp(et, "runtime") == 0) && fe.spec_traits[shape][ti - 1]) {
+            spec = fe.spec_traits[shape][ti - 1];
+            p->traits = ti;
+        }
     }
     p->launch = spec ? spec : wide ? wide : ext ? fe.ext : fe.filter;
     p->launch_lds = p->lds_doubles;
@@ -307,6 +315,12 @@ int mfs_plan_1d_geometry(const mfs_plan_1d* p, int* lanes_per_filter, int* filte
 int mfs_plan_1d_kernel_build(const mfs_plan_1d* p, int* build) {
     if (!p || !build) return fail(MFS_EINVAL, "plan or build is NULL");
     *build = p->build;
+    return MFS_OK;
+}
+
+int mfs_plan_1d_kernel_traits(const mfs_plan_1d* p, int* traits) {
+    if (!p || !traits) return fail(MFS_EINVAL, "plan or traits is NULL");
+    *traits = p->traits;
     return MFS_OK;
 }
 

@@ -434,24 +434,41 @@ constexpr int kLfacMax = 32;
 #endif
 constexpr double kLagStop = MFS_LAG_STOP;
 
+// likelihood parameters held by value: the fixed-traits one-wave builds read them from LDS once, before the time loop
+struct LikRegs { double v[MFS_MAX_LIK]; };
+__device__ __forceinline__ double lik_at(const double* lp, const int i) { return lp[i]; }
+__device__ __forceinline__ double lik_at(const LikRegs* lp, const int i) { return lp->v[i]; }
+__device__ __forceinline__ const double* lik_ptr(const double* lp) { return lp; }
+__device__ __forceinline__ const double* lik_ptr(const LikRegs* lp) { return lp->v; }
+
 // Poisson pmf with log(y!) looked up for the counts that actually occur (y <= 32) instead of a sum of logs per step
-__device__ __forceinline__ double likelihood_fast(const int kind, const double* __restrict__ lp,
+// (LP: double -- the parameters in the LDS staging area -- or LikRegs)
+template <class LP>
+__device__ __forceinline__ double likelihood_fast(const int kind, const LP* __restrict__ lp,
                                                   const double* __restrict__ lfac, const double y, const double x) {
     if (kind == MFS_LIK_POISSON_SOFTPLUS) {
-        const double rate = fast_log(1.0 + fast_exp(lp[0] * x));
+        const double rate = fast_log(1.0 + fast_exp(lik_at(lp, 0) * x));
         const double lf = (y >= 0.0 && y <= (double)kLfacMax && y == floor(y)) ? lfac[(int)y] : log_factorial(y);
         return fast_exp(y * fast_log(rate) - rate - lf);
     }
     if (kind == MFS_LIK_BERNOULLI_LOGISTIC) {
-        const double z = lp[0] + x * (lp[1] + x * (lp[2] + x * lp[3]));
+        const double z = lik_at(lp, 0) + x * (lik_at(lp, 1) + x * (lik_at(lp, 2) + x * lik_at(lp, 3)));
         const double p = rcp_sat(1.0 + fast_exp(-z));   // e^{-z} may be +inf: p = 0, as 1 / (1 + inf) upstream
         return (y > 0.5) ? p : 1.0 - p;
     }
     if (kind == MFS_LIK_GAUSSIAN) {
-        const double r = y - fma(lp[0], x, lp[1]);
-        return fast_exp(-0.5 * r * r * rcp_nr(lp[2])) * rsq_nr(6.283185307179586476925 * lp[2]);
+        const double r = y - fma(lik_at(lp, 0), x, lik_at(lp, 1));
+        return fast_exp(-0.5 * r * r * rcp_nr(lik_at(lp, 2))) * rsq_nr(6.283185307179586476925 * lik_at(lp, 2));
     }
-    return likelihood(kind, lp, y, x);
+    return likelihood(kind, lik_ptr(lp), y, x);
+}
+
+// the parameters from registers (REGS) or from their LDS staging area
+template <bool REGS>
+__device__ __forceinline__ double likelihood_sel(const int kind, const LikRegs& lpr, const double* __restrict__ lp,
+                                                 const double* __restrict__ lfac, const double y, const double x) {
+    if constexpr (REGS) return likelihood_fast(kind, &lpr, lfac, y, x);
+    else return likelihood_fast(kind, lp, lfac, y, x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -893,15 +910,55 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
 //  MFS_SPEC_AB_TABLE 0 = the table in registers, 1 = the LDS Horner pass; MFS_SPEC_AB_HALVES 0 = two straight-line halves,
 //  1 = the run-time loop over the halves.  DESIGN.md section 6.  The dead rows need no switch: with the number of terms a
 //  compile-time constant the compiler drops their loads and multiply-adds on either table route.)
+// TR = the step traits of a specialised build: the model switches the time loop would otherwise test at every step -- moment
+// mode, u-map, likelihood law -- as compile-time constants (StepTraits<MODE, UMAP, LIK>; the default StepTraits<> leaves all
+// three run-time values of Filter1dArgs and compiles to the code without the parameter).  A fixed-traits build (i) emits one
+// mode's, one u-map's and one law's code, (ii) reads the likelihood parameters from their LDS staging area once, before the
+// time loop, and keeps them in registers like the coefficient table, and (iii) decides the output stores before the loop:
+// per-lane predicates and running pointers instead of a test of each output pointer at each step.  The plan picks such a
+// build for the combinations the shipped one-wave models reach (registry.hpp, kTraitSets).  Same rule as SPEC: no
+// floating-point operation that feeds an output changes.
+// (A/B switches, each against the full fixed-traits build: MFS_TRAITS_AB_SWITCHES 1 = mode / u-map / law stay run-time
+//  values, MFS_TRAITS_AB_LIKREGS 1 = the likelihood parameters stay in LDS, MFS_TRAITS_AB_CARRYWAIT 1 = the waits for the carry loads stay at their
+//  first uses inside the loop, MFS_TRAITS_AB_OUTPUTS 1 = the per-step tests of
+//  the output pointers.  DESIGN.md section 6.)
 #ifndef MFS_SPEC_AB_TABLE
 #define MFS_SPEC_AB_TABLE 0
 #endif
 #ifndef MFS_SPEC_AB_HALVES
 #define MFS_SPEC_AB_HALVES 0
 #endif
-template <int N, int G, int WPB, int OCC, bool EXT = false, int SPEC = 0>
+#ifndef MFS_TRAITS_AB_SWITCHES
+#define MFS_TRAITS_AB_SWITCHES 0
+#endif
+#ifndef MFS_TRAITS_AB_LIKREGS
+#define MFS_TRAITS_AB_LIKREGS 0
+#endif
+#ifndef MFS_TRAITS_AB_OUTPUTS
+#define MFS_TRAITS_AB_OUTPUTS 0
+#endif
+#ifndef MFS_TRAITS_AB_CARRYWAIT
+#define MFS_TRAITS_AB_CARRYWAIT 0
+#endif
+template <int MODE = -1, int UMAP = -1, int LIK = -1>
+struct StepTraits {
+    static_assert((MODE < 0) == (UMAP < 0) && (MODE < 0) == (LIK < 0), "all three fixed, or all three run-time");
+    static constexpr bool fixed = MODE >= 0;
+    static constexpr int mode = MODE, umap = UMAP, lik = LIK;
+};
+template <int N, int G, int WPB, int OCC, bool EXT = false, int SPEC = 0, class TR = StepTraits<>>
 __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filter1dArgs a, const int lds_doubles) {
     static_assert(SPEC == 0 || (!EXT && OCC == 1), "specialised builds: plain kernel, one wave per SIMD");
+    static_assert(!TR::fixed || SPEC != 0, "fixed step traits: specialised builds only");
+    // the model switches a fixed-traits build knows at compile time
+    constexpr bool kFixSwitches = TR::fixed && (MFS_TRAITS_AB_SWITCHES == 0);
+    constexpr bool kLikRegs = TR::fixed && (MFS_TRAITS_AB_LIKREGS == 0);
+    constexpr bool kOutHoist = TR::fixed && (MFS_TRAITS_AB_OUTPUTS == 0);
+    constexpr bool kCarryWait = TR::fixed && (MFS_TRAITS_AB_CARRYWAIT == 0);
+    // (read where they are used, as `a.mode` was: a run-time-traits build keeps its device code to the instruction)
+    const auto mode = [&]() __attribute__((always_inline)) { if constexpr (kFixSwitches) return (int)TR::mode; else return a.mode; };
+    const auto umap = [&]() __attribute__((always_inline)) { if constexpr (kFixSwitches) return (int)TR::umap; else return a.umap; };
+    const auto lik_kind = [&]() __attribute__((always_inline)) { if constexpr (kFixSwitches) return (int)TR::lik; else return a.lik_kind; };
     static_assert(SPEC >= -1 && SPEC <= MFS_MAX_TERMS, "table shape");
     using L = FastTile<N, G>;
     constexpr int M2 = L::M2, TLD = L::TLD;
@@ -934,7 +991,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
         }
         const double* ls = a.lik + (a.lik_batched ? (size_t)b * a.n_lik : 0);
         for (int e = l; e < MFS_MAX_LIK; e += G) S[L::oLik + kShift + e] = (e < a.n_lik) ? ls[e] : 0.0;
-        if (a.lik_kind == MFS_LIK_POISSON_SOFTPLUS)
+        if (lik_kind() == MFS_LIK_POISSON_SOFTPLUS)
             for (int e = l; e <= kLfacMax; e += G) lfac[e] = log_factorial((double)e);
     }
     double mean = 0.0, scale = 1.0, nell = 0.0;
@@ -942,8 +999,8 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
     if (a.t_begin == 0) {
         const double* src = a.m0 + (a.m0_batched ? (size_t)b * MS : 0);
         for (int n = l; n < M2; n += G) mom[n] = src[n];
-        if (a.mode != MFS_MODE_RAW) mean = a.mean0[a.m0_batched ? b : 0];
-        if (a.mode == MFS_MODE_SCALED) scale = a.scale0[a.m0_batched ? b : 0];
+        if (mode() != MFS_MODE_RAW) mean = a.mean0[a.m0_batched ? b : 0];
+        if (mode() == MFS_MODE_SCALED) scale = a.scale0[a.m0_batched ? b : 0];
     } else {
         for (int n = l; n < M2; n += G) mom[n] = a.c_mom[(size_t)b * M2 + n];
         mean = a.c_mean[b];
@@ -965,6 +1022,24 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
         for (int q = 0; q < kSpecTop; ++q)
 #pragma unroll
             for (int r = 0; r < SR; ++r) tabr[q][r] = coef[q * kCoefRows + ((r == kVarReg) ? MFS_MAX_TERMS : r)];
+    }
+    // the likelihood parameters: like the table, time-invariant for the launch (the staging loop above has been followed by a
+    // wave_sync).  The entries a law does not read are dropped by the compiler.
+    LikRegs lpr;
+    if constexpr (kLikRegs) {
+#pragma unroll
+        for (int e = 0; e < MFS_MAX_LIK; ++e) lpr.v[e] = lp[e];
+    }
+    // output stores of a fixed-traits build: which lanes store, and where, decided here.  (out_scale is null outside scaled
+    // mode: plan_args of capi.hip, the one place that fills Filter1dArgs for a run.)
+    bool st_m0 = false, st_m1 = false, st_mean = false, st_scale = false;
+    size_t o_mom = ((size_t)b * a.T + a.t_begin) * MS + l, o_mean = (size_t)b * a.T + a.t_begin;   // running element offsets
+    if constexpr (kOutHoist) {
+        if (a.out_mom) {
+            st_m0 = l < MS; st_m1 = l + G < MS;
+        }
+        if (a.out_mean) st_mean = (l == 0);
+        if (mode() == MFS_MODE_SCALED && a.out_scale) st_scale = (l == 0);
     }
     const double* yrow = a.ys + (size_t)b * a.T;
     bool dead = (first_nan >= 0);
@@ -988,6 +1063,12 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
         gA = a.c_lam[((size_t)b * 2 + 0) * G + l];
         gW = a.c_lam[((size_t)b * 2 + 1) * G + l];
         have_atoms = true;
+    }
+    if constexpr (kCarryWait) {
+        // every value loaded from memory above is used HERE, so that its wait is in front of the time loop.  Left to its
+        // first use in the loop, the wait is an s_waitcnt vmcnt(0) executed at every step (the counter is in order: it also
+        // waits for the output stores of the step before).
+        asm volatile("" : "+v"(mean), "+v"(scale), "+v"(nell), "+v"(gA), "+v"(gW), "+v"(first_nan));
     }
     double ywin = 0.0;                  // window of measurements (16 steps, or G when G < 16), one per lane
 #ifdef MFS_EXT_DEBUG
@@ -1030,7 +1111,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                 if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[11 + half] += g_1d_stamps[10] - it_before;
 #endif
                 F1_STAMP_BEGIN;
-                const double u = (a.umap == MFS_U_TANH) ? fast_tanh(x) : x;
+                const double u = (umap() == MFS_U_TANH) ? fast_tanh(x) : x;
                 double c = 0.0, inv_sc = 1.0, py = 1.0, ipy = 1.0;
                 if (half == 0) {
                     F1_STAMP(13);
@@ -1056,10 +1137,10 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                         mu = fma(a.mean_x_coef, x, rows[0]);
                         var = rows[1];
                     }
-                    if (a.mode != MFS_MODE_RAW) {
+                    if (mode() != MFS_MODE_RAW) {
                         mean = gsum<G>(w * mu);
                         c = mean;
-                        if (a.mode == MFS_MODE_SCALED) {
+                        if (mode() == MFS_MODE_SCALED) {
                             scale = sqrt(gsum<G>(w * var));
                             inv_sc = 1.0 / scale;
                         }
@@ -1095,19 +1176,24 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                     }
                 } else {
                     // ---- update (filtering.py:82-85 / 151-157 / 228-236)
-                    const double wl = node ? w * likelihood_fast(a.lik_kind, lp, lfac, y, x) : 0.0;
+                    const double wl = node ? w * likelihood_sel<kLikRegs>(lik_kind(), lpr, lp, lfac, y, x) : 0.0;
                     py = gsum<G>(wl);
                     ipy = rcp_nr(py);
                     F1_STAMP(17);
-                    if (a.mode != MFS_MODE_RAW) {
+                    if (mode() != MFS_MODE_RAW) {
                         mean = gsum<G>(wl * x) * ipy;
                         c = mean;
                     }
-                    if (a.mode == MFS_MODE_SCALED) {
+                    if (mode() == MFS_MODE_SCALED) {
                         scale = sqrt(gsum<G>(wl * (x - c) * (x - c)) * ipy);
                         inv_sc = 1.0 / scale;
                     }
-                    const double dx = (x - c) * inv_sc;
+                    double dx;
+                    {   // not contracted: with the mode a compile-time constant c is visibly the product gsum * ipy and
+                        // inv_sc is 1, and x - c would fuse into one multiply-add that the run-time-mode builds cannot form
+#pragma clang fp contract(off)
+                        dx = (x - c) * inv_sc;
+                    }
                     {   // the spare lanes shadow the last eigenvalue (the DPP read must run with the node lanes active)
                         const double last = bcast<G, N - 1>(dx);
                         gA = node ? dx : last;
@@ -1172,14 +1258,24 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
             mean = qnan; scale = qnan; nell = qnan;
             wave_sync();
         }
-        if (a.out_mom) {
-            double* dst = a.out_mom + ((size_t)b * a.T + t) * MS;
-            if (l < MS) dst[l] = out0;
-            if (l + G < MS) dst[l + G] = out1;
-        }
-        if (l == 0) {
-            if (a.out_mean) a.out_mean[(size_t)b * a.T + t] = mean;
-            if (a.out_scale) a.out_scale[(size_t)b * a.T + t] = scale;
+        if constexpr (kOutHoist) {
+            // (a pointer is formed only under its predicate: an absent output is never the base of an address)
+            if (st_m0) a.out_mom[o_mom] = out0;
+            if (st_m1) a.out_mom[o_mom + G] = out1;
+            o_mom += MS;
+            if (st_mean) a.out_mean[o_mean] = mean;
+            if (mode() == MFS_MODE_SCALED) { if (st_scale) a.out_scale[o_mean] = scale; }
+            o_mean += 1;
+        } else {
+            if (a.out_mom) {
+                double* dst = a.out_mom + ((size_t)b * a.T + t) * MS;
+                if (l < MS) dst[l] = out0;
+                if (l + G < MS) dst[l + G] = out1;
+            }
+            if (l == 0) {
+                if (a.out_mean) a.out_mean[(size_t)b * a.T + t] = mean;
+                if (a.out_scale) a.out_scale[(size_t)b * a.T + t] = scale;
+            }
         }
     }
     if (a.t_end >= a.T) {

@@ -44,12 +44,25 @@ constexpr int kSpecShapes = 4;
 // slot of a table shape among them (-1 = normal closure, 2 / 4 / 6 = operator terms), or -1 if the shape has no such build
 constexpr int spec_shape_index(const int spec) { return (spec == -1) ? 0 : (spec == 2) ? 1 : (spec == 4) ? 2 : (spec == 6) ? 3 : -1; }
 
+// fixed step traits of the specialised builds (filter1d_fast.hpp, StepTraits): the (mode, u-map, likelihood) combinations a
+// shipped model reaches with a one-wave build.  The value is what mfs_plan_1d_kernel_traits reports (MFS_TRAITS_*); 0 = the
+// three stay run-time values.
+constexpr int kTraitSets = 2;
+constexpr int traits_index(const int mode, const int umap, const int lik_kind) {
+    return (mode != MFS_MODE_CENTRAL) ? MFS_TRAITS_RUNTIME
+         : (umap == MFS_U_TANH && lik_kind == MFS_LIK_BERNOULLI_LOGISTIC) ? MFS_TRAITS_CENTRAL_TANH_BERNOULLI
+         : (umap == MFS_U_IDENTITY && lik_kind == MFS_LIK_GAUSSIAN) ? MFS_TRAITS_CENTRAL_IDENTITY_GAUSSIAN
+         : MFS_TRAITS_RUNTIME;
+}
+
 // what the fast path has for one (N, lane group) beside its g_table slot
 struct FastEntry {
     Filter1dFastLaunch filter;             // the plain build
     Filter1dFastLaunch wide;               // one-wave-per-SIMD register budget (the orders that spill at two; default group only)
     Filter1dFastLaunch ext, ext_wide;      // extended variant (stable = 1, odd moment counts; default group only)
     Filter1dFastLaunch spec[kSpecShapes];  // [spec_shape_index]: specialised one-wave builds (default group of N = 14..16)
+    Filter1dFastLaunch spec_traits[kSpecShapes][kTraitSets];   // [spec_shape_index][traits_index - 1]: the same with fixed step
+                                                               // traits; null where the pair has no build
     Quad1dLaunch quad_ext;                 // quadrature entry with stable = 1
     Cf1dLaunch cf;                         // characteristic function
     int ext_shift;                         // extra LDS doubles per filter of the extended variant
