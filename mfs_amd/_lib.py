@@ -184,6 +184,14 @@ def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def shape_outputs(outs, squeeze, return_first_nan):
+    """What a public call returns from the arrays its C call wrote, `outs`: None stands for an output the mode does not
+    have, and the last element is always first_nan.  The Nones are left out, the leading replicate axis is dropped if `ys`
+    had none, and first_nan is kept only if asked for."""
+    outs = tuple(o[0] if squeeze else o for o in outs if o is not None)
+    return outs if return_first_nan else outs[:-1]
+
+
 _pinned_live = [0]   # bytes of pinned pool memory currently held by result arrays of this process
 
 

@@ -57,8 +57,9 @@ def _tables_and_tangents(model: Callable, params: np.ndarray, mode: str, rel_ste
         every table entry is an analytic function of theta built from the model's own arithmetic, so Im(entry) / h is its exact
         derivative -- the derivative of the traced polynomials themselves, with no truncation or cancellation error whatever the
         dependence on theta (exp, softplus, products, ...).  The model must not apply non-analytic operations to its
-        parameters (abs, comparisons, casts to float): if the complex trace raises, or disagrees with the stencil below by
-        more than 1e-5, the stencil is used and a warning says so.
+        parameters (abs, comparisons, casts to float).  Two checks guard that: the unperturbed complex trace must be real,
+        and it must equal the plain float64 trace (same shapes, rtol 1e-13); if either fails, or the complex trace raises,
+        the stencil below is used and a warning says so.  The tangents themselves are not compared with the stencil's.
     tangents = 'stencil': five-point central differences on the table builder (`rel_step`), exact for tables polynomial in
         theta up to degree four."""
     from mfs_amd import sym
@@ -142,22 +143,11 @@ def nell_and_grad_forward(model: Callable, params, ms0, mean0, ys, scale0=None, 
         raise ValueError(f'{dcoef.shape[0]} parameter points for {B} measurement rows')
     ms0 = np.ascontiguousarray(ms0, dtype=np.float64)
     N = ms0.shape[-1] // 2
-    m = _lib.MfsModel1d()
-    m.trans_kind = _lib.TRANS[tables.kind]
-    m.umap = _lib.UMAP[tables.umap]
-    m.n_terms = tables.n_terms
-    m.degree = J
-    m.n_rows = coef.shape[-2]
-    m.coef_batched = m.lik_batched = int(batched)
-    m.lik_kind = _lib.LIK[lik.kind]
-    m.n_lik = lp.shape[-1]
-    m.mean_x_coef = tables.mean_x_coef
-    coef_c = np.ascontiguousarray(coef if batched else coef[0])
-    lp_c = np.ascontiguousarray(lp if batched else lp[0])
+    # row 0 of the broadcast arrays when every trajectory shares the parameter point
+    m, keep = filtering.fill_model_struct(tables, lik, J, np.ascontiguousarray(coef if batched else coef[0]),
+                                          np.ascontiguousarray(lp if batched else lp[0]), batched, batched)
     dcoef_c = np.ascontiguousarray(dcoef if batched else dcoef[0])
     dlik_c = np.ascontiguousarray(dlik if batched else dlik[0])
-    m.coef = coef_c.ctypes.data_as(_lib.c_double_p)
-    m.lik = lp_c.ctypes.data_as(_lib.c_double_p)
     mean_a = None if mean0 is None else np.ascontiguousarray(np.atleast_1d(np.asarray(mean0, dtype=np.float64)))
     scale_a = None if scale0 is None else np.ascontiguousarray(np.atleast_1d(np.asarray(scale0, dtype=np.float64)))
     out_nell, out_grad, out_fn = np.empty((B,)), np.empty((B, P)), np.empty((B,), dtype=np.int32)
@@ -165,9 +155,8 @@ def nell_and_grad_forward(model: Callable, params, ms0, mean0, ys, scale0=None, 
                                              _lib.ptr(ms0), int(ms0.ndim == 2), _lib.ptr(mean_a), _lib.ptr(scale_a),
                                              _lib.ptr(ys2), _lib.ptr(out_nell), _lib.ptr(out_grad), _lib.ptr(out_fn), device,
                                              None))
-    if squeeze:
-        out_nell, out_grad, out_fn = out_nell[0], out_grad[0], out_fn[0]
-    return (out_nell, out_grad, out_fn) if return_first_nan else (out_nell, out_grad)
+    del keep
+    return _lib.shape_outputs((out_nell, out_grad, out_fn), squeeze, return_first_nan)
 
 
 def minimise_nell_forward(model: Callable, init_params: Sequence[float], ms0, mean0, ys, scale0=None, mode='central',

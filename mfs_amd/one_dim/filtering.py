@@ -91,31 +91,32 @@ def trace_model(mode, transition_fn, mean_fn, pdf_fn):
     return tables, _trace_likelihood(pdf_fn)
 
 
-def build_model_struct(tables: TransitionTables, lik: sym.LikelihoodSpec, B: int):
-    """Fill `struct mfs_model_1d`; returns (struct, keep-alive arrays)."""
-    coef, J = tables.table(B)
-    coef_batched = int(coef.ndim == 3)
-    lp = np.ascontiguousarray(lik.params, dtype=np.float64)
-    if lp.ndim == 1:
-        lik_batched = 0
-    elif lp.shape[:-1] == (B,):
-        lik_batched = 1
-    else:
-        raise ValueError(f'likelihood parameters are batched with shape {lp.shape[:-1]}, but the filter batch is {B}')
+def fill_model_struct(tables: TransitionTables, lik: sym.LikelihoodSpec, J: int, coef, lp, coef_batched, lik_batched):
+    """Fill `struct mfs_model_1d` from explicit C-contiguous float64 coefficient (.., n_rows, J + 1) and likelihood-parameter
+    (.., n_lik) arrays; returns (struct, keep-alive arrays): the struct points into them until the C call has returned."""
     m = _lib.MfsModel1d()
     m.trans_kind = _lib.TRANS[tables.kind]
     m.umap = _lib.UMAP[tables.umap]
     m.n_terms = tables.n_terms
     m.degree = J
     m.n_rows = coef.shape[-2]
-    m.coef_batched = coef_batched
+    m.coef_batched = int(coef_batched)
     m.lik_kind = _lib.LIK[lik.kind]
     m.n_lik = lp.shape[-1]
-    m.lik_batched = lik_batched
+    m.lik_batched = int(lik_batched)
     m.mean_x_coef = tables.mean_x_coef
     m.coef = coef.ctypes.data_as(_lib.c_double_p)
     m.lik = lp.ctypes.data_as(_lib.c_double_p)
     return m, (coef, lp)
+
+
+def build_model_struct(tables: TransitionTables, lik: sym.LikelihoodSpec, B: int):
+    """Fill `struct mfs_model_1d` from the traced model; returns (struct, keep-alive arrays)."""
+    coef, J = tables.table(B)
+    lp = np.ascontiguousarray(lik.params, dtype=np.float64)
+    if lp.ndim != 1 and lp.shape[:-1] != (B,):
+        raise ValueError(f'likelihood parameters are batched with shape {lp.shape[:-1]}, but the filter batch is {B}')
+    return fill_model_struct(tables, lik, J, coef, lp, coef.ndim == 3, lp.ndim != 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -155,7 +156,8 @@ def _prep_inputs(ms0, mean0, scale0, ys, tables, lik):
     return ys2, squeeze, B, T, ms0, num_moments // 2, batched, aux(mean0), aux(scale0)
 
 
-def _run(mode, tables, lik, ms0, mean0, scale0, ys, stable, device=0, want_first_nan=False):
+def _run(mode, tables, lik, ms0, mean0, scale0, ys, stable, device=0):
+    """-> ((moments, means, scales, nell, first_nan) with the replicate axis, None where `mode` has none; squeeze)."""
     ys2, squeeze, B, T, ms0, N, batched, mean0, scale0 = _prep_inputs(ms0, mean0, scale0, ys, tables, lik)
     if not 2 <= N <= _lib.MAX_N:
         raise ValueError(f'N = {N} outside the supported range [2, {_lib.MAX_N}]')
@@ -174,11 +176,7 @@ def _run(mode, tables, lik, ms0, mean0, scale0, ys, stable, device=0, want_first
                                _lib.ptr(out_m), _lib.ptr(out_mean), _lib.ptr(out_scale), _lib.ptr(out_nell),
                                _lib.ptr(out_fn), device, None))
     del keep
-    if squeeze:
-        out_m, out_nell, out_fn = out_m[0], out_nell[0], out_fn[0]
-        out_mean = None if out_mean is None else out_mean[0]
-        out_scale = None if out_scale is None else out_scale[0]
-    return out_m, out_mean, out_scale, out_nell, out_fn
+    return (out_m, out_mean, out_scale, out_nell, out_fn), squeeze
 
 
 def moment_filter_rms(state_cond_raw_moments: Callable, measurement_cond_pdf: Callable, rms0, ys,
@@ -189,16 +187,14 @@ def moment_filter_rms(state_cond_raw_moments: Callable, measurement_cond_pdf: Ca
     index of the first NaN-poisoned step (-1 if none).
     """
     tables, lik = trace_model('raw', state_cond_raw_moments, None, measurement_cond_pdf)
-    m, _, _, nell, fn = _run('raw', tables, lik, rms0, None, None, ys, stable, device)
-    return (m, nell, fn) if return_first_nan else (m, nell)
+    return _lib.shape_outputs(*_run('raw', tables, lik, rms0, None, None, ys, stable, device), return_first_nan)
 
 
 def moment_filter_cms(state_cond_central_moments: Callable, state_cond_mean: Callable, measurement_cond_pdf: Callable,
                       cms0, mean0, ys, stable: bool = False, *, device: int = 0, return_first_nan: bool = False):
     """Moment filter with central moments (mfs/one_dim/filtering.py:92-161): returns (cmss, means, nell)."""
     tables, lik = trace_model('central', state_cond_central_moments, state_cond_mean, measurement_cond_pdf)
-    m, means, _, nell, fn = _run('central', tables, lik, cms0, mean0, None, ys, stable, device)
-    return (m, means, nell, fn) if return_first_nan else (m, means, nell)
+    return _lib.shape_outputs(*_run('central', tables, lik, cms0, mean0, None, ys, stable, device), return_first_nan)
 
 
 def moment_filter_scms(state_cond_scaled_central_moments: Callable, state_cond_mean_var: Callable,
@@ -206,5 +202,4 @@ def moment_filter_scms(state_cond_scaled_central_moments: Callable, state_cond_m
                        device: int = 0, return_first_nan: bool = False):
     """Moment filter with scaled central moments (mfs/one_dim/filtering.py:164-240): (scmss, means, scales, nell)."""
     tables, lik = trace_model('scaled', state_cond_scaled_central_moments, state_cond_mean_var, measurement_cond_pdf)
-    m, means, scales, nell, fn = _run('scaled', tables, lik, scms0, mean0, scale0, ys, stable, device)
-    return (m, means, scales, nell, fn) if return_first_nan else (m, means, scales, nell)
+    return _lib.shape_outputs(*_run('scaled', tables, lik, scms0, mean0, scale0, ys, stable, device), return_first_nan)
