@@ -440,6 +440,44 @@ int mfs_plan_nd3_create_joint(mfs_plan_nd3** plan, const mfs_model_nd3* model, c
                               int stable, int device);
 
 /*
+ * ---- brute-force grid filter: the true 1-D filtering densities, host pointers ---------------------------------------
+ * Replaces brute_force_filter (mfs/classical_filters_smoothers/brute_force.py:26-136, Chapman--Kolmogorov branches
+ * 'chapman-euler' / 'chapman-tme-k') as the driver runs it (dardel/benes_bernoulli/brute_force.py: 2000 grid points, 100
+ * sub-steps per measurement, chapman-tme-3), for B replicates on one shared grid.  The transition density over one sub-step
+ * is Normal, N(x'; trans_mean(x), trans_sd(x)^2) (tme.mean_and_cov at :74-78, Euler at :70); the caller evaluates the two
+ * on the grid, so no model struct crosses here.  Per measurement: `substeps` applications of
+ *   p(x_i) <- sum_j w_j N(x_i; trans_mean_j, trans_sd_j^2) p(x_j)        (w = the weights of jnp.trapz(., xs), :86)
+ * then p <- lik(y, x) p / z with z = sum_i w_i lik(y, x_i) p(x_i) (:133), out_nell -= log z.
+ *
+ *   n, T, B      grid points (2 .. MFS_GRID_MAX_N), measurements, replicates
+ *   substeps     >= 1, integration_steps of the reference
+ *   use_power    1: form the n x n matrix of `substeps` sub-steps once (binary exponentiation), one product per measurement;
+ *                0: apply the one-sub-step matrix `substeps` times per measurement.  Same result up to rounding: every entry
+ *                is non-negative, so the products are componentwise forward-stable whatever the association
+ *   xs           [n] strictly increasing (uneven spacing allowed);  trans_mean, trans_sd [n], trans_sd finite and > 0
+ *   lik_kind     MFS_LIK_BERNOULLI_LOGISTIC / _POISSON_SOFTPLUS / _GAUSSIAN; lik [n_lik] or [B][n_lik] (lik_batched)
+ *   init_ps      [n] or [B][n] (init_batched): the initial density on the grid;  ys [B][T]
+ *   out_pdfs     [B][T][n] or NULL: with NULL nothing of that size exists on the device either
+ *   out_means, out_vars [B][T]: trapezoid mean and central variance of each posterior (may be NULL)
+ *   out_nell [B];  out_first_nan [B] or NULL: the first step whose normaliser is zero or not finite, -1 if none.  That
+ *                replicate is NaN from that step on, in-band, and only that replicate.
+ * Two calls with the same inputs return the same bits.  MFS_EINVAL: n < 2, T < 1, B < 1, substeps < 1, xs not strictly
+ * increasing, trans_sd not finite or not > 0, lik_kind not one of the three, a NULL required buffer.  MFS_EUNSUPPORTED:
+ * n > MFS_GRID_MAX_N (the power route holds three padded n x n buffers: 1.6 GB at 8192).
+ */
+#define MFS_GRID_MAX_N 8192
+int mfs_grid_filter_1d(int n, int T, int B, int substeps, int use_power,
+                       const double* xs, const double* trans_mean, const double* trans_sd,
+                       int lik_kind, int n_lik, const double* lik, int lik_batched,
+                       const double* init_ps, int init_batched, const double* ys,
+                       double* out_pdfs, double* out_means, double* out_vars,
+                       double* out_nell, int32_t* out_first_nan, int device, void* stream);
+/* diagnostic: the filter's fp64 matrix-core GEMM on its own, C[M][N] = A[M][K] B[K][N], row-major DEVICE pointers, enqueued
+ * on `stream`.  M and N must be multiples of 64 and K of 16 (the filter pads its buffers to that), C distinct from A and B:
+ * MFS_EINVAL otherwise.  The sum over k runs in ascending order in one wave: bit-reproducible. */
+int mfs_grid_gemm_dev(int M, int N, int K, const double* d_A, const double* d_B, double* d_C, void* stream);
+
+/*
  * ---- multi-GPU: one process per GPU, replicates sharded, NLL all-gather over RCCL / xGMI -----------------------
  * The reference has no multi-device code (its Monte-Carlo runs are separate OS processes,
  * dardel/run_benes_bernoulli_mf.sh:26-31); replicates share nothing, so the data path needs no collective and the

@@ -14,6 +14,7 @@ TRANS = {'operator': 0, 'gaussian': 1}
 UMAP = {'x': 0, 'tanh': 1}
 LIK = {'bernoulli_logistic': 0, 'poisson_softplus': 1, 'gaussian': 2, 'bearing_gaussian': 3}
 MAX_N = 32
+GRID_MAX_N = 8192   # MFS_GRID_MAX_N: grid points of the brute-force grid filter
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -143,6 +144,9 @@ _SIGNATURES = [
     ('mfs_plan_nd3_create_joint', _i, [_vpp, C.POINTER(MfsModelNd3), C.POINTER(MfsJointNd3), _i, _i, _i, _i, _i, _vp, _vp, _i,
                                        _i]),
     ('mfs_elementary', _i, [_i, _i, _vp, _vp, _i]),
+    ('mfs_grid_filter_1d', _i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp,
+                                _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ('mfs_grid_gemm_dev', _i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     ('mfs_comm_unique_id', _i, [_vp]),
     ('mfs_comm_init', _i, [_vpp, _vp, _i, _i, _i]),
     ('mfs_allgather_nell', _i, [_vp, _vp, _vp, _u64, _vp]),

@@ -2,6 +2,7 @@
 // hipGraph capture.  No compute lives here; the kernels are in filter1d_kernel.hpp.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1221,4 +1222,115 @@ extern "C" int mfs_characteristic_1d(int N, int count, const double* ms, const d
     }
     st.d2h(out, d_out, (size_t)count * nz * 16);
     return st.finish("mfs_characteristic_1d", MFS_OK);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// brute-force grid filter, host pointers (kernels: gridfilter_kernel.hpp)
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int mfs_grid_gemm_dev(int M, int N, int K, const double* d_A, const double* d_B, double* d_C, void* stream) {
+    if (M <= 0 || N <= 0 || K <= 0 || M % mfs::kGridTile || N % mfs::kGridTile || K % mfs::kGridBK)
+        return fail(MFS_EINVAL, "mfs_grid_gemm_dev: M = %d and N = %d must be positive multiples of %d, K = %d of %d", M, N,
+                    mfs::kGridTile, K, mfs::kGridBK);
+    if (!d_A || !d_B || !d_C || d_C == d_A || d_C == d_B) return fail(MFS_EINVAL, "mfs_grid_gemm_dev: NULL or aliased buffer");
+    HIP_TRY(mfs::launch_grid_gemm(M, N, K, d_A, d_B, d_C, (hipStream_t)stream));
+    return MFS_OK;
+}
+
+extern "C" int mfs_grid_filter_1d(int n, int T, int B, int substeps, int use_power, const double* xs, const double* trans_mean,
+                                  const double* trans_sd, int lik_kind, int n_lik, const double* lik, int lik_batched,
+                                  const double* init_ps, int init_batched, const double* ys, double* out_pdfs,
+                                  double* out_means, double* out_vars, double* out_nell, int32_t* out_first_nan, int device,
+                                  void* stream) {
+    if (n < 2 || T < 1 || B < 1) return fail(MFS_EINVAL, "mfs_grid_filter_1d: n = %d (>= 2), T = %d, B = %d (>= 1)", n, T, B);
+    if (substeps < 1) return fail(MFS_EINVAL, "mfs_grid_filter_1d: substeps = %d < 1", substeps);
+    if (n > MFS_GRID_MAX_N) return fail(MFS_EUNSUPPORTED, "mfs_grid_filter_1d: n = %d grid points > %d", n, MFS_GRID_MAX_N);
+    if (lik_kind < MFS_LIK_BERNOULLI_LOGISTIC || lik_kind > MFS_LIK_GAUSSIAN)
+        return fail(MFS_EINVAL, "mfs_grid_filter_1d: lik_kind %d is not a 1-D likelihood", lik_kind);
+    if (n_lik < 1 || n_lik > MFS_MAX_LIK) return fail(MFS_EINVAL, "mfs_grid_filter_1d: n_lik %d outside [1, %d]", n_lik, MFS_MAX_LIK);
+    if (!xs || !trans_mean || !trans_sd || !lik || !init_ps || !ys || !out_nell)
+        return fail(MFS_EINVAL, "mfs_grid_filter_1d: xs / trans_mean / trans_sd / lik / init_ps / ys / out_nell must not be NULL");
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(xs[i]) || (i > 0 && !(xs[i] > xs[i - 1])))
+            return fail(MFS_EINVAL, "mfs_grid_filter_1d: xs must be finite and strictly increasing (entry %d)", i);
+        if (!std::isfinite(trans_sd[i]) || !(trans_sd[i] > 0.0))
+            return fail(MFS_EINVAL, "mfs_grid_filter_1d: trans_sd[%d] = %g is not finite and > 0", i, trans_sd[i]);
+    }
+    HIP_TRY(hipSetDevice(device));
+    // trapezoid weights of jnp.trapz(., xs): w_0 = (x_1 - x_0) / 2, w_i = (x_{i+1} - x_{i-1}) / 2, w_{n-1} = (x_{n-1} - x_{n-2}) / 2
+    std::vector<double> w((size_t)n);
+    for (int i = 0; i < n; ++i) w[i] = 0.5 * (xs[i + 1 < n ? i + 1 : i] - xs[i > 0 ? i - 1 : i]);
+
+    const int n_pad = mfs::grid_pad(n), ldp = mfs::grid_pad(B);
+    const size_t kk_bytes = (size_t)n_pad * n_pad * 8, p_bytes = (size_t)n_pad * ldp * 8, bt = (size_t)B * T;
+    const size_t nb_lik = lik_batched ? (size_t)B : 1, nb_init = init_batched ? (size_t)B : 1;
+    const bool power = use_power != 0 && substeps > 1;
+    double *d_xs = nullptr, *d_m = nullptr, *d_sd = nullptr, *d_w = nullptr, *d_lik = nullptr, *d_init = nullptr, *d_ys = nullptr;
+    double *d_K[3] = {nullptr, nullptr, nullptr}, *d_P[2] = {nullptr, nullptr};
+    double *d_pdfs = nullptr, *d_means = nullptr, *d_vars = nullptr, *d_nell = nullptr;
+    int32_t* d_fn = nullptr;
+    mfs::Staging st(device, stream, true);
+    st.alloc(&d_xs, (size_t)n * 8); st.alloc(&d_m, (size_t)n * 8); st.alloc(&d_sd, (size_t)n * 8); st.alloc(&d_w, (size_t)n * 8);
+    st.alloc(&d_lik, nb_lik * n_lik * 8);
+    st.alloc(&d_init, nb_init * n * 8);
+    st.alloc(&d_ys, bt * 8);
+    for (int k = 0; k < (power ? 3 : 1); ++k) st.alloc(&d_K[k], kk_bytes);
+    st.alloc(&d_P[0], p_bytes); st.alloc(&d_P[1], p_bytes);
+    if (out_pdfs) st.alloc(&d_pdfs, bt * n * 8);
+    st.alloc(&d_means, bt * 8); st.alloc(&d_vars, bt * 8); st.alloc(&d_nell, (size_t)B * 8); st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_xs, xs, (size_t)n * 8); st.h2d(d_m, trans_mean, (size_t)n * 8); st.h2d(d_sd, trans_sd, (size_t)n * 8);
+    st.h2d(d_w, w.data(), (size_t)n * 8);
+    st.h2d(d_lik, lik, nb_lik * n_lik * 8);
+    st.h2d(d_init, init_ps, nb_init * n * 8);
+    st.h2d(d_ys, ys, bt * 8);
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_nell, 0, (size_t)B * 8, st.s);
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_fn, 0xff, (size_t)B * 4, st.s);   // -1
+    if (st.err == hipSuccess) st.err = mfs::launch_grid_build_k(n, n_pad, d_xs, d_m, d_sd, d_w, d_K[0], st.s);
+    if (st.err == hipSuccess) st.err = mfs::launch_grid_init_p(n, n_pad, B, ldp, d_init, init_batched != 0, d_P[0], st.s);
+
+    // the matrix of one measurement interval: K itself, or K^substeps by binary exponentiation over three buffers (at most
+    // two are held by base and result at any time; launches on one stream are ordered, so a buffer given back is free).
+    const double* d_M = d_K[0];
+    if (power) {
+        double* spare[3] = {d_K[1], d_K[2], nullptr};
+        int nspare = 2;
+        double *base = d_K[0], *res = nullptr;   // base = K^(2^bit); res = the product of the bases of the set bits so far
+        for (int e = substeps; e > 0 && st.err == hipSuccess; e >>= 1) {
+            if (e & 1) {
+                if (!res) {
+                    res = base;            // no copy: the squaring below leaves this buffer alone
+                } else {
+                    double* f = spare[--nspare];
+                    st.err = mfs::launch_grid_gemm(n_pad, n_pad, n_pad, res, base, f, st.s);
+                    spare[nspare++] = res;
+                    res = f;
+                }
+            }
+            if (e > 1 && st.err == hipSuccess) {
+                double* f = spare[--nspare];
+                st.err = mfs::launch_grid_gemm(n_pad, n_pad, n_pad, base, base, f, st.s);
+                if (base != res) spare[nspare++] = base;
+                base = f;
+            }
+        }
+        d_M = res;
+    }
+    mfs::GridUpdateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = n; a.T = T; a.B = B; a.ldp = ldp; a.lik_kind = lik_kind; a.n_lik = n_lik; a.lik_batched = lik_batched != 0;
+    a.xs = d_xs; a.w = d_w; a.lik = d_lik; a.ys = d_ys; a.out_pdfs = d_pdfs; a.out_means = d_means; a.out_vars = d_vars;
+    a.nell = d_nell; a.first_nan = d_fn;
+    const int reps = power ? 1 : substeps;
+    int cur = 0;
+    for (int t = 0; t < T && st.err == hipSuccess; ++t) {
+        for (int r = 0; r < reps && st.err == hipSuccess; ++r) {
+            st.err = mfs::launch_grid_gemm(n_pad, ldp, n_pad, d_M, d_P[cur], d_P[cur ^ 1], st.s);
+            cur ^= 1;
+        }
+        a.t = t; a.P = d_P[cur];
+        if (st.err == hipSuccess) st.err = mfs::launch_grid_update(a, st.s);
+    }
+    st.d2h(out_pdfs, d_pdfs, bt * n * 8);
+    st.d2h(out_means, d_means, bt * 8); st.d2h(out_vars, d_vars, bt * 8);
+    st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
+    return st.finish("mfs_grid_filter_1d", MFS_OK);
 }

@@ -1,6 +1,6 @@
 // registry.hpp -- every launcher type and launcher table of the library, declared once.  The *_inst.hip translation units
 // fill the tables from static registrars; capi.hip reads them.  A null launcher means "not compiled / does not exist".
-// Host-only: the argument structs are only named here (their definitions live with the kernels).
+// Host-only: the argument structs are only named here (their definitions live with the kernels; the grid filter's is the exception).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,5 +87,36 @@ using FilterNd3Launch = hipError_t (*)(const FilterNd3Args&, int grid, hipStream
 using FilterNd3JointLaunch = hipError_t (*)(const FilterNd3Args&, const FilterNd3Joint&, int grid, hipStream_t);
 struct Nd3Entry { FilterNd3Launch launch, launch_gauss; int S, Z, lds_bytes; FilterNd3JointLaunch joint, joint_gauss; };
 extern Nd3Entry g_nd3_table[MFS_ND3_MAX_N + 1];   // defined in filternd3_inst.hip
+
+// ---- brute-force grid filter (gridfilter_inst.hip): one build of each kernel, so plain launchers and no table.  Every
+// matrix is row-major in a buffer padded to multiples of 64 (n_pad, ldp); the GEMM takes padded sizes only and refuses
+// anything else, and C must not alias A or B.  (GridUpdateArgs is defined here, not just named: its kernels are not templates,
+// so their header can be included by gridfilter_inst.hip alone.)
+constexpr int kGridTile = 64;   // the GEMM's block tile in M and N; every padded dimension is a multiple of it
+constexpr int kGridBK = 16;     // ... and its k-slice
+
+inline int grid_pad(const int v) { return (v + kGridTile - 1) / kGridTile * kGridTile; }
+
+struct GridUpdateArgs {
+    int n, T, B, t;          // grid points, steps, replicates, the step this launch updates
+    int ldp;                 // leading dimension of P (the padded B)
+    int lik_kind, n_lik, lik_batched;
+    const double* xs;        // [n]
+    const double* w;         // [n] trapezoid weights
+    const double* lik;       // [n_lik] or [B][n_lik]
+    const double* ys;        // [B][T]
+    double* P;               // [n_pad][ldp]: predicted densities in, posteriors out
+    double* out_pdfs;        // [B][T][n] or null
+    double* out_means;       // [B][T]
+    double* out_vars;        // [B][T]
+    double* nell;            // [B], accumulated over the steps
+    int32_t* first_nan;      // [B], -1 until a step's normaliser is zero or not finite
+};
+hipError_t launch_grid_build_k(int n, int n_pad, const double* d_xs, const double* d_mean, const double* d_sd,
+                               const double* d_w, double* d_K, hipStream_t s);
+hipError_t launch_grid_init_p(int n, int n_pad, int B, int ldp, const double* d_init, int init_batched, double* d_P,
+                              hipStream_t s);
+hipError_t launch_grid_gemm(int M, int N, int Kd, const double* d_A, const double* d_B, double* d_C, hipStream_t s);
+hipError_t launch_grid_update(const GridUpdateArgs& a, hipStream_t s);
 
 }  // namespace mfs
