@@ -478,6 +478,61 @@ int mfs_grid_filter_1d(int n, int T, int B, int substeps, int use_power,
 int mfs_grid_gemm_dev(int M, int N, int K, const double* d_A, const double* d_B, double* d_C, void* stream);
 
 /*
+ * ---- bootstrap particle filter, 1-D, host pointers ------------------------------------------------------------------
+ * Replaces bootstrap_filter (mfs/classical_filters_smoothers/smc.py:26-84) with the resamplers stratified / systematic
+ * (mfs/classical_filters_smoothers/resampling.py:43-59) as the drivers run it (dardel/benes_bernoulli/pf.py: 10 000 particles,
+ * proposal tme.mean_and_cov; dardel/convergence/convergence_pf.py: 100 000), for B replicates at once, and the empirical
+ * characteristic function the driver takes of every step's samples (pf.py:58-75).  The two sampler callables of the reference
+ * become descriptors: the transition is the Normal closure of a mfs_model_1d (MFS_TRANS_GAUSSIAN: mu(x), var(x)), the initial
+ * law a mixture of at most MFS_PF_MAX_MIX Normals, or explicit samples.  Per measurement t (kernels: particle_kernel.hpp):
+ *   x_i <- mu(x_i) + sqrt(var(x_i)) z_i (var <= 0 or not finite: NaN);  w_i = lik(y_t, x_i);  nell -= log(mean_i w_i)   (:66-69)
+ *   cs = inclusive prefix sums of w / sum w;  v_i = (i + u_i) / n (stratified: one u per particle, systematic: one for all);
+ *   idx_i = the first j with cs[j] >= v_i (searchsorted, side left), clamped to [0, n - 1];  x'_i = x[idx_i]              (:76)
+ *   out_means, out_vars: mean and population variance (about that mean) of x';  out_cfs[k] = mean_i exp(i zs[k] x'_i).
+ *
+ * The random stream is part of the interface.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ * 0xBB67AE85 after every round), key = (low, high 32 bits of seeds[b]), counter = (particle i, step t, tag, draw); of the
+ * four output words r0..r3
+ *   uniform  U(a, b) = ((a >> 6) 2^26 + (b >> 6) + 1/2) 2^-52, strictly inside (0, 1);  a draw's uniform is U(r0, r1)
+ *   normal   z = sqrt(-2 ln U(r0, r1)) cos(2 pi U(r2, r3))
+ *   tag 0 (t = 0): the initial draw: draw 0 gives z, draw 1 the component uniform u_c; component c = #{k : mix_cumw[k] <= u_c}
+ *                  clamped to n_mix - 1;  x_i = mix_mean[c] + sqrt(mix_var[c]) z
+ *   tag 1: the propagation normal of step t (draw 0);  tag 2: the resampling uniform of step t (draw 0; systematic: particle 0's)
+ * A draw depends on (seed, i, t, tag, draw) alone, not on the launch geometry or the batch.
+ *
+ *   model        trans_kind MFS_TRANS_GAUSSIAN; coef_batched / lik_batched give one table per replicate (a theta grid)
+ *   n, T, B      particles (1 .. MFS_PF_MAX_PARTICLES), measurements, replicates;  resampling MFS_RESAMPLE_*
+ *   seeds [B];  n_mix 1 .. MFS_PF_MAX_MIX with mix_cumw (cumulative weights), mix_mean, mix_var [n_mix] each, or n_mix = 0 and
+ *   init_samples [n] or [B][n] (init_batched);  ys [B][T];  zs [nz] or NULL with nz = 0
+ *   out_samples  [B][T][n] or NULL: with NULL nothing of that size exists on the device either
+ *   out_means, out_vars [B][T];  out_cfs [B][T][nz][2] = (re, im), i.e. complex128, or NULL;  out_nell [B]
+ *   out_first_nan [B] or NULL: the first step whose sum of weights is zero or not finite, -1 if none.  That replicate is NaN
+ *                from that step on -- samples, summaries, cf and nell -- and only that replicate; no index leaves [0, n - 1].
+ * Every sum runs in an order fixed by n alone (block totals are combined in index order, no atomics): two calls with the same
+ * inputs return the same bits, and replicate b of a batch returns the bits of a B = 1 call with seeds[b].  On a uniformly
+ * spaced zs the cf takes one true sincos per particle and 8 frequencies and rotates by exp(i dz x) in between.
+ * MFS_EINVAL: n, T or B < 1, an unknown resampling code, a model that is not MFS_TRANS_GAUSSIAN, n_mix outside 0 .. 8, n_mix = 0
+ * without init_samples, mixture variances not finite and > 0, nz > 0 with a NULL zs or out_cfs, a NULL required buffer.
+ * MFS_EUNSUPPORTED: n > MFS_PF_MAX_PARTICLES.  MFS_ENOMEM: the work buffers cannot be had.
+ */
+#define MFS_PF_MAX_PARTICLES (1 << 20)
+#define MFS_PF_MAX_MIX 8
+#define MFS_RESAMPLE_STRATIFIED 0
+#define MFS_RESAMPLE_SYSTEMATIC 1
+int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, int B, int resampling, const uint64_t* seeds,
+                           int n_mix, const double* mix_cumw, const double* mix_mean, const double* mix_var,
+                           const double* init_samples, int init_batched, const double* ys, int nz, const double* zs,
+                           double* out_samples, double* out_means, double* out_vars, double* out_cfs, double* out_nell,
+                           int32_t* out_first_nan, int device, void* stream);
+/* diagnostic, like mfs_elementary: the stream's draws (seed, i, t, tag, draw) for particles i = 0 .. count - 1, computed on the
+ * device: out_uniform[i] = U(r0, r1), out_normal[i] = z.  Host pointers, [count] each. */
+int mfs_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* out_uniform, double* out_normal, int device);
+/* diagnostic for the benchmark tool: with MFS_PF_SPLIT=1 in the environment mfs_particle_filter_1d records an event after every
+ * launch and waits once per step; this returns the summed time in ms of the calling thread's last call per kernel, out[5] =
+ * propagate (with the block scan), offsets, resample, cf (with the variance), finalize.  Zeros without the switch. */
+int mfs_pf_last_split_ms(double* out);
+
+/*
  * ---- multi-GPU: one process per GPU, replicates sharded, NLL all-gather over RCCL / xGMI -----------------------
  * The reference has no multi-device code (its Monte-Carlo runs are separate OS processes,
  * dardel/run_benes_bernoulli_mf.sh:26-31); replicates share nothing, so the data path needs no collective and the

@@ -15,6 +15,9 @@ UMAP = {'x': 0, 'tanh': 1}
 LIK = {'bernoulli_logistic': 0, 'poisson_softplus': 1, 'gaussian': 2, 'bearing_gaussian': 3}
 MAX_N = 32
 GRID_MAX_N = 8192   # MFS_GRID_MAX_N: grid points of the brute-force grid filter
+PF_MAX_PARTICLES = 1 << 20   # MFS_PF_MAX_PARTICLES: particles per replicate of the bootstrap particle filter
+PF_MAX_MIX = 8               # MFS_PF_MAX_MIX: components of its initial mixture
+RESAMPLE = {'stratified': 0, 'systematic': 1}   # MFS_RESAMPLE_*
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -147,6 +150,10 @@ _SIGNATURES = [
     ('mfs_grid_filter_1d', _i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     ('mfs_grid_gemm_dev', _i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    ('mfs_particle_filter_1d', _i, [C.POINTER(MfsModel1d), _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ('mfs_pf_draws', _i, [_u64, _i, _i, _i, _i, _vp, _vp, _i]),
+    ('mfs_pf_last_split_ms', _i, [_vp]),
     ('mfs_comm_unique_id', _i, [_vp]),
     ('mfs_comm_init', _i, [_vpp, _vp, _i, _i, _i]),
     ('mfs_allgather_nell', _i, [_vp, _vp, _vp, _u64, _vp]),

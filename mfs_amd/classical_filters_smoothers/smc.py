@@ -1,0 +1,171 @@
+"""The bootstrap particle filter on MI355X, mirroring `mfs.classical_filters_smoothers.smc`.
+
+Same name and positional order as the reference's `bootstrap_filter` (mfs/classical_filters_smoothers/smc.py:26-33).  Its two
+sampler callables draw from JAX keys and cannot be traced, so descriptors stand in their slots: `gaussian_transition(...)` for
+`transition_sampler` (the Normal proposal of the drivers, tme.mean_and_cov or Euler--Maruyama) and a `GaussianSum1D` or an
+array of initial particles for `init_sampler`.  The time loop -- propagation, weights, prefix sums, resampling, the per-step
+mean, variance and empirical characteristic function -- runs in hand-written HIP (mfs_amd/csrc/particle_kernel.hpp) through
+`mfs_particle_filter_1d` of include/mfs_hip.h, on the counter-based random stream that header states.  Extension over the
+reference: `ys` may be (B, T) for B replicates (Monte-Carlo keys, or a parameter grid through (B,)-array model parameters).
+
+There is no CPU fallback: callables that cannot be reduced to a device description raise `NotDeviceDescribable`.
+"""
+import ctypes as C
+from typing import Callable, NamedTuple, Optional
+
+import numpy as np
+
+from mfs_amd import _lib
+from mfs_amd.classical_filters_smoothers.resampling import Resampling, stratified
+from mfs_amd.one_dim.filtering import _trace_likelihood, build_model_struct
+from mfs_amd.one_dim.moments import _trace_sde
+from mfs_amd.tme_poly import TransitionTables, euler_tables, tme_tables
+from mfs_amd.utils import GaussianSum1D
+
+__all__ = ['bootstrap_filter', 'gaussian_transition', 'GaussianTransition', 'ParticleFilterResult']
+
+_LIK_KINDS = ('bernoulli_logistic', 'poisson_softplus', 'gaussian')
+
+
+class GaussianTransition(NamedTuple):
+    """The proposal X' | x ~ N(mu(x), var(x)) as device tables (`tables.cond_mean`, `tables.cond_var` evaluate them)."""
+    tables: TransitionTables
+
+
+class ParticleFilterResult(NamedTuple):
+    """samples (B, T, n) or None: the resampled particles of every step; means, variances (B, T): their unweighted mean and
+    population variance; cfs (B, T, nz) complex or None: mean_i exp(i z_k x_i); nell (B,): minus the sum of log mean_i w_i;
+    first_nan (B,): the first step whose weights summed to zero or to a non-finite value, -1 if none.  Without a replicate
+    axis on `ys` the leading B is dropped."""
+    samples: Optional[np.ndarray]
+    means: np.ndarray
+    variances: np.ndarray
+    cfs: Optional[np.ndarray]
+    nell: np.ndarray
+    first_nan: np.ndarray
+
+
+def gaussian_transition(drift: Callable, dispersion: Callable, dt: float, method: str = 'tme-3') -> GaussianTransition:
+    """The Normal transition proposal of the reference's drivers (dardel/benes_bernoulli/pf.py: `tme.mean_and_cov`), traced
+    like `brute_force_filter` traces its SDE.  method: 'tme-k' (TME of order k, Normal closure) or 'euler'.  Drift / dispersion
+    parameters may be (B,) arrays: one table per replicate."""
+    a, b = _trace_sde(drift, dispersion)
+    if method == 'euler':
+        return GaussianTransition(euler_tables(a, b, float(dt)))
+    if method.startswith('tme-'):
+        try:
+            order = int(method.split('-')[-1])
+        except ValueError:
+            raise ValueError(f"method must be 'tme-k' or 'euler', got {method!r}") from None
+        return GaussianTransition(tme_tables(a, b, float(dt), order, gaussian=True))
+    raise ValueError(f"method must be 'tme-k' or 'euler', got {method!r}")
+
+
+def _seeds(key, B, squeeze):
+    if isinstance(key, (int, np.integer)):
+        if key < 0:
+            raise ValueError(f'key must be a non-negative integer, got {key}')
+        return (np.uint64(int(key)) + np.arange(B, dtype=np.uint64)).astype(np.uint64)
+    key = np.asarray(key)
+    if key.dtype.kind not in 'ui' or (key.dtype.kind == 'i' and np.any(key < 0)):
+        raise ValueError(f'key must be an int or an array of non-negative integers (uint64 seeds), got dtype {key.dtype}')
+    if key.shape != (B,) or squeeze:
+        raise ValueError(f'key must be an int or, with ys of shape ({B}, T), an array of shape ({B},); got shape {key.shape}')
+    return np.ascontiguousarray(key, dtype=np.uint64)
+
+
+def bootstrap_filter(transition, measurement_cond_pdf: Callable, ys, init, key, nsamples: int,
+                     resampling: Resampling = stratified, conti_resampling: bool = False, *, zs=None,
+                     return_samples: bool = True, return_summaries: bool = False, device: int = 0):
+    """Bootstrap particle filter of a 1-D state (mfs/classical_filters_smoothers/smc.py:26-84).
+
+    transition             `gaussian_transition(drift, dispersion, dt, method)`
+    measurement_cond_pdf   (y, x) -> pdf, traced like the moment filters trace it (Bernoulli-logistic, Poisson-softplus,
+                           Gaussian; parameters may be (B,) arrays)
+    ys                     (T,) or (B, T) measurements
+    init                   a `GaussianSum1D` (drawn on the device) or an array (n,) / (B, n) of initial particles
+    key                    an int k: replicate b uses seed k + b; or a (B,) array of uint64 seeds
+    nsamples               particles per replicate, 1 .. 2^20
+    resampling             `stratified` or `systematic` of mfs_amd.classical_filters_smoothers.resampling
+    zs                     (nz,) frequencies: also return the empirical characteristic function of every step
+    return_samples         False: nothing of size B * T * n is allocated, on the host or the device
+    return_summaries       True: return a `ParticleFilterResult`
+
+    Returns (samples (T, n) or (B, T, n), nell), as the reference does, or a `ParticleFilterResult`.  Replicate b depends on
+    its seed alone: it returns the same bits alone and in a batch.  A replicate whose weights sum to zero or to a non-finite
+    value is NaN from that step on (see `first_nan`); the others are unaffected.
+    """
+    if conti_resampling:
+        raise NotImplementedError('conti_resampling=True (continuous resampling, resampling.py:76-110) is not implemented: it '
+                                  'needs a sort of the particles at every step, which the device filter does not have')
+    if not isinstance(resampling, Resampling):
+        raise ValueError('resampling must be `stratified` or `systematic` of mfs_amd.classical_filters_smoothers.resampling '
+                         f'(the device draws from its own stream, not from a callable); got {resampling!r}')
+    if resampling.code is None:
+        raise NotImplementedError(f'{resampling.name} resampling is not implemented on the device (it needs n + 1 sorted '
+                                  'uniforms, a prefix sum over the random stream); use stratified or systematic')
+    if not isinstance(transition, GaussianTransition):
+        raise ValueError('transition must be built by gaussian_transition(drift, dispersion, dt, method): a sampler callable '
+                         f'cannot be traced; got {type(transition).__name__}')
+    if not (return_samples or return_summaries):
+        raise ValueError('nothing to return: return_samples and return_summaries are both False')
+    if zs is not None and not return_summaries:
+        raise ValueError('zs asks for characteristic functions, which only a ParticleFilterResult carries: pass '
+                         'return_summaries=True')
+    n = int(nsamples)
+    if n != nsamples or not 1 <= n <= _lib.PF_MAX_PARTICLES:
+        raise ValueError(f'nsamples must be an integer in [1, {_lib.PF_MAX_PARTICLES}], got {nsamples}')
+    tables = transition.tables
+    lik = _trace_likelihood(measurement_cond_pdf)
+    if lik.kind not in _LIK_KINDS or len(lik.factors) != 1:
+        raise ValueError(f'the particle filter supports the 1-D likelihoods {_LIK_KINDS}, got {lik!r}')
+
+    ys = np.asarray(ys)
+    squeeze = ys.ndim == 1
+    ys2 = np.ascontiguousarray(ys[None, :] if squeeze else ys, dtype=np.float64)
+    if ys2.ndim != 2 or ys2.shape[1] < 1 or ys2.shape[0] < 1:
+        raise ValueError(f'ys must have shape (T,) or (B, T) with T >= 1, got {ys.shape}')
+    B, T = ys2.shape
+    if squeeze and (tables.batch_shape() != () or np.ndim(lik.params) != 1):
+        raise ValueError('per-replicate model parameters need ys of shape (B, T)')
+    seeds = _seeds(key, B, squeeze)
+
+    mix = [None, None, None]
+    init_samples = None
+    if isinstance(init, GaussianSum1D):
+        K = init.means.shape[0]
+        if not 1 <= K <= _lib.PF_MAX_MIX:
+            raise ValueError(f'the initial mixture has {K} components; the device draws from 1 .. {_lib.PF_MAX_MIX}')
+        if not (np.all(np.isfinite(init.variances)) and np.all(init.variances > 0.) and np.all(np.isfinite(init.means))):
+            raise ValueError('the initial mixture needs finite means and finite variances > 0')
+        mix = [np.ascontiguousarray(np.cumsum(init.weights), dtype=np.float64),
+               np.ascontiguousarray(init.means, dtype=np.float64), np.ascontiguousarray(init.variances, dtype=np.float64)]
+    else:
+        init_samples = np.ascontiguousarray(init, dtype=np.float64)
+        if init_samples.shape not in ((n,), (B, n)) or (squeeze and init_samples.ndim == 2):
+            raise ValueError(f'init must be a GaussianSum1D or particles of shape ({n},) or, with ys of shape ({B}, T), '
+                             f'({B}, {n}); got {init_samples.shape}')
+    nz = 0
+    if zs is not None:
+        zs = np.ascontiguousarray(zs, dtype=np.float64)
+        if zs.ndim != 1 or zs.shape[0] < 1 or not np.all(np.isfinite(zs)):
+            raise ValueError(f'zs must be a finite array of shape (nz,) with nz >= 1, got shape {zs.shape}')
+        nz = zs.shape[0]
+    model, keep = build_model_struct(tables, lik, B)
+
+    samples = _lib.pinned_empty((B, T, n), device=device) if return_samples else None
+    means, variances = np.empty((B, T)), np.empty((B, T))
+    cfs = _lib.pinned_empty((B, T, nz), dtype=np.complex128, device=device) if nz else None
+    nell, first_nan = np.empty((B,)), np.empty((B,), dtype=np.int32)
+    _lib.check(_lib.lib().mfs_particle_filter_1d(
+        C.byref(model), n, T, B, resampling.code, _lib.ptr(seeds), 0 if mix[0] is None else mix[0].shape[0],
+        _lib.ptr(mix[0]), _lib.ptr(mix[1]), _lib.ptr(mix[2]), _lib.ptr(init_samples),
+        int(init_samples is not None and init_samples.ndim == 2), _lib.ptr(ys2), nz, _lib.ptr(zs), _lib.ptr(samples),
+        _lib.ptr(means), _lib.ptr(variances), _lib.ptr(cfs), _lib.ptr(nell), _lib.ptr(first_nan), device, None))
+    del keep
+    if not return_summaries:
+        return (samples[0], nell[0]) if squeeze else (samples, nell)
+    outs = [samples, means, variances, cfs, nell, first_nan]
+    if squeeze:
+        outs = [None if o is None else o[0] for o in outs]
+    return ParticleFilterResult(*outs)

@@ -1334,3 +1334,159 @@ extern "C" int mfs_grid_filter_1d(int n, int T, int B, int substeps, int use_pow
     st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
     return st.finish("mfs_grid_filter_1d", MFS_OK);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// bootstrap particle filter, host pointers (kernels: particle_kernel.hpp)
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int mfs_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* out_uniform, double* out_normal,
+                            int device) {
+    if (count < 0 || t < 0 || tag < 0 || draw < 0) return fail(MFS_EINVAL, "mfs_pf_draws: negative count, t, tag or draw");
+    if (count == 0) return MFS_OK;
+    if (!out_uniform || !out_normal) return fail(MFS_EINVAL, "mfs_pf_draws: NULL buffer");
+    HIP_TRY(hipSetDevice(device));
+    double *d_u = nullptr, *d_z = nullptr;
+    mfs::Staging st(device, nullptr, true);
+    st.alloc(&d_u, (size_t)count * 8);
+    st.alloc(&d_z, (size_t)count * 8);
+    if (st.err == hipSuccess) st.err = mfs::launch_pf_draws(seed, t, tag, draw, count, d_u, d_z, st.s);
+    st.d2h(out_uniform, d_u, (size_t)count * 8);
+    st.d2h(out_normal, d_z, (size_t)count * 8);
+    return st.finish("mfs_pf_draws", MFS_OK);
+}
+
+static thread_local double g_pf_split_ms[5];   // propagate, offsets, resample, cf, finalize of this thread's last call
+
+extern "C" int mfs_pf_last_split_ms(double* out) {
+    if (!out) return fail(MFS_EINVAL, "mfs_pf_last_split_ms: NULL buffer");
+    for (int k = 0; k < 5; ++k) out[k] = g_pf_split_ms[k];
+    return MFS_OK;
+}
+
+extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, int B, int resampling, const uint64_t* seeds,
+                                      int n_mix, const double* mix_cumw, const double* mix_mean, const double* mix_var,
+                                      const double* init_samples, int init_batched, const double* ys, int nz, const double* zs,
+                                      double* out_samples, double* out_means, double* out_vars, double* out_cfs,
+                                      double* out_nell, int32_t* out_first_nan, int device, void* stream) {
+    const char* me = "mfs_particle_filter_1d";
+    if (n < 1 || T < 1 || B < 1) return fail(MFS_EINVAL, "%s: n = %d, T = %d, B = %d (all >= 1)", me, n, T, B);
+    if (n > MFS_PF_MAX_PARTICLES) return fail(MFS_EUNSUPPORTED, "%s: n = %d particles > %d", me, n, MFS_PF_MAX_PARTICLES);
+    if (resampling != MFS_RESAMPLE_STRATIFIED && resampling != MFS_RESAMPLE_SYSTEMATIC)
+        return fail(MFS_EINVAL, "%s: unknown resampling code %d", me, resampling);
+    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
+    if (model->trans_kind != MFS_TRANS_GAUSSIAN || model->n_rows != 2)
+        return fail(MFS_EINVAL, "%s: the proposal needs a MFS_TRANS_GAUSSIAN model (trans_kind %d, n_rows %d)", me,
+                    model->trans_kind, model->n_rows);
+    if (model->degree < 0 || model->degree > MFS_MAX_DEGREE) return fail(MFS_EINVAL, "%s: degree %d outside [0, %d]", me, model->degree, MFS_MAX_DEGREE);
+    if (model->umap != MFS_U_IDENTITY && model->umap != MFS_U_TANH) return fail(MFS_EINVAL, "%s: unknown umap %d", me, model->umap);
+    if (model->lik_kind < MFS_LIK_BERNOULLI_LOGISTIC || model->lik_kind > MFS_LIK_GAUSSIAN)
+        return fail(MFS_EINVAL, "%s: lik_kind %d is not a 1-D likelihood", me, model->lik_kind);
+    if (model->n_lik < 1 || model->n_lik > MFS_MAX_LIK) return fail(MFS_EINVAL, "%s: n_lik %d outside [1, %d]", me, model->n_lik, MFS_MAX_LIK);
+    if (n_mix < 0 || n_mix > MFS_PF_MAX_MIX) return fail(MFS_EINVAL, "%s: n_mix = %d outside [0, %d]", me, n_mix, MFS_PF_MAX_MIX);
+    if (n_mix == 0 && !init_samples) return fail(MFS_EINVAL, "%s: n_mix = 0 needs init_samples", me);
+    if (n_mix > 0 && (!mix_cumw || !mix_mean || !mix_var)) return fail(MFS_EINVAL, "%s: mix_cumw / mix_mean / mix_var must not be NULL", me);
+    for (int k = 0; k < n_mix; ++k)
+        if (!std::isfinite(mix_var[k]) || !(mix_var[k] > 0.0) || !std::isfinite(mix_mean[k]))
+            return fail(MFS_EINVAL, "%s: mixture component %d is not finite with variance > 0", me, k);
+    if (nz < 0 || (nz > 0 && (!zs || !out_cfs))) return fail(MFS_EINVAL, "%s: nz = %d needs zs and out_cfs", me, nz);
+    if (!model->coef || !model->lik || !seeds || !ys || !out_means || !out_vars || !out_nell)
+        return fail(MFS_EINVAL, "%s: model tables / seeds / ys / out_means / out_vars / out_nell must not be NULL", me);
+    HIP_TRY(hipSetDevice(device));
+
+    // a uniformly spaced frequency grid lets the cf kernel rotate between true sincos evaluations
+    int z_uniform = 0;
+    double dz = 0.0;
+    if (nz > 1) {
+        dz = (zs[nz - 1] - zs[0]) / (double)(nz - 1);
+        double zmax = 0.0, dev = 0.0;
+        for (int k = 0; k < nz; ++k) {
+            zmax = std::fmax(zmax, std::fabs(zs[k]));
+            dev = std::fmax(dev, std::fabs(zs[k] - (zs[0] + (double)k * dz)));
+        }
+        z_uniform = std::isfinite(dz) && dev <= 8.0 * 2.220446049250313e-16 * zmax;
+    }
+
+    const int nblk = mfs::pf_blocks(n), nseg = mfs::pf_segments(n), J1 = model->degree + 1;
+    const size_t bn = (size_t)B * n, bt = (size_t)B * T;
+    const size_t nb_coef = model->coef_batched ? (size_t)B : 1, nb_lik = model->lik_batched ? (size_t)B : 1;
+    const size_t nb_init = init_batched ? (size_t)B : 1;
+    double *d_coef = nullptr, *d_lik = nullptr, *d_ys = nullptr, *d_mix = nullptr, *d_init = nullptr, *d_zs = nullptr;
+    uint64_t* d_seeds = nullptr;
+    double *d_x = nullptr, *d_x2 = nullptr, *d_wscan = nullptr, *d_wpart = nullptr, *d_woffs = nullptr, *d_wtot = nullptr;
+    double *d_xpart = nullptr, *d_vpart = nullptr, *d_cfpart = nullptr;
+    double *d_samples = nullptr, *d_means = nullptr, *d_vars = nullptr, *d_cfs = nullptr, *d_nell = nullptr;
+    int32_t* d_fn = nullptr;
+    mfs::Staging st(device, stream, true);
+    st.alloc(&d_coef, nb_coef * 2 * J1 * 8); st.alloc(&d_lik, nb_lik * model->n_lik * 8); st.alloc(&d_ys, bt * 8);
+    st.alloc(&d_seeds, (size_t)B * 8);
+    if (n_mix > 0) st.alloc(&d_mix, (size_t)3 * n_mix * 8); else st.alloc(&d_init, nb_init * n * 8);
+    if (nz > 0) st.alloc(&d_zs, (size_t)nz * 8);
+    st.alloc(&d_x, bn * 8); st.alloc(&d_x2, bn * 8); st.alloc(&d_wscan, bn * 8);
+    st.alloc(&d_wpart, (size_t)B * nblk * 8); st.alloc(&d_woffs, (size_t)B * nblk * 8); st.alloc(&d_wtot, (size_t)B * 8);
+    st.alloc(&d_xpart, (size_t)B * nblk * 8); st.alloc(&d_vpart, (size_t)B * nseg * 8);
+    if (nz > 0) st.alloc(&d_cfpart, (size_t)B * nseg * nz * 16);
+    if (out_samples) st.alloc(&d_samples, bt * n * 8);
+    st.alloc(&d_means, bt * 8); st.alloc(&d_vars, bt * 8);
+    if (nz > 0) st.alloc(&d_cfs, bt * nz * 16);
+    st.alloc(&d_nell, (size_t)B * 8); st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_coef, model->coef, nb_coef * 2 * J1 * 8); st.h2d(d_lik, model->lik, nb_lik * model->n_lik * 8);
+    st.h2d(d_ys, ys, bt * 8); st.h2d(d_seeds, seeds, (size_t)B * 8);
+    if (n_mix > 0) {
+        st.h2d(d_mix, mix_cumw, (size_t)n_mix * 8); st.h2d(d_mix + n_mix, mix_mean, (size_t)n_mix * 8);
+        st.h2d(d_mix + 2 * n_mix, mix_var, (size_t)n_mix * 8);
+    } else {
+        st.h2d(d_init, init_samples, nb_init * n * 8);
+    }
+    if (nz > 0) st.h2d(d_zs, zs, (size_t)nz * 8);
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_nell, 0, (size_t)B * 8, st.s);
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_fn, 0xff, (size_t)B * 4, st.s);   // -1
+
+    mfs::PfArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = n; a.T = T; a.B = B; a.nblk = nblk; a.nseg = nseg; a.resampling = resampling;
+    a.umap = model->umap; a.degree = model->degree; a.coef_batched = model->coef_batched != 0; a.lik_kind = model->lik_kind;
+    a.n_lik = model->n_lik; a.lik_batched = model->lik_batched != 0; a.mean_x_coef = model->mean_x_coef;
+    a.coef = d_coef; a.lik = d_lik; a.ys = d_ys; a.seeds = d_seeds;
+    a.n_mix = n_mix; a.init_batched = init_batched != 0;
+    if (n_mix > 0) { a.mix_cumw = d_mix; a.mix_mean = d_mix + n_mix; a.mix_var = d_mix + 2 * n_mix; }
+    a.init = d_init; a.nz = nz; a.z_uniform = z_uniform; a.dz = dz; a.zs = d_zs;
+    a.x = d_x; a.x2 = d_x2; a.wscan = d_wscan; a.wpart = d_wpart; a.woffs = d_woffs; a.wtot = d_wtot; a.xpart = d_xpart;
+    a.vpart = d_vpart; a.cfpart = d_cfpart; a.out_samples = d_samples; a.out_means = d_means; a.out_vars = d_vars;
+    a.out_cfs = d_cfs; a.nell = d_nell; a.first_nan = d_fn;
+    if (st.err == hipSuccess) st.err = mfs::launch_pf_init(a, st.s);
+    // MFS_PF_SPLIT=1 (the benchmark tool): an event after every launch and a wait per step, so that mfs_pf_last_split_ms can
+    // report the time of each of the five kernels; the results are the same bits, the call is slower by the waits
+    const char* split_env = getenv("MFS_PF_SPLIT");
+    const bool split = split_env && split_env[0] == '1';
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 6 && split && st.err == hipSuccess; ++k) st.err = hipEventCreate(&ev[k]);
+    for (int k = 0; k < 5; ++k) g_pf_split_ms[k] = 0.0;
+    auto mark = [&](int k) { if (split && st.err == hipSuccess) st.err = hipEventRecord(ev[k], st.s); };
+    for (int t = 0; t < T && st.err == hipSuccess; ++t) {
+        a.t = t;
+        mark(0);
+        st.err = mfs::launch_pf_propagate(a, st.s);
+        mark(1);
+        if (st.err == hipSuccess) st.err = mfs::launch_pf_offsets(a, st.s);
+        mark(2);
+        if (st.err == hipSuccess) st.err = mfs::launch_pf_resample(a, st.s);
+        mark(3);
+        if (st.err == hipSuccess) st.err = mfs::launch_pf_cf(a, st.s);
+        mark(4);
+        if (st.err == hipSuccess) st.err = mfs::launch_pf_finalize(a, st.s);
+        mark(5);
+        if (split && st.err == hipSuccess) st.err = hipEventSynchronize(ev[5]);
+        for (int k = 0; k < 5 && split && st.err == hipSuccess; ++k) {
+            float ms = 0.f;
+            st.err = hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            g_pf_split_ms[k] += (double)ms;
+        }
+        std::swap(a.x, a.x2);   // the resampled particles are the next step's
+    }
+    for (int k = 0; k < 6; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    st.d2h(out_samples, d_samples, bt * n * 8);
+    st.d2h(out_means, d_means, bt * 8); st.d2h(out_vars, d_vars, bt * 8);
+    st.d2h(out_cfs, d_cfs, bt * nz * 16);
+    st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
+    return st.finish(me, MFS_OK);
+}

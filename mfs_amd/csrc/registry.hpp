@@ -1,6 +1,7 @@
 // registry.hpp -- every launcher type and launcher table of the library, declared once.  The *_inst.hip translation units
 // fill the tables from static registrars; capi.hip reads them.  A null launcher means "not compiled / does not exist".
-// Host-only: the argument structs are only named here (their definitions live with the kernels; the grid filter's is the exception).
+// Host-only: the argument structs are only named here (their definitions live with the kernels; the grid filter's and the
+// particle filter's are the exceptions).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -118,5 +119,59 @@ hipError_t launch_grid_init_p(int n, int n_pad, int B, int ldp, const double* d_
                               hipStream_t s);
 hipError_t launch_grid_gemm(int M, int N, int Kd, const double* d_A, const double* d_B, double* d_C, hipStream_t s);
 hipError_t launch_grid_update(const GridUpdateArgs& a, hipStream_t s);
+
+// ---- bootstrap particle filter (particle_inst.hip): plain launchers, like the grid filter's.  One measurement is five launches
+// on one stream -- propagate (with the block scan of the weights), offsets, resample, cf (with the variance), finalize -- and
+// every sum's order is fixed by n and these constants alone.
+constexpr int kPfThreads = 256;                    // threads per block of every particle kernel
+constexpr int kPfItems = 4;                        // particles per thread
+constexpr int kPfChunk = kPfThreads * kPfItems;    // particles per block: the unit of the weight scan and of the x' partial sums
+constexpr int kPfSeg = 4 * kPfChunk;               // particles per block of the cf / variance pass
+constexpr int kPfMaxF = 8;                         // frequencies per thread of the cf pass (its rotation recurrence restarts there)
+
+inline int pf_blocks(const int n) { return (n + kPfChunk - 1) / kPfChunk; }
+inline int pf_segments(const int n) { return (n + kPfSeg - 1) / kPfSeg; }
+
+struct PfArgs {
+    int n, T, B, t;          // particles, steps, replicates, the step this launch works on
+    int nblk, nseg;          // pf_blocks(n), pf_segments(n)
+    int resampling;          // MFS_RESAMPLE_*
+    int umap, degree, coef_batched, lik_kind, n_lik, lik_batched;
+    double mean_x_coef;
+    const double* coef;      // [2][degree + 1] or [B][2][degree + 1]: P_m, P_v of MFS_TRANS_GAUSSIAN
+    const double* lik;       // [n_lik] or [B][n_lik]
+    const double* ys;        // [B][T]
+    const uint64_t* seeds;   // [B]
+    int n_mix, init_batched; // initial law: a mixture of n_mix Normals drawn on the device, or (n_mix = 0) given samples
+    const double* mix_cumw;  // [n_mix] each
+    const double* mix_mean;
+    const double* mix_var;
+    const double* init;      // [n] or [B][n]
+    int nz, z_uniform;       // frequencies of the cf; 1: zs is uniformly spaced with step dz
+    double dz;
+    const double* zs;        // [nz]
+    double* x;               // [B][n] the particles: propagated in place, read by the resampler
+    double* x2;              // [B][n] the resampled particles (the host swaps x and x2 after every step)
+    double* wscan;           // [B][n] block-local inclusive prefix sums of the weights
+    double* wpart;           // [B][nblk] block totals of the weights
+    double* woffs;           // [B][nblk] their exclusive prefix sums in index order
+    double* wtot;            // [B] sum of the weights
+    double* xpart;           // [B][nblk] block totals of the resampled particles
+    double* vpart;           // [B][nseg] segment totals of (x' - mean)^2
+    double* cfpart;          // [B][nseg][nz][2] segment totals of exp(i z x'), or null
+    double* out_samples;     // [B][T][n] or null
+    double* out_means;       // [B][T]
+    double* out_vars;        // [B][T]
+    double* out_cfs;         // [B][T][nz][2] or null
+    double* nell;            // [B], accumulated over the steps
+    int32_t* first_nan;      // [B], -1 until a step's weight sum is zero or not finite
+};
+hipError_t launch_pf_init(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf_propagate(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf_offsets(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf_resample(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf_cf(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf_finalize(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* d_uniform, double* d_normal, hipStream_t s);
 
 }  // namespace mfs

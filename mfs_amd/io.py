@@ -34,3 +34,14 @@ def save_batch(directory, mode, N, arrays, normal=False, first_k=0):
 def load_filter_result(filename, mode):
     data = np.load(filename)
     return tuple(data[k] for k in _KEYS[mode])
+
+
+def save_pf_result(filename, means, cfs):
+    """One particle-filter run in the layout dardel/benes_bernoulli/pf.py:74-75 writes: the filtering means (T,) and the
+    empirical characteristic functions (T, nz) of its samples."""
+    np.savez_compressed(filename, pf_filtering_means=np.asarray(means), pf_filtering_cfs=np.asarray(cfs))
+
+
+def load_pf_result(filename):
+    data = np.load(filename)
+    return data['pf_filtering_means'], data['pf_filtering_cfs']
