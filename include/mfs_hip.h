@@ -533,6 +533,52 @@ int mfs_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* out
 int mfs_pf_last_split_ms(double* out);
 
 /*
+ * ---- Gaussian filters: Gauss--Hermite / cubature sigma-point filter and extended Kalman filter, host pointers ----------
+ * Replaces sgp_filter and ekf (mfs/classical_filters_smoothers/gfs.py:503-551, 317-362) as the drivers run them
+ * (dardel/benes_bernoulli, dardel/parameter_estimation/ghf_ekf.py, dardel/prey_predator/ghf_ekf.py), for B replicates at once
+ * and a scalar measurement (dy = 1).  The two callables of the reference become descriptors: state_cond_m_cov is the Normal
+ * closure of the model (MFS_TRANS_GAUSSIAN: mu(x), var(x); MFS_ND_TRANS_GAUSSIAN: mu(x), S(x)), measurement_cond_m_cov the mean
+ * h(x) and variance Xi(x) of the likelihood kind: Bernoulli-logistic (p, p (1 - p)), Poisson-softplus (rate, rate), Gaussian
+ * (l0 x + l1, l2).  The whole time loop is one launch (kernels: gaussfilter_kernel.hpp).  Per measurement y_t:
+ *
+ *   MFS_GF_SIGMA_POINT, with points xi_i and weights w_i (SigmaPoints of the reference; any rule of 1 .. MFS_GF_MAX_POINTS points):
+ *     chi_i = m + L xi_i, L the lower Cholesky factor of P;  mp = sum w_i mu(chi_i);
+ *     Pp = sum w_i (mu mu^T + S(chi_i)) - mp mp^T;  chi_i = mp + Lp xi_i redrawn from (mp, Pp);
+ *     pred = sum w h;  S = sum w (h^2 + Xi) - pred^2;  C = sum w chi h - mp pred;  K = C / S
+ *   MFS_GF_EKF (xi, w, n_points ignored), with analytic Jacobians F = d mu / d x at m and H = d h / d x at mp:
+ *     mp = mu(m);  Pp = F P F^T + S(m);  pred = h(mp);  S = H Pp H^T + Xi(mp);  K = Pp H^T / S
+ *   both:  m = mp + K (y - pred);  P = Pp - K K^T S;  nell += ((y - pred)^2 / S + log(2 pi S)) / 2
+ *
+ *   model        1-D: trans_kind MFS_TRANS_GAUSSIAN; coef_batched / lik_batched give one table per replicate (a theta grid).
+ *                d = 2: d = 2, trans_kind MFS_ND_TRANS_GAUSSIAN, one likelihood factor on one state component, ny = 1;
+ *                lik_batched allowed, coef_batched not
+ *   xi, w        [n_points] ([n_points][2] for d = 2), [n_points];  T, B measurements, replicates
+ *   m0, v0       [1] or [B] (init_batched);  d = 2: m0 [2], P0 [2][2] or [B][2], [B][2][2] (the lower triangle of P0 is read)
+ *   ys           [B][T]
+ *   out_means    [B][T] ([B][T][2]);  out_vars [B][T] (out_covs [B][T][2][2]);  either may be NULL
+ *   out_nells    [B][T]: the running sum, as the reference's scan returns it
+ *   out_first_nan [B] or NULL.  The reference's Cholesky of a matrix that is not positive definite is NaN: a replicate whose
+ *                Cholesky pivot is negative or not finite (zero is legal), or whose S is not finite and > 0, is NaN in every
+ *                output from that step on, and that step is its first_nan (-1 if none).  Only that replicate.  The EKF takes
+ *                no Cholesky, so only the rule on S applies to it.
+ * A group of L lanes owns a replicate, L the smallest power of two >= n_points, at most 64 (one lane for the EKF); the sums are
+ * butterfly reductions in an order fixed by n_points alone and there are no atomics: two calls with the same inputs return the
+ * same bits, and replicate b of a batch returns the bits of a B = 1 call.
+ * MFS_EINVAL: a model outside the Gaussian family, an unknown method, T or B < 1, a NULL required buffer, an unknown u-map or
+ * likelihood kind.  MFS_EUNSUPPORTED: n_points outside 1 .. MFS_GF_MAX_POINTS (sigma-point method), d != 2, more than one
+ * likelihood factor, a factor of both components, ny != 1, coef_batched at d = 2.
+ */
+#define MFS_GF_SIGMA_POINT 0
+#define MFS_GF_EKF 1
+#define MFS_GF_MAX_POINTS 256
+int mfs_gaussian_filter_1d(const mfs_model_1d* model, int method, int n_points, const double* xi, const double* w, int T, int B,
+                           const double* m0, const double* v0, int init_batched, const double* ys, double* out_means,
+                           double* out_vars, double* out_nells, int32_t* out_first_nan, int device, void* stream);
+int mfs_gaussian_filter_nd(const mfs_model_nd* model, int method, int n_points, const double* xi, const double* w, int T, int B,
+                           const double* m0, const double* P0, int init_batched, const double* ys, double* out_means,
+                           double* out_covs, double* out_nells, int32_t* out_first_nan, int device, void* stream);
+
+/*
  * ---- multi-GPU: one process per GPU, replicates sharded, NLL all-gather over RCCL / xGMI -----------------------
  * The reference has no multi-device code (its Monte-Carlo runs are separate OS processes,
  * dardel/run_benes_bernoulli_mf.sh:26-31); replicates share nothing, so the data path needs no collective and the

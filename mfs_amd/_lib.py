@@ -18,6 +18,8 @@ GRID_MAX_N = 8192   # MFS_GRID_MAX_N: grid points of the brute-force grid filter
 PF_MAX_PARTICLES = 1 << 20   # MFS_PF_MAX_PARTICLES: particles per replicate of the bootstrap particle filter
 PF_MAX_MIX = 8               # MFS_PF_MAX_MIX: components of its initial mixture
 RESAMPLE = {'stratified': 0, 'systematic': 1}   # MFS_RESAMPLE_*
+GF_METHOD = {'sigma_point': 0, 'ekf': 1}     # MFS_GF_*: the Gaussian filters
+GF_MAX_POINTS = 256                          # MFS_GF_MAX_POINTS: sigma points of a rule
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -154,6 +156,10 @@ _SIGNATURES = [
                                     _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     ('mfs_pf_draws', _i, [_u64, _i, _i, _i, _i, _vp, _vp, _i]),
     ('mfs_pf_last_split_ms', _i, [_vp]),
+    ('mfs_gaussian_filter_1d', _i, [C.POINTER(MfsModel1d), _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _i, _vp]),
+    ('mfs_gaussian_filter_nd', _i, [C.POINTER(MfsModelNd), _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _i, _vp]),
     ('mfs_comm_unique_id', _i, [_vp]),
     ('mfs_comm_init', _i, [_vpp, _vp, _i, _i, _i]),
     ('mfs_allgather_nell', _i, [_vp, _vp, _vp, _u64, _vp]),

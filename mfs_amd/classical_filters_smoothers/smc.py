@@ -28,8 +28,11 @@ _LIK_KINDS = ('bernoulli_logistic', 'poisson_softplus', 'gaussian')
 
 
 class GaussianTransition(NamedTuple):
-    """The proposal X' | x ~ N(mu(x), var(x)) as device tables (`tables.cond_mean`, `tables.cond_var` evaluate them)."""
+    """The proposal X' | x ~ N(mu(x), var(x)) as device tables (`tables.cond_mean`, `tables.cond_var` evaluate them); `dt` is
+    the step the tables were built for (None if they were not built by `gaussian_transition`), which the Gaussian filters check
+    against their own `dt` argument."""
     tables: TransitionTables
+    dt: Optional[float] = None
 
 
 class ParticleFilterResult(NamedTuple):
@@ -51,13 +54,13 @@ def gaussian_transition(drift: Callable, dispersion: Callable, dt: float, method
     parameters may be (B,) arrays: one table per replicate."""
     a, b = _trace_sde(drift, dispersion)
     if method == 'euler':
-        return GaussianTransition(euler_tables(a, b, float(dt)))
+        return GaussianTransition(euler_tables(a, b, float(dt)), float(dt))
     if method.startswith('tme-'):
         try:
             order = int(method.split('-')[-1])
         except ValueError:
             raise ValueError(f"method must be 'tme-k' or 'euler', got {method!r}") from None
-        return GaussianTransition(tme_tables(a, b, float(dt), order, gaussian=True))
+        return GaussianTransition(tme_tables(a, b, float(dt), order, gaussian=True), float(dt))
     raise ValueError(f"method must be 'tme-k' or 'euler', got {method!r}")
 
 

@@ -1490,3 +1490,106 @@ extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, i
     st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
     return st.finish(me, MFS_OK);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Gaussian filters: sigma-point filter and EKF, host pointers (kernels: gaussfilter_kernel.hpp)
+// ---------------------------------------------------------------------------------------------------------------
+// what the two entry points share once `a` describes the model: the rule, the staging, the launch and the copies back
+static int run_gauss_filter(const char* me, mfs::GfArgs& a, const double* coef, size_t coef_doubles, const double* lik,
+                            size_t lik_doubles, const double* xi, const double* w, const double* m0, const double* P0,
+                            const double* ys, double* out_means, double* out_covs, double* out_nells, int32_t* out_first_nan,
+                            int device, void* stream) {
+    const int d = a.d, T = a.T, B = a.B;
+    if (a.method != MFS_GF_SIGMA_POINT && a.method != MFS_GF_EKF) return fail(MFS_EINVAL, "%s: unknown method %d", me, a.method);
+    if (T < 1 || B < 1) return fail(MFS_EINVAL, "%s: T = %d, B = %d (both >= 1)", me, T, B);
+    if (a.method == MFS_GF_SIGMA_POINT) {
+        if (a.n_points < 1 || a.n_points > MFS_GF_MAX_POINTS)
+            return fail(MFS_EUNSUPPORTED, "%s: n_points = %d outside [1, %d]", me, a.n_points, MFS_GF_MAX_POINTS);
+        if (!xi || !w) return fail(MFS_EINVAL, "%s: the sigma-point method needs xi and w", me);
+        a.lanes = mfs::gf_lanes(a.n_points);
+    } else {
+        a.n_points = 0;
+        a.lanes = 1;
+    }
+    if (!coef || !lik || !m0 || !P0 || !ys || !out_nells)
+        return fail(MFS_EINVAL, "%s: model tables / m0 / v0 / ys / out_nells must not be NULL", me);
+    HIP_TRY(hipSetDevice(device));
+    const size_t bt = (size_t)B * T, nb_init = a.init_batched ? (size_t)B : 1, np = (size_t)a.n_points;
+    double *d_coef = nullptr, *d_lik = nullptr, *d_xi = nullptr, *d_w = nullptr, *d_m0 = nullptr, *d_P0 = nullptr, *d_ys = nullptr;
+    double *d_means = nullptr, *d_covs = nullptr, *d_nells = nullptr;
+    int32_t* d_fn = nullptr;
+    mfs::Staging st(device, stream, true);
+    st.alloc(&d_coef, coef_doubles * 8); st.alloc(&d_lik, lik_doubles * 8);
+    if (np) { st.alloc(&d_xi, np * d * 8); st.alloc(&d_w, np * 8); }
+    st.alloc(&d_m0, nb_init * d * 8); st.alloc(&d_P0, nb_init * d * d * 8); st.alloc(&d_ys, bt * 8);
+    if (out_means) st.alloc(&d_means, bt * d * 8);
+    if (out_covs) st.alloc(&d_covs, bt * d * d * 8);
+    st.alloc(&d_nells, bt * 8);
+    if (out_first_nan) st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_coef, coef, coef_doubles * 8); st.h2d(d_lik, lik, lik_doubles * 8);
+    if (np) { st.h2d(d_xi, xi, np * d * 8); st.h2d(d_w, w, np * 8); }
+    st.h2d(d_m0, m0, nb_init * d * 8); st.h2d(d_P0, P0, nb_init * d * d * 8); st.h2d(d_ys, ys, bt * 8);
+    a.coef = d_coef; a.lik = d_lik; a.xi = d_xi; a.w = d_w; a.m0 = d_m0; a.P0 = d_P0; a.ys = d_ys;
+    a.out_means = d_means; a.out_covs = d_covs; a.out_nells = d_nells; a.out_first_nan = d_fn;
+    if (st.err == hipSuccess) st.err = mfs::launch_gauss_filter(a, st.s);
+    st.d2h(out_means, d_means, bt * d * 8); st.d2h(out_covs, d_covs, bt * d * d * 8);
+    st.d2h(out_nells, d_nells, bt * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
+    return st.finish(me, MFS_OK);
+}
+
+extern "C" int mfs_gaussian_filter_1d(const mfs_model_1d* model, int method, int n_points, const double* xi, const double* w,
+                                      int T, int B, const double* m0, const double* v0, int init_batched, const double* ys,
+                                      double* out_means, double* out_vars, double* out_nells, int32_t* out_first_nan,
+                                      int device, void* stream) {
+    const char* me = "mfs_gaussian_filter_1d";
+    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
+    if (model->trans_kind != MFS_TRANS_GAUSSIAN || model->n_rows != 2)
+        return fail(MFS_EINVAL, "%s: the filter needs a MFS_TRANS_GAUSSIAN model (trans_kind %d, n_rows %d)", me,
+                    model->trans_kind, model->n_rows);
+    if (model->degree < 0 || model->degree > MFS_MAX_DEGREE) return fail(MFS_EINVAL, "%s: degree %d outside [0, %d]", me, model->degree, MFS_MAX_DEGREE);
+    if (model->umap != MFS_U_IDENTITY && model->umap != MFS_U_TANH) return fail(MFS_EINVAL, "%s: unknown umap %d", me, model->umap);
+    if (model->lik_kind < MFS_LIK_BERNOULLI_LOGISTIC || model->lik_kind > MFS_LIK_GAUSSIAN)
+        return fail(MFS_EINVAL, "%s: lik_kind %d is not a 1-D likelihood", me, model->lik_kind);
+    if (model->n_lik < 1 || model->n_lik > MFS_MAX_LIK) return fail(MFS_EINVAL, "%s: n_lik %d outside [1, %d]", me, model->n_lik, MFS_MAX_LIK);
+    mfs::GfArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = 1; a.method = method; a.n_points = n_points; a.T = T; a.B = B; a.init_batched = init_batched != 0;
+    a.umap = model->umap; a.degree = model->degree; a.coef_batched = model->coef_batched != 0; a.lik_kind = model->lik_kind;
+    a.n_lik = model->n_lik; a.lik_batched = model->lik_batched != 0; a.mean_x_coef = model->mean_x_coef;
+    const size_t nb = (B > 0) ? (size_t)B : 0;
+    return run_gauss_filter(me, a, model->coef, (a.coef_batched ? nb : 1) * 2 * (model->degree + 1), model->lik,
+                            (a.lik_batched ? nb : 1) * model->n_lik, xi, w, m0, v0, ys, out_means, out_vars, out_nells,
+                            out_first_nan, device, stream);
+}
+
+extern "C" int mfs_gaussian_filter_nd(const mfs_model_nd* model, int method, int n_points, const double* xi, const double* w,
+                                      int T, int B, const double* m0, const double* P0, int init_batched, const double* ys,
+                                      double* out_means, double* out_covs, double* out_nells, int32_t* out_first_nan,
+                                      int device, void* stream) {
+    const char* me = "mfs_gaussian_filter_nd";
+    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
+    if (model->d != 2) return fail(MFS_EUNSUPPORTED, "%s: d = %d (the filter runs d = 2; d = 1 goes through mfs_gaussian_filter_1d)", me, model->d);
+    if (model->trans_kind != MFS_ND_TRANS_GAUSSIAN)
+        return fail(MFS_EINVAL, "%s: the filter needs a MFS_ND_TRANS_GAUSSIAN model (trans_kind %d)", me, model->trans_kind);
+    if (model->n_factors != 1 || model->ny != 1 || model->fac_ycol[0] != 0)
+        return fail(MFS_EUNSUPPORTED, "%s: one likelihood factor of a scalar measurement is supported (n_factors %d, ny %d)", me,
+                    model->n_factors, model->ny);
+    if (model->fac_kind[0] == MFS_LIK_BEARING_GAUSSIAN || model->fac_component[0] == 2)
+        return fail(MFS_EUNSUPPORTED, "%s: a likelihood factor of both state components is not supported", me);
+    if (model->fac_kind[0] < MFS_LIK_BERNOULLI_LOGISTIC || model->fac_kind[0] > MFS_LIK_GAUSSIAN)
+        return fail(MFS_EINVAL, "%s: unknown likelihood kind %d", me, model->fac_kind[0]);
+    if (model->fac_component[0] < 0 || model->fac_component[0] > 1) return fail(MFS_EINVAL, "%s: fac_component %d outside [0, 1]", me, model->fac_component[0]);
+    if (model->extent < 1 || model->extent > MFS_ND_MAX_EXTENT_HI)
+        return fail(MFS_EINVAL, "%s: extent %d outside [1, %d]", me, model->extent, MFS_ND_MAX_EXTENT_HI);
+    if (model->coef_batched) return fail(MFS_EUNSUPPORTED, "%s: per-replicate transition tables (coef_batched) are not supported at d = 2", me);
+    mfs::GfArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = 2; a.method = method; a.n_points = n_points; a.T = T; a.B = B; a.init_batched = init_batched != 0;
+    a.extent = model->extent; a.component = model->fac_component[0]; a.lik_kind = model->fac_kind[0]; a.n_lik = MFS_MAX_LIK;
+    a.lik_batched = model->lik_batched != 0;
+    const size_t nb = (B > 0) ? (size_t)B : 0;
+    // blocks 0..4 of the table (mu_0, mu_1, S_00, S_01, S_11) are all the filter reads
+    return run_gauss_filter(me, a, model->coef, (size_t)5 * model->extent * model->extent, model->lik,
+                            (a.lik_batched ? nb : 1) * MFS_MAX_LIK, xi, w, m0, P0, ys, out_means, out_covs, out_nells,
+                            out_first_nan, device, stream);
+}

@@ -1,7 +1,7 @@
 // registry.hpp -- every launcher type and launcher table of the library, declared once.  The *_inst.hip translation units
 // fill the tables from static registrars; capi.hip reads them.  A null launcher means "not compiled / does not exist".
-// Host-only: the argument structs are only named here (their definitions live with the kernels; the grid filter's and the
-// particle filter's are the exceptions).
+// Host-only: the argument structs are only named here (their definitions live with the kernels; the grid filter's, the
+// particle filter's and the Gaussian filters' are the exceptions).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -173,5 +173,44 @@ hipError_t launch_pf_resample(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_cf(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_finalize(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* d_uniform, double* d_normal, hipStream_t s);
+
+// ---- Gaussian filters (gaussfilter_inst.hip): the Gauss--Hermite / cubature sigma-point filter and the extended Kalman filter,
+// d = 1 and d = 2, the whole time loop in one launch.  A group of gf_lanes(n_points) lanes owns a replicate (one lane for the
+// EKF); a block is one wavefront, so it holds kGfThreads / lanes replicates.
+constexpr int kGfThreads = 64;
+
+// lanes per replicate of the sigma-point filter: the smallest power of two >= n_points, at most a wavefront.  It depends on
+// n_points alone, never on B, so a replicate's sums run in the same order whatever the batch.
+inline int gf_lanes(const int n_points) {
+    int L = 1;
+    while (L < n_points && L < kGfThreads) L <<= 1;
+    return L;
+}
+
+struct GfArgs {
+    int d, method;           // 1 or 2; MFS_GF_*
+    int n_points, lanes;     // sigma points (0 for the EKF) and lanes per replicate (1 for the EKF)
+    int T, B;
+    // d = 1 (mfs_model_1d, MFS_TRANS_GAUSSIAN): coef [2][degree + 1] or [B][2][degree + 1]; lik [n_lik] or [B][n_lik]
+    int umap, degree, coef_batched, lik_kind, n_lik, lik_batched;
+    double mean_x_coef;
+    // d = 2 (mfs_model_nd, MFS_ND_TRANS_GAUSSIAN): coef [rows][extent][extent], blocks 0..4 = mu_0, mu_1, S_00, S_01, S_11; one
+    // likelihood factor of kind lik_kind on state component `component`, lik [MFS_MAX_LIK] or [B][MFS_MAX_LIK]
+    int extent, component;
+    const double* coef;
+    const double* lik;
+    const double* xi;        // [n_points][d]
+    const double* w;         // [n_points]
+    const double* m0;        // [d] or [B][d]
+    const double* P0;        // [d][d] or [B][d][d]
+    int init_batched;
+    const double* ys;        // [B][T]
+    double* out_means;       // [B][T][d] or null
+    double* out_covs;        // [B][T][d][d] or null
+    double* out_nells;       // [B][T], the running sum
+    int32_t* out_first_nan;  // [B] or null
+};
+int gf_lds_bytes(const GfArgs& a);   // dynamic LDS of one block
+hipError_t launch_gauss_filter(const GfArgs& a, hipStream_t s);
 
 }  // namespace mfs
