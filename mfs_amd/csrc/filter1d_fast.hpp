@@ -529,15 +529,102 @@ __device__ __forceinline__ double twisted_weight(const double (&a)[N], const dou
     return zz * rcp_sat(sm);
 }
 
+// One Laguerre evaluation of quadrature_fast, as a macro so that every caller compiles the same statements in the same order
+// and a caller that only loops over it keeps its device code to the instruction (a lambda taking the state by reference does
+// not: its captures keep the state in memory through the early passes, and the schedule that comes out differs).  It works on
+// the caller's a, b2, k, x, lo, hi, conv, prev_step, tol and wacc:
+//   * p, p' and h = p''/2 by the three-term recurrence (h_n = t h_{n-1} - b^2 h_{n-2} - p'_{n-1}).
+//   * Sturm count = number of sign changes along p_0..p_N.  The sign bits are shifted into one word as the recurrence runs
+//     (one v_alignbit per step; floating-point compares would bounce through SGPR masks next to the chain) and the changes are
+//     counted at the end.  p_0 = 1 > 0 is the zero bit above the first one.
+//   * The step logic is straight-line and predicated (bitwise, not short-circuit, logic: no divergent branches); a converged
+//     lane is frozen by the selects at the end.
+//   * S = sqrt((N-1) ((N-1) p'^2 - N p p'')) >= 0 for real-rooted p (clamped against rounding).  The step only has to be
+//     accurate enough to converge: seeds + one Newton step instead of full-precision sqrt / divide; the accuracy of the root
+//     comes from the recurrence evaluation.
+//   * Laguerre converges cubically near its root: e_next ~ e^3 / gap^2 with gap >~ W / N, so a step below 1e-6 W lands within
+//     ~N^2 1e-18 W of the root and the confirming evaluation can be skipped -- but only with evidence of that regime: a small
+//     step also occurs right after leaving the neighbourhood of a DIFFERENT root (steps then grow by ~N/(N-2) per iteration).
+//     Hence: small AND at least 100x smaller than the previous Laguerre step of this lane ...
+//   * ... or with the bound that needs no history (`near`): p'/p = sum_i 1/(x - lambda_i), so when the Newton step -p/p' points
+//     the way we travel, the roots ahead dominate that sum and the nearest of them lies within N |p/p'| of x.  If that is below
+//     3e-7 W, the Laguerre step lands within ~(3e-7)^3 (N/W)^2 W of it.  (This is what accepts, after ONE evaluation, the
+//     predict-half rule started from the reweighted update-half rule -- see the kernel.)
+//   * EXT: a step below the tolerance is convergence only when the root it approaches lies AHEAD.  After a completed or dense
+//     rule the eigenvalues come back in another order, and a lane can start ON a root that is not its own (the atoms of a
+//     posterior survive a step to the last bit): travelling away from that root Laguerre's first steps are as small as the
+//     distance to it -- or zero -- and would be mistaken for convergence (two lanes on one eigenvalue, a rule of weight 1.5).
+//     Such a lane is pushed off by a few tolerances instead; the count then says on which side its root lies.
+#ifdef MFS_1D_STAMPS
+#define F1_COUNT_EVAL do { if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[10] += 1; } while (0)
+#else
+#define F1_COUNT_EVAL do {} while (0)
+#endif
+#define MFS_LAGUERRE_EVAL                                                                                             \
+                F1_COUNT_EVAL;                                                                                        \
+                double p0 = 1.0, p1 = a[0] - x, d0 = 0.0, d1 = -1.0, e0 = 0.0, e1 = 0.0;                              \
+                unsigned signs = (unsigned)__double2hiint(p1) >> 31;                                                  \
+                static_for<1, N>([&](auto Jc) {                                                                       \
+                    constexpr int j = Jc;                                                                             \
+                    const double t = a[j] - x;                                                                        \
+                    const double pn = fma(t, p1, -b2[j - 1] * p0);                                                    \
+                    const double dn = fma(t, d1, fma(-b2[j - 1], d0, -p1));                                           \
+                    const double en = fma(t, e1, fma(-b2[j - 1], e0, -d1));                                           \
+                    signs = __builtin_amdgcn_alignbit(signs, (unsigned)__double2hiint(pn), 31);                       \
+                    p0 = p1; p1 = pn; d0 = d1; d1 = dn; e0 = e1; e1 = en;                                             \
+                });                                                                                                   \
+                const int cnt = __popc(signs ^ (signs >> 1));                                                         \
+                {                                                                                                     \
+                    const bool below = cnt <= k;                                                                      \
+                    const double lo_n = below ? x : lo, hi_n = below ? hi : x;                                        \
+                    const double mid = 0.5 * (lo_n + hi_n);                                                           \
+                    const double disc = fmax((double)(N - 1) * fma((double)(N - 1) * d1, d1, -(double)(2 * N) * p1 * e1), 0.0);\
+                    double rs = __builtin_amdgcn_rsq(disc);                                                           \
+                    rs = fma(rs, fma(-0.5 * disc * rs, rs, 0.5), rs);                                                 \
+                    const double S = copysign(disc > 0.0 ? disc * rs : 0.0, p1);                                      \
+                    const bool right = (cnt == k), left = (cnt == k + 1);                                             \
+                    const double den = right ? (d1 - S) : (d1 + S);                                                   \
+                    double rd = __builtin_amdgcn_rcp(den);                                                            \
+                    rd = fma(fma(-den, rd, 1.0), rd, rd);                                                             \
+                    double xn = x - (double)N * p1 * rd;                                                              \
+                    const bool ok = (right & (xn >= x) & (xn < hi_n)) | (left & (xn <= x) & (xn > lo_n));             \
+                    xn = ok ? xn : mid;                                                                               \
+                    const double step = fabs(xn - x);                                                                 \
+                    const double nwt = -p1 * d1;                                                                      \
+                    const bool ahead = right ? (nwt > 0.0) : (nwt < 0.0);                                             \
+                    const bool near = ok & ahead & ((double)N * fabs(p1) <= (3e-7 * wacc) * fabs(d1));                \
+                    bool conv_n;                                                                                      \
+                    if constexpr (EXT) {                                                                              \
+                        const bool leaving = ok & !ahead & (step <= tol) & !((p1 == 0.0) & right);                    \
+                        const double push = right ? x + 4.0 * tol : x - 4.0 * tol;                                    \
+                        xn = leaving ? (((push > lo_n) & (push < hi_n)) ? push : mid) : xn;                           \
+                        conv_n = (ok & !leaving & (step <= tol)) | (ok & (step <= kLagStop * wacc) & (step <= 1e-2 * prev_step)) |\
+                                 near | (hi_n - lo_n <= tol) | ((p1 == 0.0) & right);                                 \
+                    } else {                                                                                          \
+                        conv_n = (ok & (step <= tol)) | (ok & (step <= kLagStop * wacc) & (step <= 1e-2 * prev_step)) |\
+                                 near | (hi_n - lo_n <= tol) | ((p1 == 0.0) & (right | left));                        \
+                    }                                                                                                 \
+                    lo = conv ? lo : lo_n;                                                                            \
+                    hi = conv ? hi : hi_n;                                                                            \
+                    prev_step = conv ? prev_step : (ok ? step : 0.0);                                                 \
+                    x = conv ? x : xn;                                                                                \
+                    conv = conv | conv_n;                                                                             \
+                }                                                                                                     \
+                do {} while (0)
+
 // Gauss quadrature from the 2N moments in LDS.  Lane l < N returns node x and weight w; other lanes get w = 0.
 // Returns the group-uniform poison flag (a Cholesky pivot was not > 0, as LAPACK potrf / XLA report).
-template <int N, int G, bool EXT = false>
+// SL = what a specialised one-wave build of the filter kernel asks for in its update half (kSl* below; 0 = the code every
+// other caller gets).
+constexpr int kSlEigLoop = 1;   // first Laguerre evaluation straight-line, then a loop with a wave-uniform exit
+template <int N, int G, bool EXT = false, int SL = 0>
 __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, const int l, const int grp,
                                                 const double mean, const double scale, double& x_out, double& w_out,
                                                 double& lam_io, const bool recentre = false, const bool atoms = false,
                                                 const double w_atom = 0.0, double* __restrict__ S = nullptr,
                                                 const int stable = 0, int* dense_rules = nullptr) {
     static_assert(N + 1 <= G, "needs one lane per row of the extended Hankel matrix");
+    static_assert(SL == 0 || !EXT, "straight-line variants: plain rule only");
     F1_STAMP_BEGIN;
     // -- row l of the extended Hankel matrix: g[j] = m[l + j], l = 0..N (quadtures.py:124-125)
     const int li = (l <= N) ? l : N;
@@ -786,83 +873,21 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
             if (lam_io > lo && lam_io < hi) x = lam_io;
             bool conv = false;
             double prev_step = 0.0;
-            for (int it = 0; it < kMaxEigIters; ++it) {
-    #ifdef MFS_1D_STAMPS
-                if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[10] += 1;
-    #endif
-                // p, p' and h = p''/2 by the three-term recurrence (h_n = t h_{n-1} - b^2 h_{n-2} - p'_{n-1})
-                double p0 = 1.0, p1 = a[0] - x, d0 = 0.0, d1 = -1.0, e0 = 0.0, e1 = 0.0;
-                // Sturm count = number of sign changes along p_0..p_N.  The sign bits are shifted into one word as the
-                // recurrence runs (one v_alignbit per step; floating-point compares would bounce through SGPR masks next
-                // to the chain) and the changes are counted at the end.  p_0 = 1 > 0 is the zero bit above the first one.
-                unsigned signs = (unsigned)__double2hiint(p1) >> 31;
-                static_for<1, N>([&](auto Jc) {
-                    constexpr int j = Jc;
-                    const double t = a[j] - x;
-                    const double pn = fma(t, p1, -b2[j - 1] * p0);
-                    const double dn = fma(t, d1, fma(-b2[j - 1], d0, -p1));
-                    const double en = fma(t, e1, fma(-b2[j - 1], e0, -d1));
-                    signs = __builtin_amdgcn_alignbit(signs, (unsigned)__double2hiint(pn), 31);
-                    p0 = p1; p1 = pn; d0 = d1; d1 = dn; e0 = e1; e1 = en;
-                });
-                const int cnt = __popc(signs ^ (signs >> 1));
-                {   // straight-line and predicated (bitwise, not short-circuit, logic: no divergent branches in the loop);
-                    // a converged lane is frozen by the selects at the end
-                    const bool below = cnt <= k;
-                    const double lo_n = below ? x : lo, hi_n = below ? hi : x;
-                    const double mid = 0.5 * (lo_n + hi_n);
-                    // S = sqrt((N-1) ((N-1) p'^2 - N p p'')) >= 0 for real-rooted p (clamped against rounding)
-                    // (the step only has to be accurate enough to converge: seeds + one Newton step instead of
-                    //  full-precision sqrt / divide; the accuracy of the root comes from the recurrence evaluation)
-                    const double disc = fmax((double)(N - 1) * fma((double)(N - 1) * d1, d1, -(double)(2 * N) * p1 * e1), 0.0);
-                    double rs = __builtin_amdgcn_rsq(disc);
-                    rs = fma(rs, fma(-0.5 * disc * rs, rs, 0.5), rs);
-                    const double S = copysign(disc > 0.0 ? disc * rs : 0.0, p1);
-                    const bool right = (cnt == k), left = (cnt == k + 1);
-                    const double den = right ? (d1 - S) : (d1 + S);
-                    double rd = __builtin_amdgcn_rcp(den);
-                    rd = fma(fma(-den, rd, 1.0), rd, rd);
-                    double xn = x - (double)N * p1 * rd;
-                    const bool ok = (right & (xn >= x) & (xn < hi_n)) | (left & (xn <= x) & (xn > lo_n));  // false for NaN
-                    xn = ok ? xn : mid;
-                    // Laguerre converges cubically near its root: e_next ~ e^3 / gap^2 with gap >~ W / N, so a step below
-                    // 1e-6 W lands within ~N^2 1e-18 W of the root and the confirming evaluation can be skipped -- but only
-                    // with evidence of that regime: a small step also occurs right after leaving the neighbourhood of a
-                    // DIFFERENT root (steps then grow by ~N/(N-2) per iteration).  Hence: small AND at least 100x smaller
-                    // than the previous Laguerre step of this lane ...
-                    const double step = fabs(xn - x);
-                    // ... or with the bound that needs no history: p'/p = sum_i 1/(x - lambda_i), so when the Newton step
-                    // -p/p' points the way we travel, the roots ahead dominate that sum and the nearest of them lies within
-                    // N |p/p'| of x.  If that is below 3e-7 W, the Laguerre step lands within ~(3e-7)^3 (N/W)^2 W of it.
-                    // (This is what accepts, after ONE evaluation, the predict-half rule started from the reweighted
-                    //  update-half rule -- see the kernel.)
-                    const double nwt = -p1 * d1;   // sign of the Newton step -p/p'
-                    const bool ahead = right ? (nwt > 0.0) : (nwt < 0.0);
-                    const bool near = ok & ahead & ((double)N * fabs(p1) <= (3e-7 * wacc) * fabs(d1));
-                    bool conv_n;
-                    if constexpr (EXT) {
-                        // A step below the tolerance is convergence only when the root it approaches lies AHEAD.  After a
-                        // completed or dense rule the eigenvalues come back in another order, and a lane can start ON a
-                        // root that is not its own (the atoms of a posterior survive a step to the last bit): travelling
-                        // away from that root Laguerre's first steps are as small as the distance to it -- or zero -- and
-                        // would be mistaken for convergence (two lanes on one eigenvalue, a rule of weight 1.5).  Such a
-                        // lane is pushed off by a few tolerances instead; the count then says on which side its root lies.
-                        const bool leaving = ok & !ahead & (step <= tol) & !((p1 == 0.0) & right);
-                        const double push = right ? x + 4.0 * tol : x - 4.0 * tol;
-                        xn = leaving ? (((push > lo_n) & (push < hi_n)) ? push : mid) : xn;
-                        conv_n = (ok & !leaving & (step <= tol)) | (ok & (step <= kLagStop * wacc) & (step <= 1e-2 * prev_step)) |
-                                 near | (hi_n - lo_n <= tol) | ((p1 == 0.0) & right);
-                    } else {
-                        conv_n = (ok & (step <= tol)) | (ok & (step <= kLagStop * wacc) & (step <= 1e-2 * prev_step)) |
-                                 near | (hi_n - lo_n <= tol) | ((p1 == 0.0) & (right | left));
-                    }
-                    lo = conv ? lo : lo_n;
-                    hi = conv ? hi : hi_n;
-                    prev_step = conv ? prev_step : (ok ? step : 0.0);
-                    x = conv ? x : xn;
-                    conv = conv | conv_n;
+            if constexpr ((SL & kSlEigLoop) != 0) {
+                // The first evaluation straight-line: conv == false and prev_step == 0 are visible to the compiler here, so
+                // its freeze selects fold away.  Then a loop whose exit is wave-uniform -- one ballot and a scalar branch,
+                // no EXEC-masked loop: a pass costs the wave the same with one group in it as with four, so a group that
+                // has converged rides along with conv == true and every select keeps its x, lo, hi and prev_step.
+                MFS_LAGUERRE_EVAL;
+                for (int it = 1; it < kMaxEigIters; ++it) {
+                    if (__builtin_amdgcn_ballot_w64(!conv) == 0ull) break;
+                    MFS_LAGUERRE_EVAL;
                 }
+            } else {
+            for (int it = 0; it < kMaxEigIters; ++it) {
+                MFS_LAGUERRE_EVAL;
                 if (gall<G>(conv, grp)) break;
+            }
             }
             lam = x;
             lam_io = x;
@@ -885,6 +910,9 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
     w_out = poisoned ? qnan : ((l < N) ? w : 0.0);
     return poisoned;
 }
+
+#undef MFS_LAGUERRE_EVAL
+#undef F1_COUNT_EVAL
 
 // ---------------------------------------------------------------------------------------------------------------
 // the filter kernel (fast path)
@@ -910,6 +938,9 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
 //  MFS_SPEC_AB_TABLE 0 = the table in registers, 1 = the LDS Horner pass; MFS_SPEC_AB_HALVES 0 = two straight-line halves,
 //  1 = the run-time loop over the halves.  DESIGN.md section 6.  The dead rows need no switch: with the number of terms a
 //  compile-time constant the compiler drops their loads and multiply-adds on either table route.)
+// A specialised build also (iii) takes the divergent break out of the update half's eigenvalue iteration:
+//  MFS_SPEC_AB_EIGLOOP 0 = the first Laguerre evaluation straight-line and the rest in a loop whose exit is wave-uniform
+//  (quadrature_fast, kSlEigLoop), 1 = the loop every group leaves on its own.  DESIGN.md sections 3.1 and 6.
 // TR = the step traits of a specialised build: the model switches the time loop would otherwise test at every step -- moment
 // mode, u-map, likelihood law -- as compile-time constants (StepTraits<MODE, UMAP, LIK>; the default StepTraits<> leaves all
 // three run-time values of Filter1dArgs and compiles to the code without the parameter).  A fixed-traits build (i) emits one
@@ -927,6 +958,9 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
 #endif
 #ifndef MFS_SPEC_AB_HALVES
 #define MFS_SPEC_AB_HALVES 0
+#endif
+#ifndef MFS_SPEC_AB_EIGLOOP
+#define MFS_SPEC_AB_EIGLOOP 0
 #endif
 #ifndef MFS_TRAITS_AB_SWITCHES
 #define MFS_TRAITS_AB_SWITCHES 0
@@ -1013,6 +1047,8 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
     const int trans_kind = (SPEC > 0) ? MFS_TRANS_OPERATOR : (SPEC < 0) ? MFS_TRANS_GAUSSIAN : a.trans_kind;
     const int n_terms = (SPEC > 0) ? SPEC : a.n_terms;
     constexpr bool kRegTable = (SPEC != 0) && (MFS_SPEC_AB_TABLE == 0);
+    constexpr bool kHalves = (SPEC != 0) && (MFS_SPEC_AB_HALVES == 0);
+    constexpr int kSlUpdate = (kHalves && (MFS_SPEC_AB_EIGLOOP == 0)) ? kSlEigLoop : 0;
     // live rows: the operator terms + the variance row (LDS row MFS_MAX_TERMS), or mean and variance
     constexpr int SR = (SPEC > 0) ? SPEC + 1 : 2;
     constexpr int kVarReg = (SPEC > 0) ? SPEC : -1;     // the register row that holds LDS row MFS_MAX_TERMS
@@ -1101,11 +1137,17 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                 // predict half: the rule of the posterior moments is the posterior's own atoms (see quadrature_fast); the
                 // reference's recomputation stays available as an A/B switch
                 const bool atoms = (half == 0) && (bool)atoms_ok;
+                if constexpr (kSlUpdate != 0) {
+                    // (a specialised build passes its halves as compile-time constants: the update half asks for kSlUpdate)
+                    constexpr int kSl = std::is_same_v<std::decay_t<decltype(half)>, std::integral_constant<int, 1>> ? kSlUpdate : 0;
+                    quadrature_fast<N, G, EXT, kSl>(mom, l, grp, mean, scale, x, w, lam_io, half == 1, atoms, gW, S, a.stable);
+                } else {
 #ifdef MFS_EXT_DEBUG
                 quadrature_fast<N, G, EXT>(mom, l, grp, mean, scale, x, w, lam_io, half == 1, atoms, gW, S, a.stable, dbg_dense);
 #else
                 quadrature_fast<N, G, EXT>(mom, l, grp, mean, scale, x, w, lam_io, half == 1, atoms, gW, S, a.stable);
 #endif
+                }
                 if (half == 0) gB = lam_io;
 #ifdef MFS_1D_STAMPS
                 if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[11 + half] += g_1d_stamps[10] - it_before;
@@ -1242,7 +1284,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                 if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[9] += 1;
 #endif
             };
-            if constexpr (SPEC != 0 && MFS_SPEC_AB_HALVES == 0) {
+            if constexpr (kHalves) {
                 if (have_atoms & (a.recompute_rule == 0)) half_step(std::integral_constant<int, 0>{}, std::true_type{});
                 else half_step(std::integral_constant<int, 0>{}, std::false_type{});   // the first step of a run; MFS_PREDICT_RULE=recompute
                 half_step(std::integral_constant<int, 1>{}, std::false_type{});
