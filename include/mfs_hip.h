@@ -201,6 +201,16 @@ int mfs_plan_1d_kernel_build(const mfs_plan_1d* plan, int* build);
 #define MFS_TRAITS_CENTRAL_TANH_BERNOULLI 1      /* operator table of 6 terms (TME-3) or normal closure */
 #define MFS_TRAITS_CENTRAL_IDENTITY_GAUSSIAN 2   /* normal closure */
 int mfs_plan_1d_kernel_traits(const mfs_plan_1d* plan, int* traits);
+/* 1: the plan runs the partner-wave variant of its fixed-traits build (N = 14, 15): 512-thread workgroups in which four main
+ * waves run the step's critical path and four partner waves, one beside each on its SIMD, form the posterior moments, decide
+ * the poisoning and accumulate the likelihood.  Bit for bit the one-wave build's outputs (MFS_FAST_PARTNER=0, read at plan
+ * creation, keeps that one; a run under MFS_PREDICT_RULE=recompute takes it as well).  mfs_plan_1d_kernel_build and
+ * mfs_plan_1d_kernel_traits report what they report for the one-wave build; mfs_plan_1d_geometry reports the variant's. */
+int mfs_plan_1d_kernel_partner(const mfs_plan_1d* plan, int* partner);
+/* placement record of the partner-wave variant, over the launches of this process on the current device: the workgroups
+ * whose prologue compared the SIMDs of its waves, and those among them in which a main wave and its partner did not share one.
+ * Sums over every order that has the variant.  A profile record: nothing but speed depends on the placement. */
+int mfs_partner_placement(uint64_t* workgroups, uint64_t* mismatches);
 
 /*
  * ---- negative log-likelihood and its gradient, forward mode inside the time loop ------------------------------------

@@ -130,6 +130,8 @@ _SIGNATURES = [
                                   C.POINTER(C.c_int)]),
     ('mfs_plan_1d_kernel_build', _i, [_vp, C.POINTER(C.c_int)]),
     ('mfs_plan_1d_kernel_traits', _i, [_vp, C.POINTER(C.c_int)]),
+    ('mfs_plan_1d_kernel_partner', _i, [_vp, C.POINTER(C.c_int)]),
+    ('mfs_partner_placement', _i, [C.POINTER(_u64), C.POINTER(_u64)]),
     ('mfs_quadrature_1d', _i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     ('mfs_characteristic_1d', _i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     ('mfs_filter_nd', _i, [C.POINTER(MfsModelNd), _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i,

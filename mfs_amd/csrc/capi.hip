@@ -112,6 +112,10 @@ struct mfs_plan_1d {
     // (bytes per block for the dense path, doubles per filter for the fast one) and its MFS_BUILD_* code
     mfs::Filter1dLaunch launch = nullptr;
     int launch_lds = 0, build = MFS_BUILD_DENSE, traits = MFS_TRAITS_RUNTIME;
+    // partner-wave variant (filter1d_partner.hpp): `launch` and `grid` are the variant's, and the one-wave build it stands in for
+    // stays at hand for the runs it does not cover (MFS_PREDICT_RULE=recompute, read at every run)
+    int partner = 0, one_wave_grid = 0;
+    mfs::Filter1dFastLaunch one_wave_launch = nullptr;
     double* d_coef = nullptr;
     double* d_lik = nullptr;
     double* c_mom = nullptr;
@@ -218,7 +222,9 @@ int mfs_plan_1d_destroy(mfs_plan_1d* p) {
 // one, else the generic one where the order has one; otherwise the two-wave build.  MFS_FAST_BUILD=generic skips the
 // specialised builds (A/B switch, like MFS_PREDICT_RULE).  A specialised build exists a second time with the model's step
 // switches compiled in (StepTraits) for a few (table shape, mode, u-map, law) combinations: the plan takes it where its model
-// is one of them, MFS_FAST_TRAITS=runtime keeps the run-time-traits build.
+// is one of them, MFS_FAST_TRAITS=runtime keeps the run-time-traits build.  Where a fixed-traits build has a partner-wave variant
+// (N = 14, 15: 512-thread workgroups of four main and four partner waves) the plan takes that, under the same batch condition
+// -- one workgroup per compute unit is one main wave per SIMD; MFS_FAST_PARTNER=0 keeps the one-wave build.
 static void resolve_launch(mfs_plan_1d* p, int slot, bool ext) {
     if (slot < 3) {
         p->launch = mfs::g_table[p->N][slot].filter; p->launch_lds = p->lds_bytes; p->build = MFS_BUILD_DENSE;
@@ -238,6 +244,16 @@ static void resolve_launch(mfs_plan_1d* p, int slot, bool ext) {
         if (spec && ti != MFS_TRAITS_RUNTIME && !(et && strcmp(et, "runtime") == 0) && fe.spec_traits[shape][ti - 1]) {
             spec = fe.spec_traits[shape][ti - 1];
             p->traits = ti;
+            const char* ep = getenv("MFS_FAST_PARTNER");
+            const int lds = mfs::partner_lds_bytes(p->lds_doubles, fe.partner_doubles);
+            if (fe.partner[shape][ti - 1] && !(ep && strcmp(ep, "0") == 0) && lds <= mfs::kPartnerLdsMax) {
+                p->partner = 1;
+                p->one_wave_launch = spec; p->one_wave_grid = p->grid;
+                spec = fe.partner[shape][ti - 1];
+                p->fpb = mfs::kPartnerFilters;
+                p->grid = (p->B + p->fpb - 1) / p->fpb;
+                p->lds_bytes = lds;
+            }
         }
     }
     p->launch = spec ? spec : wide ? wide : ext ? fe.ext : fe.filter;
@@ -319,6 +335,33 @@ int mfs_plan_1d_kernel_build(const mfs_plan_1d* p, int* build) {
     return MFS_OK;
 }
 
+int mfs_plan_1d_kernel_partner(const mfs_plan_1d* p, int* partner) {
+    if (!p || !partner) return fail(MFS_EINVAL, "plan or partner is NULL");
+    *partner = p->partner;
+    return MFS_OK;
+}
+
+int mfs_partner_placement(uint64_t* workgroups, uint64_t* mismatches) {
+    if (!workgroups || !mismatches) return fail(MFS_EINVAL, "workgroups or mismatches is NULL");
+    uint64_t sum[2] = {0, 0};
+    for (int N = 0; N <= MFS_MAX_N; ++N)          // every translation unit with partner kernels holds its own counters
+        for (int gi = 0; gi < 4; ++gi)
+            if (mfs::PartnerPlacementRead read = mfs::g_fast[N][gi].partner_placement) {
+                unsigned long long c[2] = {0, 0};
+                HIP_TRY(read(c));
+                sum[0] += c[0]; sum[1] += c[1];
+            }
+    *workgroups = sum[0]; *mismatches = sum[1];
+    return MFS_OK;
+}
+
+// one launch of the plan's kernel build.  The partner-wave variant has no recomputed predict-half rule: such a run takes the
+// one-wave build the variant stands in for.
+static hipError_t plan_launch(const mfs_plan_1d* p, const mfs::Filter1dArgs& a, hipStream_t s) {
+    if (p->partner && a.recompute_rule) return p->one_wave_launch(a, p->one_wave_grid, p->launch_lds, s);
+    return p->launch(a, p->grid, p->launch_lds, s);
+}
+
 int mfs_plan_1d_kernel_traits(const mfs_plan_1d* p, int* traits) {
     if (!p || !traits) return fail(MFS_EINVAL, "plan or traits is NULL");
     *traits = p->traits;
@@ -331,7 +374,7 @@ static int enqueue_chunks(mfs_plan_1d* p, const mfs::Filter1dArgs& base, hipStre
     do {  // (an empty measurement sequence still takes its one launch: nell = 0, nothing else to write)
         a.t_begin = t0;
         a.t_end = (t0 + p->chunk < p->T) ? t0 + p->chunk : p->T;
-        hipError_t e = p->launch(a, p->grid, p->launch_lds, s);
+        hipError_t e = plan_launch(p, a, s);
         if (e != hipSuccess) return fail(MFS_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     } while ((t0 += p->chunk) < p->T);
     return MFS_OK;
@@ -456,7 +499,7 @@ int mfs_filter_1d(const mfs_model_1d* model, int mode, int N, int T, int B, cons
     mfs::Filter1dArgs a = plan_args(p, d_m0, m0_batched, d_mean0, d_scale0, d_ys, d_mom, d_means, d_scales, d_nell, d_fn);
     const int rc = mfs::run_streaming_out(st, T, B, nchunks, M2, out_moments, d_mom, [&](int t0, int t1) {
         a.t_begin = t0; a.t_end = t1;
-        const hipError_t e = p->launch(a, p->grid, p->launch_lds, st.s);
+        const hipError_t e = plan_launch(p, a, st.s);
         return (e == hipSuccess) ? MFS_OK : fail(MFS_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     });
     if (rc == MFS_OK) {

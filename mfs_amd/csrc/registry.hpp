@@ -56,6 +56,10 @@ constexpr int traits_index(const int mode, const int umap, const int lik_kind) {
          : MFS_TRAITS_RUNTIME;
 }
 
+// placement counters of the partner-wave variant: {workgroups checked, workgroups whose waves w and w + 4 did not share a SIMD},
+// over the launches of the process.  Each translation unit with partner kernels holds its own copy and registers a reader.
+using PartnerPlacementRead = hipError_t (*)(unsigned long long counts[2]);
+
 // what the fast path has for one (N, lane group) beside its g_table slot
 struct FastEntry {
     Filter1dFastLaunch filter;             // the plain build
@@ -64,12 +68,24 @@ struct FastEntry {
     Filter1dFastLaunch spec[kSpecShapes];  // [spec_shape_index]: specialised one-wave builds (default group of N = 14..16)
     Filter1dFastLaunch spec_traits[kSpecShapes][kTraitSets];   // [spec_shape_index][traits_index - 1]: the same with fixed step
                                                                // traits; null where the pair has no build
+    Filter1dFastLaunch partner[kSpecShapes][kTraitSets];       // the partner-wave variant of spec_traits (filter1d_partner.hpp:
+    int partner_doubles;                                       // N = 14, 15), and its extra LDS doubles per filter
+    PartnerPlacementRead partner_placement;                    // reader of the placement counters of the unit that holds them
     Quad1dLaunch quad_ext;                 // quadrature entry with stable = 1
     Cf1dLaunch cf;                         // characteristic function
     int ext_shift;                         // extra LDS doubles per filter of the extended variant
     int quad_ext_lds;                      // LDS doubles per filter of quad_ext
 };
-extern FastEntry g_fast[MFS_MAX_N + 1][4];   // defined in capi.hip, filled by filter1d_inst.hip (spec: filter1d_spec_inst.hip)
+extern FastEntry g_fast[MFS_MAX_N + 1][4];   // defined in capi.hip, filled by filter1d_inst.hip (spec: filter1d_spec_inst.hip,
+                                             // partner: filter1d_partner_inst.hip)
+
+// geometry of the partner-wave variant: 512-thread workgroups, four main waves of four filters and their four partner waves;
+// dynamic LDS = the main waves' tiles (the one-wave builds') + the partner's tile per filter, within the CU's 160 KiB
+constexpr int kPartnerFilters = 16;
+constexpr int kPartnerLdsMax = 160 * 1024;
+constexpr int partner_lds_bytes(const int lds_doubles_per_filter, const int partner_doubles) {
+    return kPartnerFilters * (lds_doubles_per_filter + partner_doubles) * 8;
+}
 
 // ---- 1-D gradient: [N][n_par]
 using Filter1dGradLaunch = hipError_t (*)(const Filter1dGradArgs&, int n_filters, hipStream_t);
