@@ -539,8 +539,58 @@ int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, int B, int r
 int mfs_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* out_uniform, double* out_normal, int device);
 /* diagnostic for the benchmark tool: with MFS_PF_SPLIT=1 in the environment mfs_particle_filter_1d records an event after every
  * launch and waits once per step; this returns the summed time in ms of the calling thread's last call per kernel, out[5] =
- * propagate (with the block scan), offsets, resample, cf (with the variance), finalize.  Zeros without the switch. */
+ * propagate (with the block scan), offsets, resample, cf (with the variance), finalize.  Zeros without the switch.
+ * mfs_particle_filter_nd honours the same switch; its fourth kernel is the covariance pass. */
 int mfs_pf_last_split_ms(double* out);
+
+/*
+ * ---- bootstrap particle filter, d = 2, host pointers ----------------------------------------------------------------
+ * bootstrap_filter (mfs/classical_filters_smoothers/smc.py:26-84) as dardel/prey_predator/pf.py runs it: 10 000 particles of a
+ * two-dimensional state, Normal proposal N(mu(x), S(x)) with a Cholesky factor per particle, stratified resampling, T = 2000;
+ * for B replicates at once.  The transition is the Normal closure of a mfs_model_nd (MFS_ND_TRANS_GAUSSIAN: blocks 0..4 of
+ * coef = mu_0, mu_1, S_00, S_01, S_11), the likelihood its 1..MFS_ND_MAX_FACTORS single-component factors, the initial law a
+ * mixture of at most MFS_PF_MAX_MIX bivariate Normals given by their lower Cholesky factors, or explicit samples.  Per
+ * measurement t (kernels: particle_nd_kernel.hpp; the particles are held as [B][2][n], component-major):
+ *   L = lower Cholesky factor of S(x_i) in closed form: l_00 = sqrt(S_00), l_10 = S_01 / l_00, l_11 = sqrt(S_11 - l_10^2);
+ *   x'_i0 = mu_0(x_i) + l_00 z_i0,  x'_i1 = mu_1(x_i) + l_10 z_i0 + l_11 z_i1;  a pivot (S_00, S_11 - l_10^2) that is negative
+ *   or not finite makes both components NaN (zero is legal), as jnp.linalg.cholesky does;
+ *   w_i = prod_f lik(kind_f, params_f, y_t[ycol_f], x'_i[component_f]);  nell -= log(mean_i w_i);
+ *   cs, v_i, idx_i as in mfs_particle_filter_1d; the one ancestor index gathers both components: x''_i = x'[idx_i];
+ *   out_means: mean of x'';  out_covs: population covariance about that mean, entries (0,1) and (1,0) both written.
+ *
+ * The random stream extends the 1-D statement above: counter = (particle i, step t, tag, draw), key = the halves of seeds[b];
+ *   tag 0 (t = 0): draws 0, 1 give the normals z_0, z_1, draw 2 the component uniform u_c; c = #{k : mix_cumw[k] <= u_c} clamped
+ *                  to n_mix - 1;  x_i = mix_mean[c] + mix_chol[c] (z_0, z_1)^T
+ *   tag 1: draw k is the propagation normal of component k at step t;  tag 2: draw 0 the resampling uniform, as in 1-D.
+ * Every normal is z = sqrt(-2 ln U(r0, r1)) cos(2 pi U(r2, r3)) of its own Philox block, so mfs_pf_draws reproduces each one.
+ *
+ *   model        d = 2, trans_kind MFS_ND_TRANS_GAUSSIAN, 1..MFS_ND_MAX_FACTORS factors of kind Bernoulli-logistic,
+ *                Poisson-softplus or Gaussian, ny 1 or 2; coef_batched / lik_batched give one table per replicate
+ *   n, T, B      particles (1 .. MFS_PF_MAX_PARTICLES), measurements, replicates;  resampling MFS_RESAMPLE_*
+ *   seeds [B];  n_mix 1 .. MFS_PF_MAX_MIX with mix_cumw [n_mix], mix_mean [n_mix][2], mix_chol [n_mix][2][2] (lower factors,
+ *   computed on the host; entry [0][1] is not read), or n_mix = 0 and init_samples [n][2] or [B][n][2] (init_batched);
+ *   ys [B][T][ny]
+ *   out_samples  [B][T][n][2] or NULL: with NULL nothing of size B T n exists on the device either
+ *   out_means [B][T][2];  out_covs [B][T][2][2];  out_nell [B]
+ *   out_first_nan [B] or NULL: the first step whose sum of weights is zero or not finite, -1 if none.  A NaN particle makes the
+ *                sum NaN.  That replicate is NaN from that step on -- samples, summaries and nell -- and only that replicate;
+ *                no index leaves [0, n - 1].
+ * At most five launches per step and no atomics: every sum runs in an order fixed by n alone (block totals in index order,
+ * covariance partials per segment of 4096 particles in index order), so two calls with the same inputs return the same bits,
+ * and replicate b of a batch returns the bits of a B = 1 call with seeds[b].
+ * MFS_EINVAL: a model that is not MFS_ND_TRANS_GAUSSIAN, n, T or B < 1, an unknown resampling code, n_factors, ny, a factor's
+ * kind, component or column out of range, n_mix outside 0 .. 8, n_mix = 0 without init_samples, a mixture factor whose diagonal
+ * is not finite and > 0, a NULL required buffer.  MFS_EUNSUPPORTED: n > MFS_PF_MAX_PARTICLES, d != 2.  MFS_ENOMEM: the work
+ * buffers cannot be had.
+ */
+int mfs_particle_filter_nd(const mfs_model_nd* model, int n, int T, int B, int resampling, const uint64_t* seeds,
+                           int n_mix, const double* mix_cumw, const double* mix_mean /* [n_mix][2] */,
+                           const double* mix_chol /* [n_mix][2][2], lower factor, computed on the host */,
+                           const double* init_samples /* [n][2] or [B][n][2] */, int init_batched,
+                           const double* ys /* [B][T][ny] */,
+                           double* out_samples /* [B][T][n][2] or NULL */, double* out_means /* [B][T][2] */,
+                           double* out_covs /* [B][T][2][2] */, double* out_nell /* [B] */,
+                           int32_t* out_first_nan /* [B] */, int device, void* stream);
 
 /*
  * ---- Gaussian filters: Gauss--Hermite / cubature sigma-point filter and extended Kalman filter, host pointers ----------

@@ -156,6 +156,8 @@ _SIGNATURES = [
     ('mfs_grid_gemm_dev', _i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     ('mfs_particle_filter_1d', _i, [C.POINTER(MfsModel1d), _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ('mfs_particle_filter_nd', _i, [C.POINTER(MfsModelNd), _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _i, _vp]),
     ('mfs_pf_draws', _i, [_u64, _i, _i, _i, _i, _vp, _vp, _i]),
     ('mfs_pf_last_split_ms', _i, [_vp]),
     ('mfs_gaussian_filter_1d', _i, [C.POINTER(MfsModel1d), _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,

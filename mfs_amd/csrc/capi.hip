@@ -1534,6 +1534,135 @@ extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, i
     return st.finish(me, MFS_OK);
 }
 
+// the same for a two-dimensional state (kernels: particle_nd_kernel.hpp; the `offsets` launch is the 1-D kernel)
+extern "C" int mfs_particle_filter_nd(const mfs_model_nd* model, int n, int T, int B, int resampling, const uint64_t* seeds,
+                                      int n_mix, const double* mix_cumw, const double* mix_mean, const double* mix_chol,
+                                      const double* init_samples, int init_batched, const double* ys, double* out_samples,
+                                      double* out_means, double* out_covs, double* out_nell, int32_t* out_first_nan,
+                                      int device, void* stream) {
+    const char* me = "mfs_particle_filter_nd";
+    if (n < 1 || T < 1 || B < 1) return fail(MFS_EINVAL, "%s: n = %d, T = %d, B = %d (all >= 1)", me, n, T, B);
+    if (n > MFS_PF_MAX_PARTICLES) return fail(MFS_EUNSUPPORTED, "%s: n = %d particles > %d", me, n, MFS_PF_MAX_PARTICLES);
+    if (resampling != MFS_RESAMPLE_STRATIFIED && resampling != MFS_RESAMPLE_SYSTEMATIC)
+        return fail(MFS_EINVAL, "%s: unknown resampling code %d", me, resampling);
+    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
+    if (model->d != 2) return fail(MFS_EUNSUPPORTED, "%s: d = %d (the filter runs d = 2; d = 1 goes through mfs_particle_filter_1d)", me, model->d);
+    if (model->trans_kind != MFS_ND_TRANS_GAUSSIAN)
+        return fail(MFS_EINVAL, "%s: the proposal needs a MFS_ND_TRANS_GAUSSIAN model (trans_kind %d)", me, model->trans_kind);
+    if (model->extent < 1 || model->extent > MFS_ND_MAX_EXTENT_HI)
+        return fail(MFS_EINVAL, "%s: extent %d outside [1, %d]", me, model->extent, MFS_ND_MAX_EXTENT_HI);
+    if (model->n_factors < 1 || model->n_factors > MFS_ND_MAX_FACTORS)
+        return fail(MFS_EINVAL, "%s: n_factors %d outside [1, %d]", me, model->n_factors, MFS_ND_MAX_FACTORS);
+    if (model->ny < 1 || model->ny > 2) return fail(MFS_EINVAL, "%s: ny %d outside [1, 2]", me, model->ny);
+    for (int f = 0; f < model->n_factors; ++f) {
+        if (model->fac_kind[f] < MFS_LIK_BERNOULLI_LOGISTIC || model->fac_kind[f] > MFS_LIK_GAUSSIAN)
+            return fail(MFS_EINVAL, "%s: factor %d: kind %d is not a likelihood of one state component", me, f, model->fac_kind[f]);
+        if (model->fac_component[f] < 0 || model->fac_component[f] > 1)
+            return fail(MFS_EINVAL, "%s: factor %d: fac_component %d outside [0, 1]", me, f, model->fac_component[f]);
+        if (model->fac_ycol[f] < 0 || model->fac_ycol[f] >= model->ny)
+            return fail(MFS_EINVAL, "%s: factor %d: fac_ycol %d outside [0, ny = %d)", me, f, model->fac_ycol[f], model->ny);
+    }
+    if (n_mix < 0 || n_mix > MFS_PF_MAX_MIX) return fail(MFS_EINVAL, "%s: n_mix = %d outside [0, %d]", me, n_mix, MFS_PF_MAX_MIX);
+    if (n_mix == 0 && !init_samples) return fail(MFS_EINVAL, "%s: n_mix = 0 needs init_samples", me);
+    if (n_mix > 0 && (!mix_cumw || !mix_mean || !mix_chol)) return fail(MFS_EINVAL, "%s: mix_cumw / mix_mean / mix_chol must not be NULL", me);
+    for (int k = 0; k < n_mix; ++k) {
+        const double* L = mix_chol + 4 * k;
+        if (!std::isfinite(L[0]) || !(L[0] > 0.0) || !std::isfinite(L[3]) || !(L[3] > 0.0) || !std::isfinite(L[2]) ||
+            !std::isfinite(mix_mean[2 * k]) || !std::isfinite(mix_mean[2 * k + 1]))
+            return fail(MFS_EINVAL, "%s: mixture component %d is not finite with a factor of diagonal > 0", me, k);
+    }
+    if (!model->coef || !model->lik || !seeds || !ys || !out_means || !out_covs || !out_nell)
+        return fail(MFS_EINVAL, "%s: model tables / seeds / ys / out_means / out_covs / out_nell must not be NULL", me);
+    HIP_TRY(hipSetDevice(device));
+
+    const int nblk = mfs::pf_blocks(n), nseg = mfs::pf_segments(n), ny = model->ny, nf = model->n_factors;
+    const size_t table = (size_t)MFS_ND_TABLE_ROWS(model->n_terms) * model->extent * model->extent;
+    const size_t bn = (size_t)B * n, bt = (size_t)B * T;
+    const size_t nb_coef = model->coef_batched ? (size_t)B : 1, nb_lik = model->lik_batched ? (size_t)B : 1;
+    const size_t nb_init = init_batched ? (size_t)B : 1;
+    double *d_coef = nullptr, *d_lik = nullptr, *d_ys = nullptr, *d_mix = nullptr, *d_init = nullptr;
+    uint64_t* d_seeds = nullptr;
+    double *d_x = nullptr, *d_x2 = nullptr, *d_wscan = nullptr, *d_wpart = nullptr, *d_woffs = nullptr, *d_wtot = nullptr;
+    double *d_xpart = nullptr, *d_cpart = nullptr;
+    double *d_samples = nullptr, *d_means = nullptr, *d_covs = nullptr, *d_nell = nullptr;
+    int32_t* d_fn = nullptr;
+    mfs::Staging st(device, stream, true);
+    st.alloc(&d_coef, nb_coef * table * 8); st.alloc(&d_lik, nb_lik * nf * MFS_MAX_LIK * 8); st.alloc(&d_ys, bt * ny * 8);
+    st.alloc(&d_seeds, (size_t)B * 8);
+    if (n_mix > 0) st.alloc(&d_mix, (size_t)7 * n_mix * 8); else st.alloc(&d_init, nb_init * n * 16);
+    st.alloc(&d_x, bn * 16); st.alloc(&d_x2, bn * 16); st.alloc(&d_wscan, bn * 8);
+    st.alloc(&d_wpart, (size_t)B * nblk * 8); st.alloc(&d_woffs, (size_t)B * nblk * 8); st.alloc(&d_wtot, (size_t)B * 8);
+    st.alloc(&d_xpart, (size_t)B * nblk * 16); st.alloc(&d_cpart, (size_t)B * nseg * 24);
+    if (out_samples) st.alloc(&d_samples, bt * n * 16);
+    st.alloc(&d_means, bt * 16); st.alloc(&d_covs, bt * 32);
+    st.alloc(&d_nell, (size_t)B * 8); st.alloc(&d_fn, (size_t)B * 4);
+    st.h2d(d_coef, model->coef, nb_coef * table * 8); st.h2d(d_lik, model->lik, nb_lik * nf * MFS_MAX_LIK * 8);
+    st.h2d(d_ys, ys, bt * ny * 8); st.h2d(d_seeds, seeds, (size_t)B * 8);
+    if (n_mix > 0) {
+        st.h2d(d_mix, mix_cumw, (size_t)n_mix * 8); st.h2d(d_mix + n_mix, mix_mean, (size_t)n_mix * 16);
+        st.h2d(d_mix + 3 * n_mix, mix_chol, (size_t)n_mix * 32);
+    } else {
+        st.h2d(d_init, init_samples, nb_init * n * 16);
+    }
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_nell, 0, (size_t)B * 8, st.s);
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_fn, 0xff, (size_t)B * 4, st.s);   // -1
+
+    mfs::PfNdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = n; a.T = T; a.B = B; a.nblk = nblk; a.nseg = nseg; a.resampling = resampling;
+    a.extent = model->extent; a.coef_stride = (int)table; a.coef_batched = model->coef_batched != 0;
+    a.n_factors = nf; a.ny = ny; a.lik_batched = model->lik_batched != 0;
+    for (int f = 0; f < nf; ++f) {
+        a.fac_kind[f] = model->fac_kind[f]; a.fac_component[f] = model->fac_component[f]; a.fac_ycol[f] = model->fac_ycol[f];
+    }
+    a.coef = d_coef; a.lik = d_lik; a.ys = d_ys; a.seeds = d_seeds;
+    a.n_mix = n_mix; a.init_batched = init_batched != 0;
+    if (n_mix > 0) { a.mix_cumw = d_mix; a.mix_mean = d_mix + n_mix; a.mix_chol = d_mix + 3 * n_mix; }
+    a.init = d_init;
+    a.x = d_x; a.x2 = d_x2; a.wscan = d_wscan; a.wpart = d_wpart; a.woffs = d_woffs; a.wtot = d_wtot; a.xpart = d_xpart;
+    a.cpart = d_cpart; a.out_samples = d_samples; a.out_means = d_means; a.out_covs = d_covs;
+    // what the 1-D `offsets` kernel reads: the geometry, the step, the weight buffers, nell and first_nan
+    mfs::PfArgs o;
+    memset(&o, 0, sizeof(o));
+    o.n = n; o.T = T; o.B = B; o.nblk = nblk; o.nseg = nseg;
+    o.wpart = d_wpart; o.woffs = d_woffs; o.wtot = d_wtot; o.nell = d_nell; o.first_nan = d_fn;
+    if (st.err == hipSuccess) st.err = mfs::launch_pfnd_init(a, st.s);
+    // MFS_PF_SPLIT=1: as in mfs_particle_filter_1d, the five kernels here being propagate, offsets, resample, cov, finalize
+    const char* split_env = getenv("MFS_PF_SPLIT");
+    const bool split = split_env && split_env[0] == '1';
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 6 && split && st.err == hipSuccess; ++k) st.err = hipEventCreate(&ev[k]);
+    for (int k = 0; k < 5; ++k) g_pf_split_ms[k] = 0.0;
+    auto mark = [&](int k) { if (split && st.err == hipSuccess) st.err = hipEventRecord(ev[k], st.s); };
+    for (int t = 0; t < T && st.err == hipSuccess; ++t) {
+        a.t = t; o.t = t;
+        mark(0);
+        st.err = mfs::launch_pfnd_propagate(a, st.s);
+        mark(1);
+        if (st.err == hipSuccess) st.err = mfs::launch_pf_offsets(o, st.s);
+        mark(2);
+        if (st.err == hipSuccess) st.err = mfs::launch_pfnd_resample(a, st.s);
+        mark(3);
+        if (st.err == hipSuccess) st.err = mfs::launch_pfnd_cov(a, st.s);
+        mark(4);
+        if (st.err == hipSuccess) st.err = mfs::launch_pfnd_finalize(a, st.s);
+        mark(5);
+        if (split && st.err == hipSuccess) st.err = hipEventSynchronize(ev[5]);
+        for (int k = 0; k < 5 && split && st.err == hipSuccess; ++k) {
+            float ms = 0.f;
+            st.err = hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            g_pf_split_ms[k] += (double)ms;
+        }
+        std::swap(a.x, a.x2);   // the resampled particles are the next step's
+    }
+    for (int k = 0; k < 6; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    st.d2h(out_samples, d_samples, bt * n * 16);
+    st.d2h(out_means, d_means, bt * 16); st.d2h(out_covs, d_covs, bt * 32);
+    st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
+    return st.finish(me, MFS_OK);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Gaussian filters: sigma-point filter and EKF, host pointers (kernels: gaussfilter_kernel.hpp)
 // ---------------------------------------------------------------------------------------------------------------

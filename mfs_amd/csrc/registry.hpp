@@ -190,6 +190,43 @@ hipError_t launch_pf_cf(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_finalize(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* d_uniform, double* d_normal, hipStream_t s);
 
+// ---- bootstrap particle filter, d = 2 (particle_nd_inst.hip).  The same five launches per measurement, the same constants
+// and the 1-D `offsets` kernel itself (through a PfArgs that names the weight buffers); the particles are [B][2][n],
+// component-major, so every particle pass is coalesced.
+struct PfNdArgs {
+    int n, T, B, t;          // particles, steps, replicates, the step this launch works on
+    int nblk, nseg;          // pf_blocks(n), pf_segments(n)
+    int resampling;          // MFS_RESAMPLE_*
+    int extent, coef_stride, coef_batched;   // D; doubles between two replicates' tables (rows D D); 1: one table per replicate
+    int n_factors, ny, lik_batched;
+    int fac_kind[MFS_ND_MAX_FACTORS], fac_component[MFS_ND_MAX_FACTORS], fac_ycol[MFS_ND_MAX_FACTORS];
+    const double* coef;      // [rows][D][D] or [B][rows][D][D]; blocks 0..4 = mu_0, mu_1, S_00, S_01, S_11
+    const double* lik;       // [n_factors][MFS_MAX_LIK] or [B][n_factors][MFS_MAX_LIK]
+    const double* ys;        // [B][T][ny]
+    const uint64_t* seeds;   // [B]
+    int n_mix, init_batched; // initial law: a mixture of n_mix Normals drawn on the device, or (n_mix = 0) given samples
+    const double* mix_cumw;  // [n_mix]
+    const double* mix_mean;  // [n_mix][2]
+    const double* mix_chol;  // [n_mix][2][2], lower factors
+    const double* init;      // [n][2] or [B][n][2]
+    double* x;               // [B][2][n] the particles: propagated in place, read by the resampler
+    double* x2;              // [B][2][n] the resampled particles (the host swaps x and x2 after every step)
+    double* wscan;           // [B][n] block-local inclusive prefix sums of the weights
+    double* wpart;           // [B][nblk] block totals of the weights
+    double* woffs;           // [B][nblk] their exclusive prefix sums in index order
+    double* wtot;            // [B] sum of the weights
+    double* xpart;           // [B][2][nblk] block totals of the resampled particles, per component
+    double* cpart;           // [B][3][nseg] segment totals of d_0 d_0, d_0 d_1, d_1 d_1, d = x' - mean
+    double* out_samples;     // [B][T][n][2] or null
+    double* out_means;       // [B][T][2]
+    double* out_covs;        // [B][T][2][2]
+};
+hipError_t launch_pfnd_init(const PfNdArgs& a, hipStream_t s);
+hipError_t launch_pfnd_propagate(const PfNdArgs& a, hipStream_t s);
+hipError_t launch_pfnd_resample(const PfNdArgs& a, hipStream_t s);
+hipError_t launch_pfnd_cov(const PfNdArgs& a, hipStream_t s);
+hipError_t launch_pfnd_finalize(const PfNdArgs& a, hipStream_t s);
+
 // ---- Gaussian filters (gaussfilter_inst.hip): the Gauss--Hermite / cubature sigma-point filter and the extended Kalman filter,
 // d = 1 and d = 2, the whole time loop in one launch.  A group of gf_lanes(n_points) lanes owns a replicate (one lane for the
 // EKF); a block is one wavefront, so it holds kGfThreads / lanes replicates.

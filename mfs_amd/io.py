@@ -45,3 +45,13 @@ def save_pf_result(filename, means, cfs):
 def load_pf_result(filename):
     data = np.load(filename)
     return data['pf_filtering_means'], data['pf_filtering_cfs']
+
+
+def save_pf_errs(filename, errs):
+    """One 2-D particle-filter run in the layout dardel/prey_predator/pf.py:77 writes: the absolute errors (T, 2) of the
+    filtering means against the simulated trajectory, under the key `errs`."""
+    np.savez_compressed(filename, errs=np.asarray(errs))
+
+
+def load_pf_errs(filename):
+    return np.load(filename)['errs']
