@@ -1379,7 +1379,8 @@ extern "C" int mfs_grid_filter_1d(int n, int T, int B, int substeps, int use_pow
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// bootstrap particle filter, host pointers (kernels: particle_kernel.hpp)
+// bootstrap particle filters, host pointers (kernels: particle_kernel.hpp for d = 1, particle_nd_kernel.hpp for d = 2).  The two
+// entries share their argument check, their work buffers and the step driver below; each stages its own model and summaries
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int mfs_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* out_uniform, double* out_normal,
                             int device) {
@@ -1405,28 +1406,114 @@ extern "C" int mfs_pf_last_split_ms(double* out) {
     return MFS_OK;
 }
 
-extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, int B, int resampling, const uint64_t* seeds,
-                                      int n_mix, const double* mix_cumw, const double* mix_mean, const double* mix_var,
-                                      const double* init_samples, int init_batched, const double* ys, int nz, const double* zs,
-                                      double* out_samples, double* out_means, double* out_vars, double* out_cfs,
-                                      double* out_nell, int32_t* out_first_nan, int device, void* stream) {
-    const char* me = "mfs_particle_filter_1d";
+// ---- what the particle filters of every state dimension share on the host
+// the arguments both entries take; `mix_spread` is the mixture's third array (mix_var, mix_chol), named in the message
+static int check_pf_args(const char* me, int n, int T, int B, int resampling, int n_mix, const double* mix_cumw,
+                         const double* mix_mean, const double* mix_spread, const char* spread_name, const double* init_samples) {
     if (n < 1 || T < 1 || B < 1) return fail(MFS_EINVAL, "%s: n = %d, T = %d, B = %d (all >= 1)", me, n, T, B);
     if (n > MFS_PF_MAX_PARTICLES) return fail(MFS_EUNSUPPORTED, "%s: n = %d particles > %d", me, n, MFS_PF_MAX_PARTICLES);
     if (resampling != MFS_RESAMPLE_STRATIFIED && resampling != MFS_RESAMPLE_SYSTEMATIC)
         return fail(MFS_EINVAL, "%s: unknown resampling code %d", me, resampling);
+    if (n_mix < 0 || n_mix > MFS_PF_MAX_MIX) return fail(MFS_EINVAL, "%s: n_mix = %d outside [0, %d]", me, n_mix, MFS_PF_MAX_MIX);
+    if (n_mix == 0 && !init_samples) return fail(MFS_EINVAL, "%s: n_mix = 0 needs init_samples", me);
+    if (n_mix > 0 && (!mix_cumw || !mix_mean || !mix_spread))
+        return fail(MFS_EINVAL, "%s: mix_cumw / mix_mean / %s must not be NULL", me, spread_name);
+    return MFS_OK;
+}
+
+// The work buffers that do not depend on the state dimension: the seeds (uploaded), the weight scan, and what the `offsets`
+// kernel takes -- the block totals, their offsets, the weight sums, nell (zeroed) and first_nan (-1) -- which is returned
+static mfs::PfOffsetsArgs pf_work_buffers(mfs::Staging& st, int n, int B, const uint64_t* seeds, uint64_t** d_seeds,
+                                          double** d_wscan) {
+    mfs::PfOffsetsArgs o;
+    memset(&o, 0, sizeof(o));
+    o.n = n; o.B = B; o.nblk = mfs::pf_blocks(n);
+    st.alloc(d_seeds, (size_t)B * 8); st.alloc(d_wscan, (size_t)B * n * 8);
+    st.alloc(&o.wpart, (size_t)B * o.nblk * 8); st.alloc(&o.woffs, (size_t)B * o.nblk * 8); st.alloc(&o.wtot, (size_t)B * 8);
+    st.alloc(&o.nell, (size_t)B * 8); st.alloc(&o.first_nan, (size_t)B * 4);
+    st.h2d(*d_seeds, seeds, (size_t)B * 8);
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(o.nell, 0, (size_t)B * 8, st.s);
+    if (st.err == hipSuccess) st.err = hipMemsetAsync(o.first_nan, 0xff, (size_t)B * 4, st.s);   // -1
+    return o;
+}
+
+// The T steps of a call on st.s: begin(t), then the step's five launches launch(0) .. launch(4) (propagate, offsets, resample,
+// the summary pass, finalize), then end().  MFS_PF_SPLIT=1 (the benchmark tools; read at every call): an event after every
+// launch and a wait per step, so that mfs_pf_last_split_ms can report the time of each of the five kernels; the results are
+// the same bits, the call is slower by the waits
+template <typename Begin, typename Launch, typename End>
+static void pf_run_steps(mfs::Staging& st, int T, Begin&& begin, Launch&& launch, End&& end) {
+    const char* split_env = getenv("MFS_PF_SPLIT");
+    const bool split = split_env && split_env[0] == '1';
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 6 && split && st.err == hipSuccess; ++k) st.err = hipEventCreate(&ev[k]);
+    for (int k = 0; k < 5; ++k) g_pf_split_ms[k] = 0.0;
+    auto mark = [&](int k) { if (split && st.err == hipSuccess) st.err = hipEventRecord(ev[k], st.s); };
+    for (int t = 0; t < T && st.err == hipSuccess; ++t) {
+        begin(t);
+        mark(0);
+        for (int k = 0; k < 5; ++k) {
+            if (st.err == hipSuccess) st.err = launch(k);
+            mark(k + 1);
+        }
+        if (split && st.err == hipSuccess) st.err = hipEventSynchronize(ev[5]);
+        for (int k = 0; k < 5 && split && st.err == hipSuccess; ++k) {
+            float ms = 0.f;
+            st.err = hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            g_pf_split_ms[k] += (double)ms;
+        }
+        end();
+    }
+    for (int k = 0; k < 6; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+}
+
+// ---- Gaussian-transition models, as the baselines take them (the particle filters here, the Gaussian filters below).  `me`
+// is the entry's name and `what` the thing that needs the model ("proposal", "filter")
+static int check_gaussian_model_1d(const char* me, const char* what, const mfs_model_1d* model) {
     if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
     if (model->trans_kind != MFS_TRANS_GAUSSIAN || model->n_rows != 2)
-        return fail(MFS_EINVAL, "%s: the proposal needs a MFS_TRANS_GAUSSIAN model (trans_kind %d, n_rows %d)", me,
+        return fail(MFS_EINVAL, "%s: the %s needs a MFS_TRANS_GAUSSIAN model (trans_kind %d, n_rows %d)", me, what,
                     model->trans_kind, model->n_rows);
     if (model->degree < 0 || model->degree > MFS_MAX_DEGREE) return fail(MFS_EINVAL, "%s: degree %d outside [0, %d]", me, model->degree, MFS_MAX_DEGREE);
     if (model->umap != MFS_U_IDENTITY && model->umap != MFS_U_TANH) return fail(MFS_EINVAL, "%s: unknown umap %d", me, model->umap);
     if (model->lik_kind < MFS_LIK_BERNOULLI_LOGISTIC || model->lik_kind > MFS_LIK_GAUSSIAN)
         return fail(MFS_EINVAL, "%s: lik_kind %d is not a 1-D likelihood", me, model->lik_kind);
     if (model->n_lik < 1 || model->n_lik > MFS_MAX_LIK) return fail(MFS_EINVAL, "%s: n_lik %d outside [1, %d]", me, model->n_lik, MFS_MAX_LIK);
-    if (n_mix < 0 || n_mix > MFS_PF_MAX_MIX) return fail(MFS_EINVAL, "%s: n_mix = %d outside [0, %d]", me, n_mix, MFS_PF_MAX_MIX);
-    if (n_mix == 0 && !init_samples) return fail(MFS_EINVAL, "%s: n_mix = 0 needs init_samples", me);
-    if (n_mix > 0 && (!mix_cumw || !mix_mean || !mix_var)) return fail(MFS_EINVAL, "%s: mix_cumw / mix_mean / mix_var must not be NULL", me);
+    return MFS_OK;
+}
+
+// d = 2: the model and its table, then its likelihood factors 0 .. n_factors - 1.  An entry's own restrictions on the factors
+// (how many, which columns; MFS_EUNSUPPORTED where the model is valid but not run) come between the two
+static int check_gaussian_model_nd(const char* me, const char* what, const mfs_model_nd* model) {
+    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
+    if (model->d != 2) return fail(MFS_EUNSUPPORTED, "%s: d = %d (the filter runs d = 2; d = 1 goes through %.*s1d)", me, model->d,
+                                       (int)strlen(me) - 2, me);
+    if (model->trans_kind != MFS_ND_TRANS_GAUSSIAN)
+        return fail(MFS_EINVAL, "%s: the %s needs a MFS_ND_TRANS_GAUSSIAN model (trans_kind %d)", me, what, model->trans_kind);
+    if (model->extent < 1 || model->extent > MFS_ND_MAX_EXTENT_HI)
+        return fail(MFS_EINVAL, "%s: extent %d outside [1, %d]", me, model->extent, MFS_ND_MAX_EXTENT_HI);
+    return MFS_OK;
+}
+
+static int check_gaussian_factors_nd(const char* me, const mfs_model_nd* model, int n_factors) {
+    for (int f = 0; f < n_factors; ++f) {
+        if (model->fac_kind[f] < MFS_LIK_BERNOULLI_LOGISTIC || model->fac_kind[f] > MFS_LIK_GAUSSIAN)
+            return fail(MFS_EINVAL, "%s: factor %d: kind %d is not a likelihood of one state component", me, f, model->fac_kind[f]);
+        if (model->fac_component[f] < 0 || model->fac_component[f] > 1)
+            return fail(MFS_EINVAL, "%s: factor %d: fac_component %d outside [0, 1]", me, f, model->fac_component[f]);
+    }
+    return MFS_OK;
+}
+
+extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, int B, int resampling, const uint64_t* seeds,
+                                      int n_mix, const double* mix_cumw, const double* mix_mean, const double* mix_var,
+                                      const double* init_samples, int init_batched, const double* ys, int nz, const double* zs,
+                                      double* out_samples, double* out_means, double* out_vars, double* out_cfs,
+                                      double* out_nell, int32_t* out_first_nan, int device, void* stream) {
+    const char* me = "mfs_particle_filter_1d";
+    if (const int rc = check_pf_args(me, n, T, B, resampling, n_mix, mix_cumw, mix_mean, mix_var, "mix_var", init_samples)) return rc;
+    if (const int rc = check_gaussian_model_1d(me, "proposal", model)) return rc;
     for (int k = 0; k < n_mix; ++k)
         if (!std::isfinite(mix_var[k]) || !(mix_var[k] > 0.0) || !std::isfinite(mix_mean[k]))
             return fail(MFS_EINVAL, "%s: mixture component %d is not finite with variance > 0", me, k);
@@ -1454,25 +1541,21 @@ extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, i
     const size_t nb_init = init_batched ? (size_t)B : 1;
     double *d_coef = nullptr, *d_lik = nullptr, *d_ys = nullptr, *d_mix = nullptr, *d_init = nullptr, *d_zs = nullptr;
     uint64_t* d_seeds = nullptr;
-    double *d_x = nullptr, *d_x2 = nullptr, *d_wscan = nullptr, *d_wpart = nullptr, *d_woffs = nullptr, *d_wtot = nullptr;
-    double *d_xpart = nullptr, *d_vpart = nullptr, *d_cfpart = nullptr;
-    double *d_samples = nullptr, *d_means = nullptr, *d_vars = nullptr, *d_cfs = nullptr, *d_nell = nullptr;
-    int32_t* d_fn = nullptr;
+    double *d_x = nullptr, *d_x2 = nullptr, *d_wscan = nullptr, *d_xpart = nullptr, *d_vpart = nullptr, *d_cfpart = nullptr;
+    double *d_samples = nullptr, *d_means = nullptr, *d_vars = nullptr, *d_cfs = nullptr;
     mfs::Staging st(device, stream, true);
     st.alloc(&d_coef, nb_coef * 2 * J1 * 8); st.alloc(&d_lik, nb_lik * model->n_lik * 8); st.alloc(&d_ys, bt * 8);
-    st.alloc(&d_seeds, (size_t)B * 8);
+    mfs::PfOffsetsArgs o = pf_work_buffers(st, n, B, seeds, &d_seeds, &d_wscan);
     if (n_mix > 0) st.alloc(&d_mix, (size_t)3 * n_mix * 8); else st.alloc(&d_init, nb_init * n * 8);
     if (nz > 0) st.alloc(&d_zs, (size_t)nz * 8);
-    st.alloc(&d_x, bn * 8); st.alloc(&d_x2, bn * 8); st.alloc(&d_wscan, bn * 8);
-    st.alloc(&d_wpart, (size_t)B * nblk * 8); st.alloc(&d_woffs, (size_t)B * nblk * 8); st.alloc(&d_wtot, (size_t)B * 8);
+    st.alloc(&d_x, bn * 8); st.alloc(&d_x2, bn * 8);
     st.alloc(&d_xpart, (size_t)B * nblk * 8); st.alloc(&d_vpart, (size_t)B * nseg * 8);
     if (nz > 0) st.alloc(&d_cfpart, (size_t)B * nseg * nz * 16);
     if (out_samples) st.alloc(&d_samples, bt * n * 8);
     st.alloc(&d_means, bt * 8); st.alloc(&d_vars, bt * 8);
     if (nz > 0) st.alloc(&d_cfs, bt * nz * 16);
-    st.alloc(&d_nell, (size_t)B * 8); st.alloc(&d_fn, (size_t)B * 4);
     st.h2d(d_coef, model->coef, nb_coef * 2 * J1 * 8); st.h2d(d_lik, model->lik, nb_lik * model->n_lik * 8);
-    st.h2d(d_ys, ys, bt * 8); st.h2d(d_seeds, seeds, (size_t)B * 8);
+    st.h2d(d_ys, ys, bt * 8);
     if (n_mix > 0) {
         st.h2d(d_mix, mix_cumw, (size_t)n_mix * 8); st.h2d(d_mix + n_mix, mix_mean, (size_t)n_mix * 8);
         st.h2d(d_mix + 2 * n_mix, mix_var, (size_t)n_mix * 8);
@@ -1480,8 +1563,6 @@ extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, i
         st.h2d(d_init, init_samples, nb_init * n * 8);
     }
     if (nz > 0) st.h2d(d_zs, zs, (size_t)nz * 8);
-    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_nell, 0, (size_t)B * 8, st.s);
-    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_fn, 0xff, (size_t)B * 4, st.s);   // -1
 
     mfs::PfArgs a;
     memset(&a, 0, sizeof(a));
@@ -1492,79 +1573,40 @@ extern "C" int mfs_particle_filter_1d(const mfs_model_1d* model, int n, int T, i
     a.n_mix = n_mix; a.init_batched = init_batched != 0;
     if (n_mix > 0) { a.mix_cumw = d_mix; a.mix_mean = d_mix + n_mix; a.mix_var = d_mix + 2 * n_mix; }
     a.init = d_init; a.nz = nz; a.z_uniform = z_uniform; a.dz = dz; a.zs = d_zs;
-    a.x = d_x; a.x2 = d_x2; a.wscan = d_wscan; a.wpart = d_wpart; a.woffs = d_woffs; a.wtot = d_wtot; a.xpart = d_xpart;
+    a.x = d_x; a.x2 = d_x2; a.wscan = d_wscan; a.wpart = o.wpart; a.woffs = o.woffs; a.wtot = o.wtot; a.xpart = d_xpart;
     a.vpart = d_vpart; a.cfpart = d_cfpart; a.out_samples = d_samples; a.out_means = d_means; a.out_vars = d_vars;
-    a.out_cfs = d_cfs; a.nell = d_nell; a.first_nan = d_fn;
+    a.out_cfs = d_cfs;
     if (st.err == hipSuccess) st.err = mfs::launch_pf_init(a, st.s);
-    // MFS_PF_SPLIT=1 (the benchmark tool): an event after every launch and a wait per step, so that mfs_pf_last_split_ms can
-    // report the time of each of the five kernels; the results are the same bits, the call is slower by the waits
-    const char* split_env = getenv("MFS_PF_SPLIT");
-    const bool split = split_env && split_env[0] == '1';
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 6 && split && st.err == hipSuccess; ++k) st.err = hipEventCreate(&ev[k]);
-    for (int k = 0; k < 5; ++k) g_pf_split_ms[k] = 0.0;
-    auto mark = [&](int k) { if (split && st.err == hipSuccess) st.err = hipEventRecord(ev[k], st.s); };
-    for (int t = 0; t < T && st.err == hipSuccess; ++t) {
-        a.t = t;
-        mark(0);
-        st.err = mfs::launch_pf_propagate(a, st.s);
-        mark(1);
-        if (st.err == hipSuccess) st.err = mfs::launch_pf_offsets(a, st.s);
-        mark(2);
-        if (st.err == hipSuccess) st.err = mfs::launch_pf_resample(a, st.s);
-        mark(3);
-        if (st.err == hipSuccess) st.err = mfs::launch_pf_cf(a, st.s);
-        mark(4);
-        if (st.err == hipSuccess) st.err = mfs::launch_pf_finalize(a, st.s);
-        mark(5);
-        if (split && st.err == hipSuccess) st.err = hipEventSynchronize(ev[5]);
-        for (int k = 0; k < 5 && split && st.err == hipSuccess; ++k) {
-            float ms = 0.f;
-            st.err = hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-            g_pf_split_ms[k] += (double)ms;
-        }
-        std::swap(a.x, a.x2);   // the resampled particles are the next step's
-    }
-    for (int k = 0; k < 6; ++k)
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    pf_run_steps(st, T, [&](int t) { a.t = o.t = t; },
+                 [&](int k) {
+                     return k == 0 ? mfs::launch_pf_propagate(a, st.s) : k == 1 ? mfs::launch_pf_offsets(o, st.s)
+                          : k == 2 ? mfs::launch_pf_resample(a, st.s) : k == 3 ? mfs::launch_pf_cf(a, st.s)
+                                                                               : mfs::launch_pf_finalize(a, st.s);
+                 },
+                 [&] { std::swap(a.x, a.x2); });   // the resampled particles are the next step's
     st.d2h(out_samples, d_samples, bt * n * 8);
     st.d2h(out_means, d_means, bt * 8); st.d2h(out_vars, d_vars, bt * 8);
     st.d2h(out_cfs, d_cfs, bt * nz * 16);
-    st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
+    st.d2h(out_nell, o.nell, (size_t)B * 8); st.d2h(out_first_nan, o.first_nan, (size_t)B * 4);
     return st.finish(me, MFS_OK);
 }
 
-// the same for a two-dimensional state (kernels: particle_nd_kernel.hpp; the `offsets` launch is the 1-D kernel)
+// the same for a two-dimensional state (kernels: particle_nd_kernel.hpp)
 extern "C" int mfs_particle_filter_nd(const mfs_model_nd* model, int n, int T, int B, int resampling, const uint64_t* seeds,
                                       int n_mix, const double* mix_cumw, const double* mix_mean, const double* mix_chol,
                                       const double* init_samples, int init_batched, const double* ys, double* out_samples,
                                       double* out_means, double* out_covs, double* out_nell, int32_t* out_first_nan,
                                       int device, void* stream) {
     const char* me = "mfs_particle_filter_nd";
-    if (n < 1 || T < 1 || B < 1) return fail(MFS_EINVAL, "%s: n = %d, T = %d, B = %d (all >= 1)", me, n, T, B);
-    if (n > MFS_PF_MAX_PARTICLES) return fail(MFS_EUNSUPPORTED, "%s: n = %d particles > %d", me, n, MFS_PF_MAX_PARTICLES);
-    if (resampling != MFS_RESAMPLE_STRATIFIED && resampling != MFS_RESAMPLE_SYSTEMATIC)
-        return fail(MFS_EINVAL, "%s: unknown resampling code %d", me, resampling);
-    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
-    if (model->d != 2) return fail(MFS_EUNSUPPORTED, "%s: d = %d (the filter runs d = 2; d = 1 goes through mfs_particle_filter_1d)", me, model->d);
-    if (model->trans_kind != MFS_ND_TRANS_GAUSSIAN)
-        return fail(MFS_EINVAL, "%s: the proposal needs a MFS_ND_TRANS_GAUSSIAN model (trans_kind %d)", me, model->trans_kind);
-    if (model->extent < 1 || model->extent > MFS_ND_MAX_EXTENT_HI)
-        return fail(MFS_EINVAL, "%s: extent %d outside [1, %d]", me, model->extent, MFS_ND_MAX_EXTENT_HI);
+    if (const int rc = check_pf_args(me, n, T, B, resampling, n_mix, mix_cumw, mix_mean, mix_chol, "mix_chol", init_samples)) return rc;
+    if (const int rc = check_gaussian_model_nd(me, "proposal", model)) return rc;
     if (model->n_factors < 1 || model->n_factors > MFS_ND_MAX_FACTORS)
         return fail(MFS_EINVAL, "%s: n_factors %d outside [1, %d]", me, model->n_factors, MFS_ND_MAX_FACTORS);
     if (model->ny < 1 || model->ny > 2) return fail(MFS_EINVAL, "%s: ny %d outside [1, 2]", me, model->ny);
-    for (int f = 0; f < model->n_factors; ++f) {
-        if (model->fac_kind[f] < MFS_LIK_BERNOULLI_LOGISTIC || model->fac_kind[f] > MFS_LIK_GAUSSIAN)
-            return fail(MFS_EINVAL, "%s: factor %d: kind %d is not a likelihood of one state component", me, f, model->fac_kind[f]);
-        if (model->fac_component[f] < 0 || model->fac_component[f] > 1)
-            return fail(MFS_EINVAL, "%s: factor %d: fac_component %d outside [0, 1]", me, f, model->fac_component[f]);
+    if (const int rc = check_gaussian_factors_nd(me, model, model->n_factors)) return rc;
+    for (int f = 0; f < model->n_factors; ++f)
         if (model->fac_ycol[f] < 0 || model->fac_ycol[f] >= model->ny)
             return fail(MFS_EINVAL, "%s: factor %d: fac_ycol %d outside [0, ny = %d)", me, f, model->fac_ycol[f], model->ny);
-    }
-    if (n_mix < 0 || n_mix > MFS_PF_MAX_MIX) return fail(MFS_EINVAL, "%s: n_mix = %d outside [0, %d]", me, n_mix, MFS_PF_MAX_MIX);
-    if (n_mix == 0 && !init_samples) return fail(MFS_EINVAL, "%s: n_mix = 0 needs init_samples", me);
-    if (n_mix > 0 && (!mix_cumw || !mix_mean || !mix_chol)) return fail(MFS_EINVAL, "%s: mix_cumw / mix_mean / mix_chol must not be NULL", me);
     for (int k = 0; k < n_mix; ++k) {
         const double* L = mix_chol + 4 * k;
         if (!std::isfinite(L[0]) || !(L[0] > 0.0) || !std::isfinite(L[3]) || !(L[3] > 0.0) || !std::isfinite(L[2]) ||
@@ -1582,30 +1624,24 @@ extern "C" int mfs_particle_filter_nd(const mfs_model_nd* model, int n, int T, i
     const size_t nb_init = init_batched ? (size_t)B : 1;
     double *d_coef = nullptr, *d_lik = nullptr, *d_ys = nullptr, *d_mix = nullptr, *d_init = nullptr;
     uint64_t* d_seeds = nullptr;
-    double *d_x = nullptr, *d_x2 = nullptr, *d_wscan = nullptr, *d_wpart = nullptr, *d_woffs = nullptr, *d_wtot = nullptr;
-    double *d_xpart = nullptr, *d_cpart = nullptr;
-    double *d_samples = nullptr, *d_means = nullptr, *d_covs = nullptr, *d_nell = nullptr;
-    int32_t* d_fn = nullptr;
+    double *d_x = nullptr, *d_x2 = nullptr, *d_wscan = nullptr, *d_xpart = nullptr, *d_cpart = nullptr;
+    double *d_samples = nullptr, *d_means = nullptr, *d_covs = nullptr;
     mfs::Staging st(device, stream, true);
     st.alloc(&d_coef, nb_coef * table * 8); st.alloc(&d_lik, nb_lik * nf * MFS_MAX_LIK * 8); st.alloc(&d_ys, bt * ny * 8);
-    st.alloc(&d_seeds, (size_t)B * 8);
+    mfs::PfOffsetsArgs o = pf_work_buffers(st, n, B, seeds, &d_seeds, &d_wscan);
     if (n_mix > 0) st.alloc(&d_mix, (size_t)7 * n_mix * 8); else st.alloc(&d_init, nb_init * n * 16);
-    st.alloc(&d_x, bn * 16); st.alloc(&d_x2, bn * 16); st.alloc(&d_wscan, bn * 8);
-    st.alloc(&d_wpart, (size_t)B * nblk * 8); st.alloc(&d_woffs, (size_t)B * nblk * 8); st.alloc(&d_wtot, (size_t)B * 8);
+    st.alloc(&d_x, bn * 16); st.alloc(&d_x2, bn * 16);
     st.alloc(&d_xpart, (size_t)B * nblk * 16); st.alloc(&d_cpart, (size_t)B * nseg * 24);
     if (out_samples) st.alloc(&d_samples, bt * n * 16);
     st.alloc(&d_means, bt * 16); st.alloc(&d_covs, bt * 32);
-    st.alloc(&d_nell, (size_t)B * 8); st.alloc(&d_fn, (size_t)B * 4);
     st.h2d(d_coef, model->coef, nb_coef * table * 8); st.h2d(d_lik, model->lik, nb_lik * nf * MFS_MAX_LIK * 8);
-    st.h2d(d_ys, ys, bt * ny * 8); st.h2d(d_seeds, seeds, (size_t)B * 8);
+    st.h2d(d_ys, ys, bt * ny * 8);
     if (n_mix > 0) {
         st.h2d(d_mix, mix_cumw, (size_t)n_mix * 8); st.h2d(d_mix + n_mix, mix_mean, (size_t)n_mix * 16);
         st.h2d(d_mix + 3 * n_mix, mix_chol, (size_t)n_mix * 32);
     } else {
         st.h2d(d_init, init_samples, nb_init * n * 16);
     }
-    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_nell, 0, (size_t)B * 8, st.s);
-    if (st.err == hipSuccess) st.err = hipMemsetAsync(d_fn, 0xff, (size_t)B * 4, st.s);   // -1
 
     mfs::PfNdArgs a;
     memset(&a, 0, sizeof(a));
@@ -1619,47 +1655,19 @@ extern "C" int mfs_particle_filter_nd(const mfs_model_nd* model, int n, int T, i
     a.n_mix = n_mix; a.init_batched = init_batched != 0;
     if (n_mix > 0) { a.mix_cumw = d_mix; a.mix_mean = d_mix + n_mix; a.mix_chol = d_mix + 3 * n_mix; }
     a.init = d_init;
-    a.x = d_x; a.x2 = d_x2; a.wscan = d_wscan; a.wpart = d_wpart; a.woffs = d_woffs; a.wtot = d_wtot; a.xpart = d_xpart;
+    a.x = d_x; a.x2 = d_x2; a.wscan = d_wscan; a.wpart = o.wpart; a.woffs = o.woffs; a.wtot = o.wtot; a.xpart = d_xpart;
     a.cpart = d_cpart; a.out_samples = d_samples; a.out_means = d_means; a.out_covs = d_covs;
-    // what the 1-D `offsets` kernel reads: the geometry, the step, the weight buffers, nell and first_nan
-    mfs::PfArgs o;
-    memset(&o, 0, sizeof(o));
-    o.n = n; o.T = T; o.B = B; o.nblk = nblk; o.nseg = nseg;
-    o.wpart = d_wpart; o.woffs = d_woffs; o.wtot = d_wtot; o.nell = d_nell; o.first_nan = d_fn;
     if (st.err == hipSuccess) st.err = mfs::launch_pfnd_init(a, st.s);
-    // MFS_PF_SPLIT=1: as in mfs_particle_filter_1d, the five kernels here being propagate, offsets, resample, cov, finalize
-    const char* split_env = getenv("MFS_PF_SPLIT");
-    const bool split = split_env && split_env[0] == '1';
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 6 && split && st.err == hipSuccess; ++k) st.err = hipEventCreate(&ev[k]);
-    for (int k = 0; k < 5; ++k) g_pf_split_ms[k] = 0.0;
-    auto mark = [&](int k) { if (split && st.err == hipSuccess) st.err = hipEventRecord(ev[k], st.s); };
-    for (int t = 0; t < T && st.err == hipSuccess; ++t) {
-        a.t = t; o.t = t;
-        mark(0);
-        st.err = mfs::launch_pfnd_propagate(a, st.s);
-        mark(1);
-        if (st.err == hipSuccess) st.err = mfs::launch_pf_offsets(o, st.s);
-        mark(2);
-        if (st.err == hipSuccess) st.err = mfs::launch_pfnd_resample(a, st.s);
-        mark(3);
-        if (st.err == hipSuccess) st.err = mfs::launch_pfnd_cov(a, st.s);
-        mark(4);
-        if (st.err == hipSuccess) st.err = mfs::launch_pfnd_finalize(a, st.s);
-        mark(5);
-        if (split && st.err == hipSuccess) st.err = hipEventSynchronize(ev[5]);
-        for (int k = 0; k < 5 && split && st.err == hipSuccess; ++k) {
-            float ms = 0.f;
-            st.err = hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-            g_pf_split_ms[k] += (double)ms;
-        }
-        std::swap(a.x, a.x2);   // the resampled particles are the next step's
-    }
-    for (int k = 0; k < 6; ++k)
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    pf_run_steps(st, T, [&](int t) { a.t = o.t = t; },
+                 [&](int k) {
+                     return k == 0 ? mfs::launch_pfnd_propagate(a, st.s) : k == 1 ? mfs::launch_pf_offsets(o, st.s)
+                          : k == 2 ? mfs::launch_pfnd_resample(a, st.s) : k == 3 ? mfs::launch_pfnd_cov(a, st.s)
+                                                                                 : mfs::launch_pfnd_finalize(a, st.s);
+                 },
+                 [&] { std::swap(a.x, a.x2); });   // the resampled particles are the next step's
     st.d2h(out_samples, d_samples, bt * n * 16);
     st.d2h(out_means, d_means, bt * 16); st.d2h(out_covs, d_covs, bt * 32);
-    st.d2h(out_nell, d_nell, (size_t)B * 8); st.d2h(out_first_nan, d_fn, (size_t)B * 4);
+    st.d2h(out_nell, o.nell, (size_t)B * 8); st.d2h(out_first_nan, o.first_nan, (size_t)B * 4);
     return st.finish(me, MFS_OK);
 }
 
@@ -1714,15 +1722,7 @@ extern "C" int mfs_gaussian_filter_1d(const mfs_model_1d* model, int method, int
                                       double* out_means, double* out_vars, double* out_nells, int32_t* out_first_nan,
                                       int device, void* stream) {
     const char* me = "mfs_gaussian_filter_1d";
-    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
-    if (model->trans_kind != MFS_TRANS_GAUSSIAN || model->n_rows != 2)
-        return fail(MFS_EINVAL, "%s: the filter needs a MFS_TRANS_GAUSSIAN model (trans_kind %d, n_rows %d)", me,
-                    model->trans_kind, model->n_rows);
-    if (model->degree < 0 || model->degree > MFS_MAX_DEGREE) return fail(MFS_EINVAL, "%s: degree %d outside [0, %d]", me, model->degree, MFS_MAX_DEGREE);
-    if (model->umap != MFS_U_IDENTITY && model->umap != MFS_U_TANH) return fail(MFS_EINVAL, "%s: unknown umap %d", me, model->umap);
-    if (model->lik_kind < MFS_LIK_BERNOULLI_LOGISTIC || model->lik_kind > MFS_LIK_GAUSSIAN)
-        return fail(MFS_EINVAL, "%s: lik_kind %d is not a 1-D likelihood", me, model->lik_kind);
-    if (model->n_lik < 1 || model->n_lik > MFS_MAX_LIK) return fail(MFS_EINVAL, "%s: n_lik %d outside [1, %d]", me, model->n_lik, MFS_MAX_LIK);
+    if (const int rc = check_gaussian_model_1d(me, "filter", model)) return rc;
     mfs::GfArgs a;
     memset(&a, 0, sizeof(a));
     a.d = 1; a.method = method; a.n_points = n_points; a.T = T; a.B = B; a.init_batched = init_batched != 0;
@@ -1739,20 +1739,13 @@ extern "C" int mfs_gaussian_filter_nd(const mfs_model_nd* model, int method, int
                                       double* out_means, double* out_covs, double* out_nells, int32_t* out_first_nan,
                                       int device, void* stream) {
     const char* me = "mfs_gaussian_filter_nd";
-    if (!model) return fail(MFS_EINVAL, "%s: NULL model", me);
-    if (model->d != 2) return fail(MFS_EUNSUPPORTED, "%s: d = %d (the filter runs d = 2; d = 1 goes through mfs_gaussian_filter_1d)", me, model->d);
-    if (model->trans_kind != MFS_ND_TRANS_GAUSSIAN)
-        return fail(MFS_EINVAL, "%s: the filter needs a MFS_ND_TRANS_GAUSSIAN model (trans_kind %d)", me, model->trans_kind);
+    if (const int rc = check_gaussian_model_nd(me, "filter", model)) return rc;
     if (model->n_factors != 1 || model->ny != 1 || model->fac_ycol[0] != 0)
         return fail(MFS_EUNSUPPORTED, "%s: one likelihood factor of a scalar measurement is supported (n_factors %d, ny %d)", me,
                     model->n_factors, model->ny);
     if (model->fac_kind[0] == MFS_LIK_BEARING_GAUSSIAN || model->fac_component[0] == 2)
         return fail(MFS_EUNSUPPORTED, "%s: a likelihood factor of both state components is not supported", me);
-    if (model->fac_kind[0] < MFS_LIK_BERNOULLI_LOGISTIC || model->fac_kind[0] > MFS_LIK_GAUSSIAN)
-        return fail(MFS_EINVAL, "%s: unknown likelihood kind %d", me, model->fac_kind[0]);
-    if (model->fac_component[0] < 0 || model->fac_component[0] > 1) return fail(MFS_EINVAL, "%s: fac_component %d outside [0, 1]", me, model->fac_component[0]);
-    if (model->extent < 1 || model->extent > MFS_ND_MAX_EXTENT_HI)
-        return fail(MFS_EINVAL, "%s: extent %d outside [1, %d]", me, model->extent, MFS_ND_MAX_EXTENT_HI);
+    if (const int rc = check_gaussian_factors_nd(me, model, 1)) return rc;
     if (model->coef_batched) return fail(MFS_EUNSUPPORTED, "%s: per-replicate transition tables (coef_batched) are not supported at d = 2", me);
     mfs::GfArgs a;
     memset(&a, 0, sizeof(a));

@@ -15,7 +15,7 @@ hipError_t launch_pf_propagate(const PfArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_pf_offsets(const PfArgs& a, hipStream_t s) {
+hipError_t launch_pf_offsets(const PfOffsetsArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(pf_offsets, dim3((a.B + 63) / 64), dim3(64), 0, s, a);
     return hipGetLastError();
 }

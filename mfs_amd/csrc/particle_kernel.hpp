@@ -4,12 +4,13 @@
 //
 // One measurement t is five launches on one stream (PfArgs, registry.hpp):
 //   propagate  x_i <- mu(x_i) + sqrt(var(x_i)) z_i (the model tables of MFS_TRANS_GAUSSIAN), w_i = p(y_t | x_i), and the
-//              block-local inclusive prefix sums of w: per thread over its kPfItems consecutive particles, a wave scan of the
-//              thread totals by shuffles, one LDS exchange of the four wave totals.  Block total -> wpart
+//              block-local inclusive prefix sums of w: per thread over its kPfItems consecutive particles, then the block scan
+//              (pf_weight_scan, particle_stream.hpp).  Block total -> wpart
 //   offsets    one thread per replicate adds the block totals in index order: woffs (exclusive), wtot, nell -= log(wtot / n),
-//              and the NaN rule: wtot zero or not finite -> first_nan, nell = NaN
-//   resample   target v_i = (i + u_i) / n; idx_i = the first j with woffs[j / kPfChunk] + wscan[j] >= v_i wtot (binary search,
-//              side left), clamped to [0, n - 1] whatever the sums hold; x'_i = x[idx_i].  Block total of x' -> xpart
+//              and the NaN rule: wtot zero or not finite -> first_nan, nell = NaN.  The kernel of every state dimension, with
+//              an argument struct of its own (PfOffsetsArgs)
+//   resample   x'_i = x[idx_i], idx_i the ancestor of particle i (pf_ancestor, particle_stream.hpp: target (i + u_i) / n wtot,
+//              binary search over woffs[j / kPfChunk] + wscan[j], clamped to [0, n - 1]).  Block total of x' -> xpart
 //   cf         per segment of kPfSeg particles: sum of (x' - mean)^2 and, for each frequency, of exp(i z_k x').  A thread owns F
 //              consecutive frequencies and walks the segment's particles (staged in LDS) in index order; on a uniform z grid it
 //              takes one true sincos per particle at its first frequency and rotates by exp(i dz x') for the other F - 1 <= 7
@@ -25,12 +26,12 @@
 
 #include "../../include/mfs_hip.h"
 #include "filter1d_kernel.hpp"   // likelihood(), horner(), finite()
-#include "particle_stream.hpp"   // philox4x32_10, pf_words, pf_uniform, pf_normal, pf_block_sum, pf_ordered_sum
-#include "registry.hpp"          // PfArgs, kPf*
+#include "particle_stream.hpp"   // the stream, the ordered sums, pf_weight_scan, pf_ancestor, pf_mixture_pick
+#include "registry.hpp"          // PfArgs, PfOffsetsArgs, kPf*
 
 namespace mfs {
 
-// (the stream and the ordered sums, shared with the d = 2 filter: particle_stream.hpp)
+// (the stream, the sums, the weight scan and the ancestor search, shared with the d = 2 filter: particle_stream.hpp)
 __global__ void __launch_bounds__(kPfThreads) pf_draws(const uint64_t seed, const int t, const int tag, const int draw,
                                                        const int count, double* __restrict__ out_u, double* __restrict__ out_z) {
     const int i = blockIdx.x * kPfThreads + threadIdx.x;
@@ -54,10 +55,7 @@ __global__ void __launch_bounds__(kPfThreads) pf_init(const PfArgs a) {
         if (a.n_mix > 0) {
             const double z = pf_normal(pf_words(seed, i, 0, 0, 0));
             const PfWords r = pf_words(seed, i, 0, 0, 1);
-            const double uc = pf_uniform(r.r0, r.r1);
-            int c = 0;
-            for (int k = 0; k < a.n_mix; ++k) c += (a.mix_cumw[k] <= uc) ? 1 : 0;
-            c = (c < a.n_mix - 1) ? c : a.n_mix - 1;
+            const int c = pf_mixture_pick(a.mix_cumw, a.n_mix, pf_uniform(r.r0, r.r1));
             x[i] = a.mix_mean[c] + sqrt(a.mix_var[c]) * z;
         } else {
             x[i] = a.init[(a.init_batched ? (size_t)b * a.n : 0) + i];
@@ -70,7 +68,7 @@ __global__ void __launch_bounds__(kPfThreads) pf_init(const PfArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kPfThreads) pf_propagate(const PfArgs a) {
     __shared__ double wave_tot[kPfThreads / 64];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = blockIdx.y, tid = threadIdx.x;
     const uint64_t seed = a.seeds[b];
     const int J1 = a.degree + 1;
     const double* coef = a.coef + (a.coef_batched ? (size_t)b * 2 * J1 : 0);
@@ -101,34 +99,13 @@ __global__ void __launch_bounds__(kPfThreads) pf_propagate(const PfArgs a) {
         run += w;
         pre[j] = run;
     }
-    // inclusive scan of the thread totals inside the wave, then the exclusive offset of this thread
-    double inc = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    double exc = __shfl_up(inc, 1, 64);
-    if (lane == 0) exc = 0.0;
-    if (lane == 63) wave_tot[wv] = inc;
-    __syncthreads();
-    double base = 0.0, total = 0.0;
-#pragma unroll
-    for (int q = 0; q < kPfThreads / 64; ++q) {
-        if (q == wv) base = total;
-        total += wave_tot[q];
-    }
-    base += exc;
-#pragma unroll
-    for (int j = 0; j < kPfItems; ++j)
-        if (i0 + j < a.n) ws[i0 + j] = base + pre[j];
-    if (tid == 0) a.wpart[(size_t)b * a.nblk + blockIdx.x] = total;
+    pf_weight_scan(pre, run, i0, a.n, ws, a.wpart + (size_t)b * a.nblk + blockIdx.x, wave_tot);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // block offsets, sum of the weights, NLL and the NaN rule.  One thread per replicate; grid ceil(B / 64), 64 threads
 // ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) pf_offsets(const PfArgs a) {
+__global__ void __launch_bounds__(64) pf_offsets(const PfOffsetsArgs a) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     const double* part = a.wpart + (size_t)b * a.nblk;
@@ -158,31 +135,13 @@ __global__ void __launch_bounds__(kPfThreads) pf_resample(const PfArgs a) {
     double* out = a.out_samples ? a.out_samples + ((size_t)b * a.T + a.t) * n : nullptr;
     const double tot = a.wtot[b];
     const bool ok = (tot > 0.0) && finite(tot);
-    double u_sys = 0.0;
-    if (a.resampling == MFS_RESAMPLE_SYSTEMATIC) {
-        const PfWords r = pf_words(seed, 0, a.t, 2, 0);
-        u_sys = pf_uniform(r.r0, r.r1);
-    }
+    const double u_sys = pf_systematic_uniform(a.resampling, seed, a.t);
     double part = 0.0;
 #pragma unroll
     for (int q = 0; q < kPfItems; ++q) {
         const int i = blockIdx.x * kPfChunk + q * kPfThreads + threadIdx.x;
         if (i >= n) continue;
-        double u = u_sys;
-        if (a.resampling != MFS_RESAMPLE_SYSTEMATIC) {
-            const PfWords r = pf_words(seed, i, a.t, 2, 0);
-            u = pf_uniform(r.r0, r.r1);
-        }
-        const double target = ((double)i + u) / (double)n * tot;
-        // the first j in [0, n) with cs[j] >= target, n if there is none; every probe is inside [0, n - 1], and a comparison
-        // with NaN sends the search right, so the result is clamped whatever the sums hold
-        int lo = 0, hi = n;
-        while (lo < hi) {
-            const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-            const double c = offs[mid / kPfChunk] + ws[mid];
-            if (c >= target) hi = mid; else lo = mid + 1;
-        }
-        const int idx = (lo < n - 1) ? lo : n - 1;
+        const int idx = pf_ancestor(a.resampling, seed, a.t, i, n, u_sys, tot, offs, ws);
         const double xn = ok ? x[idx] : __builtin_nan("");
         x2[i] = xn;
         if (out) out[i] = xn;

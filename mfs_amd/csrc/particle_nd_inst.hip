@@ -1,5 +1,5 @@
 // particle_nd_inst.hip -- the d = 2 bootstrap particle filter's kernels (particle_nd_kernel.hpp) and their launchers
-// (registry.hpp).  The `offsets` launch of a step is the 1-D filter's (particle_inst.hip).
+// (registry.hpp).  The `offsets` kernel of a step is the one in particle_inst.hip, which serves every state dimension.
 #include "particle_nd_kernel.hpp"
 
 namespace mfs {

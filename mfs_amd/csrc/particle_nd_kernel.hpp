@@ -8,14 +8,15 @@
 //   propagate  mu, S from the five polynomials of MFS_ND_TRANS_GAUSSIAN at (x_0, x_1) (the table, this replicate's if batched,
 //              staged in LDS); L the closed-form lower Cholesky factor of S; x'_0 = mu_0 + l_00 z_0, x'_1 = mu_1 + l_10 z_0 +
 //              l_11 z_1, both NaN if a pivot is negative or not finite; w_i = prod_f lik_f(y_t[ycol_f], x'_i[component_f]); and
-//              the block-local inclusive prefix sums of w exactly as the 1-D kernel takes them.  Block total -> wpart
-//   offsets    the 1-D kernel itself (pf_offsets, particle_kernel.hpp): woffs, wtot, nell -= log(wtot / n), the NaN rule
-//   resample   the 1-D targets, binary search, clamp and NaN handling; the one ancestor index gathers both components, and
-//              writes out_samples[b][t][i][0..1] as one 16-byte store.  Block totals of x'_0, x'_1 -> xpart
+//              the block-local inclusive prefix sums of w by the 1-D filter's scan (pf_weight_scan).  Block total -> wpart
+//   offsets    pf_offsets (particle_kernel.hpp), launched by the host with its own PfOffsetsArgs: woffs, wtot, nell -=
+//              log(wtot / n), the NaN rule
+//   resample   the 1-D filter's ancestor search (pf_ancestor) and NaN handling; the one ancestor index gathers both components,
+//              and writes out_samples[b][t][i][0..1] as one 16-byte store.  Block totals of x'_0, x'_1 -> xpart
 //   cov        per segment of kPfSeg particles: sums of d_0 d_0, d_0 d_1, d_1 d_1 with d = x' - mean -> cpart
 //   finalize   adds the block / segment totals in index order: out_means, out_covs (both off-diagonal entries)
 //
-// The stream is the 1-D filter's (particle_stream.hpp), counter = (particle, step, tag, draw): tag 0 draws 0, 1 the initial
+// The stream, the weight scan, the ancestor search and the mixture pick are the 1-D filter's (particle_stream.hpp).  Counter = (particle, step, tag, draw): tag 0 draws 0, 1 the initial
 // normals z_0, z_1 and draw 2 the component uniform; tag 1 draw k the propagation normal of component k; tag 2 draw 0 the
 // resampling uniform.  No atomics: every sum runs in an order fixed by n and the constants of registry.hpp.
 // The kernels of one translation unit (particle_nd_inst.hip).
@@ -26,7 +27,7 @@
 #include "../../include/mfs_hip.h"
 #include "filter1d_kernel.hpp"      // likelihood(), finite()
 #include "gaussfilter_kernel.hpp"   // gf_poly2(), gf_chol2()
-#include "particle_stream.hpp"      // pf_words, pf_uniform, pf_normal, pf_block_sum, pf_ordered_sum
+#include "particle_stream.hpp"      // the stream, the ordered sums, pf_weight_scan, pf_ancestor, pf_mixture_pick
 #include "registry.hpp"             // PfNdArgs, kPf*
 
 namespace mfs {
@@ -49,10 +50,7 @@ __global__ void __launch_bounds__(kPfThreads) pfnd_init(const PfNdArgs a) {
             const double z0 = pf_normal(pf_words(seed, i, 0, 0, 0));
             const double z1 = pf_normal(pf_words(seed, i, 0, 0, 1));
             const PfWords r = pf_words(seed, i, 0, 0, 2);
-            const double uc = pf_uniform(r.r0, r.r1);
-            int c = 0;
-            for (int k = 0; k < a.n_mix; ++k) c += (a.mix_cumw[k] <= uc) ? 1 : 0;
-            c = (c < a.n_mix - 1) ? c : a.n_mix - 1;
+            const int c = pf_mixture_pick(a.mix_cumw, a.n_mix, pf_uniform(r.r0, r.r1));
             const double* L = a.mix_chol + 4 * c;
             x0[i] = a.mix_mean[2 * c] + L[0] * z0;
             x1[i] = a.mix_mean[2 * c + 1] + L[2] * z0 + L[3] * z1;
@@ -70,7 +68,7 @@ __global__ void __launch_bounds__(kPfThreads) pfnd_init(const PfNdArgs a) {
 __global__ void __launch_bounds__(kPfThreads) pfnd_propagate(const PfNdArgs a) {
     __shared__ double s_coef[kPfNdCoefMax];
     __shared__ double wave_tot[kPfThreads / 64];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = a.n;
+    const int b = blockIdx.y, tid = threadIdx.x, n = a.n;
     const uint64_t seed = a.seeds[b];
     const int D = a.extent, DD = D * D;
     const double* coef = a.coef + (a.coef_batched ? (size_t)b * a.coef_stride : 0);
@@ -117,28 +115,7 @@ __global__ void __launch_bounds__(kPfThreads) pfnd_propagate(const PfNdArgs a) {
         run += w;
         pre[j] = run;
     }
-    // inclusive scan of the thread totals inside the wave, then the exclusive offset of this thread
-    double inc = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    double exc = __shfl_up(inc, 1, 64);
-    if (lane == 0) exc = 0.0;
-    if (lane == 63) wave_tot[wv] = inc;
-    __syncthreads();
-    double base = 0.0, total = 0.0;
-#pragma unroll
-    for (int q = 0; q < kPfThreads / 64; ++q) {
-        if (q == wv) base = total;
-        total += wave_tot[q];
-    }
-    base += exc;
-#pragma unroll
-    for (int j = 0; j < kPfItems; ++j)
-        if (i0 + j < n) ws[i0 + j] = base + pre[j];
-    if (tid == 0) a.wpart[(size_t)b * a.nblk + blockIdx.x] = total;
+    pf_weight_scan(pre, run, i0, n, ws, a.wpart + (size_t)b * a.nblk + blockIdx.x, wave_tot);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -157,31 +134,13 @@ __global__ void __launch_bounds__(kPfThreads) pfnd_resample(const PfNdArgs a) {
     double2* out = a.out_samples ? reinterpret_cast<double2*>(a.out_samples) + ((size_t)b * a.T + a.t) * n : nullptr;
     const double tot = a.wtot[b];
     const bool ok = (tot > 0.0) && finite(tot);
-    double u_sys = 0.0;
-    if (a.resampling == MFS_RESAMPLE_SYSTEMATIC) {
-        const PfWords r = pf_words(seed, 0, a.t, 2, 0);
-        u_sys = pf_uniform(r.r0, r.r1);
-    }
+    const double u_sys = pf_systematic_uniform(a.resampling, seed, a.t);
     double part0 = 0.0, part1 = 0.0;
 #pragma unroll
     for (int q = 0; q < kPfItems; ++q) {
         const int i = blockIdx.x * kPfChunk + q * kPfThreads + threadIdx.x;
         if (i >= n) continue;
-        double u = u_sys;
-        if (a.resampling != MFS_RESAMPLE_SYSTEMATIC) {
-            const PfWords r = pf_words(seed, i, a.t, 2, 0);
-            u = pf_uniform(r.r0, r.r1);
-        }
-        const double target = ((double)i + u) / (double)n * tot;
-        // the first j in [0, n) with cs[j] >= target, n if there is none; every probe is inside [0, n - 1], and a comparison
-        // with NaN sends the search right, so the result is clamped whatever the sums hold
-        int lo = 0, hi = n;
-        while (lo < hi) {
-            const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-            const double c = offs[mid / kPfChunk] + ws[mid];
-            if (c >= target) hi = mid; else lo = mid + 1;
-        }
-        const int idx = (lo < n - 1) ? lo : n - 1;
+        const int idx = pf_ancestor(a.resampling, seed, a.t, i, n, u_sys, tot, offs, ws);
         const double n0 = ok ? x0[idx] : __builtin_nan(""), n1 = ok ? x1[idx] : __builtin_nan("");
         y0[i] = n0;
         y1[i] = n1;

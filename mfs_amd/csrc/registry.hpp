@@ -179,20 +179,27 @@ struct PfArgs {
     double* out_means;       // [B][T]
     double* out_vars;        // [B][T]
     double* out_cfs;         // [B][T][nz][2] or null
+};
+// what the `offsets` kernel reads and writes: the same kernel for every state dimension
+struct PfOffsetsArgs {
+    int n, B, t, nblk;       // particles, replicates, the step this launch works on, pf_blocks(n)
+    double* wpart;           // [B][nblk] block totals of the weights (read)
+    double* woffs;           // [B][nblk] their exclusive prefix sums in index order
+    double* wtot;            // [B] sum of the weights
     double* nell;            // [B], accumulated over the steps
     int32_t* first_nan;      // [B], -1 until a step's weight sum is zero or not finite
 };
 hipError_t launch_pf_init(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_propagate(const PfArgs& a, hipStream_t s);
-hipError_t launch_pf_offsets(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf_offsets(const PfOffsetsArgs& a, hipStream_t s);
 hipError_t launch_pf_resample(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_cf(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_finalize(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* d_uniform, double* d_normal, hipStream_t s);
 
 // ---- bootstrap particle filter, d = 2 (particle_nd_inst.hip).  The same five launches per measurement, the same constants
-// and the 1-D `offsets` kernel itself (through a PfArgs that names the weight buffers); the particles are [B][2][n],
-// component-major, so every particle pass is coalesced.
+// and the same `offsets` kernel (launch_pf_offsets with a PfOffsetsArgs); the particles are [B][2][n], component-major, so
+// every particle pass is coalesced.
 struct PfNdArgs {
     int n, T, B, t;          // particles, steps, replicates, the step this launch works on
     int nblk, nseg;          // pf_blocks(n), pf_segments(n)

@@ -23,7 +23,9 @@ from mfs_amd.classical_filters_smoothers.gfs import GaussianTransitionND
 from mfs_amd.multi_dims import ss_models
 from mfs_amd.multi_dims.filtering import _model_struct, _trace_likelihood
 from mfs_amd.tme_poly_nd import BatchedTablesND, GaussianTablesND
+from tests import brute_force_ref as R
 from tests import particle_filter_nd_ref as P
+from tests import test_gpu_particle_filter as pf1d      # the 1-D filter's linear model, for the test of the shared step driver
 
 pytestmark = pytest.mark.gpu
 
@@ -246,6 +248,47 @@ def test_negative_pivot_poisons_one_replicate_only():
                            return_summaries=True)
     assert list(res.first_nan) == [-1, -1, 0]
     _assert_poisoned(res, clean, 2, 0, B)
+
+
+# ---- the per-kernel timing switch: both entries run their steps through one driver on the host
+def _last_split_ms():
+    out = (C.c_double * 5)()
+    _lib.check(_lib.lib().mfs_pf_last_split_ms(out))
+    return np.array(out)
+
+
+@pytest.mark.parametrize('d', [1, 2])
+def test_split_timing_switch_leaves_the_results_alone(d, monkeypatch):
+    """MFS_PF_SPLIT is read at every call: with it the same bits and five kernel times, without it five zeros.  One full
+    block and a ragged one, one segment."""
+    n, B, T = 1500, 2, 3
+    seeds = np.array([1, 2], dtype=np.uint64)
+    if d == 1:
+        trans, init = pf1d._sweep_model()
+        ys = np.stack([R.ou_data(T, np.random.default_rng(b), pf1d.SWEEP_DT) for b in range(B)])
+        pdf = pf1d._gauss_pdf
+    else:
+        trans, init, F, Q = _lin_model()
+        ys = np.stack([P.lin_data(T, np.random.default_rng(b), F, Q) for b in range(B)])
+        pdf = P.lin_pdf
+
+    def run():
+        res = bootstrap_filter(trans, pdf, ys, init, seeds, n, stratified, return_summaries=True)
+        return [v for v in res if v is not None]
+
+    monkeypatch.delenv('MFS_PF_SPLIT', raising=False)
+    plain = run()
+    assert len(plain) == 5 and plain[0].shape[:3] == (B, T, n) and np.isfinite(plain[-2]).all()
+    monkeypatch.setenv('MFS_PF_SPLIT', '1')
+    timed = run()
+    ms = _last_split_ms()
+    for a, b in zip(plain, timed):
+        assert np.array_equal(a, b), 'the timing switch changed a result'
+    assert ms.shape == (5,) and np.isfinite(ms).all() and (ms >= 0.).all() and ms.sum() > 0., ms
+    monkeypatch.setenv('MFS_PF_SPLIT', '0')
+    for a, b in zip(plain, run()):
+        assert np.array_equal(a, b)
+    assert (_last_split_ms() == 0.).all()
 
 
 # ---- error codes of the C entry
