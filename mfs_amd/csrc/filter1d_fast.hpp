@@ -538,7 +538,8 @@ __device__ __forceinline__ double twisted_weight(const double (&a)[N], const dou
 //     (one v_alignbit per step; floating-point compares would bounce through SGPR masks next to the chain) and the changes are
 //     counted at the end.  p_0 = 1 > 0 is the zero bit above the first one.
 //   * The step logic is straight-line and predicated (bitwise, not short-circuit, logic: no divergent branches); a converged
-//     lane is frozen by the selects at the end.
+//     lane is frozen by the selects at the end.  KEEP (a compile-time constant) = the selects on lo, hi and prev_step as well as
+//     those on x and conv; false only where the caller reads nothing but x after the loop (kSlFreezeX).
 //   * S = sqrt((N-1) ((N-1) p'^2 - N p p'')) >= 0 for real-rooted p (clamped against rounding).  The step only has to be
 //     accurate enough to converge: seeds + one Newton step instead of full-precision sqrt / divide; the accuracy of the root
 //     comes from the recurrence evaluation.
@@ -560,7 +561,7 @@ __device__ __forceinline__ double twisted_weight(const double (&a)[N], const dou
 #else
 #define F1_COUNT_EVAL do {} while (0)
 #endif
-#define MFS_LAGUERRE_EVAL                                                                                             \
+#define MFS_LAGUERRE_EVAL(KEEP)                                                                                        \
                 F1_COUNT_EVAL;                                                                                        \
                 double p0 = 1.0, p1 = a[0] - x, d0 = 0.0, d1 = -1.0, e0 = 0.0, e1 = 0.0;                              \
                 unsigned signs = (unsigned)__double2hiint(p1) >> 31;                                                  \
@@ -604,9 +605,15 @@ __device__ __forceinline__ double twisted_weight(const double (&a)[N], const dou
                         conv_n = (ok & (step <= tol)) | (ok & (step <= kLagStop * wacc) & (step <= 1e-2 * prev_step)) |\
                                  near | (hi_n - lo_n <= tol) | ((p1 == 0.0) & (right | left));                        \
                     }                                                                                                 \
-                    lo = conv ? lo : lo_n;                                                                            \
-                    hi = conv ? hi : hi_n;                                                                            \
-                    prev_step = conv ? prev_step : (ok ? step : 0.0);                                                 \
+                    if constexpr (KEEP) {                                                                             \
+                        lo = conv ? lo : lo_n;                                                                        \
+                        hi = conv ? hi : hi_n;                                                                        \
+                        prev_step = conv ? prev_step : (ok ? step : 0.0);                                             \
+                    } else {                                                                                          \
+                        lo = lo_n;                                                                                    \
+                        hi = hi_n;                                                                                    \
+                        prev_step = ok ? step : 0.0;                                                                  \
+                    }                                                                                                 \
                     x = conv ? x : xn;                                                                                \
                     conv = conv | conv_n;                                                                             \
                 }                                                                                                     \
@@ -617,6 +624,9 @@ __device__ __forceinline__ double twisted_weight(const double (&a)[N], const dou
 // SL = what a specialised one-wave build of the filter kernel asks for in its update half (kSl* below; 0 = the code every
 // other caller gets).
 constexpr int kSlEigLoop = 1;   // first Laguerre evaluation straight-line, then a loop with a wave-uniform exit
+// the two bits below are set by the partner-wave variant only (filter1d_partner.hpp), each behind its own leave-one-out switch
+constexpr int kSlFreezeX = 2;   // with kSlEigLoop: the loop passes freeze only x (and conv) of a converged lane
+constexpr int kSlPivMin = 4;    // G = 16: the poison flag from a running minimum of the pivots, see the elimination
 template <int N, int G, bool EXT = false, int SL = 0>
 __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, const int l, const int grp,
                                                 const double mean, const double scale, double& x_out, double& w_out,
@@ -646,6 +656,15 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
     // (lane j < 16 from the first copy, else from the second), instead of two ds_swizzle round trips per term.
     double piv[N], sub[N], ipiv[N];  // group-uniform
     bool poisoned = false;
+    // kSlPivMin: `poisoned` = "some pivot is not > 0" without a compare and a scalar OR per pivot.  pmin is the minimum of the
+    // pivots 0 .. N - 2 (v_min_f64 drops a NaN operand, so pmin is the minimum of those that are numbers), and the flag is
+    // !(pmin > 0) | !(p_{N-1} > 0).  Pivot by pivot, for k < N - 1: p_k < 0, +-0 or -inf makes pmin <= 0, flagged either way.
+    // p_k = NaN: y0 = rcp(NaN) = NaN, so the factor u / d is NaN in every lane and every later column takes a NaN term in every
+    // lane -- p_{N-1} is NaN and its own compare flags it, whether or not the minimum kept the NaN.  p_k = +inf is > 0 and raises
+    // no flag by itself in either form, but rcp(inf) = 0 and the Newton step 0 * inf is NaN: every later column is NaN again and
+    // p_{N-1} flags it, as p_{k+1} = NaN does in the compare-per-pivot form.  k = N - 1 has its own compare in both forms, so
+    // an infinite last pivot is > 0 in both.  A filter flagged in one form is flagged in the other; no value changes.
+    double pmin = 0.0;
     if constexpr (G == 16 || G == 8) {
         // right-looking order: as soon as column k is final every later column takes its term.  Each column is one
         // accumulator (its updates arrive a whole column apart, so no dependent-issue stall and no partial sums to add),
@@ -658,7 +677,13 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
             const double pj = bcast<G, k>(s);
             piv[k] = pj;
             sub[k] = bcast<G, k + 1>(s);
-            poisoned |= !(pj > 0.0);
+            if constexpr (G == 16 && (SL & kSlPivMin) != 0 && N >= 2) {
+                if constexpr (k == 0) pmin = pj;
+                else if constexpr (k < N - 1) pmin = vmin_f64(pmin, pj);
+                else poisoned = !(pmin > 0.0) | !(pj > 0.0);
+            } else {
+                poisoned |= !(pj > 0.0);
+            }
             // 1 / pivot: hardware v_rcp_f64 seed + two Newton-Raphson steps -> ~1e-16; the second step is folded into
             // the consumers (y1 (1 + delta) with delta = 1 - pivot y1) so that s * y1 and delta form side by side
             const double y0 = __builtin_amdgcn_rcp(pj);
@@ -878,14 +903,17 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
                 // its freeze selects fold away.  Then a loop whose exit is wave-uniform -- one ballot and a scalar branch,
                 // no EXEC-masked loop: a pass costs the wave the same with one group in it as with four, so a group that
                 // has converged rides along with conv == true and every select keeps its x, lo, hi and prev_step.
-                MFS_LAGUERRE_EVAL;
+                // kSlFreezeX: of a lane that rides along only x is kept.  Its lo, hi and prev_step are read by nothing but its own
+                // next evaluation, whose x and conv the selects on x and conv hold: the lane re-evaluates at an unchanged x, its
+                // bracket only tightens around that x, and lam = x is all that leaves the loop.
+                MFS_LAGUERRE_EVAL(true);
                 for (int it = 1; it < kMaxEigIters; ++it) {
                     if (__builtin_amdgcn_ballot_w64(!conv) == 0ull) break;
-                    MFS_LAGUERRE_EVAL;
+                    MFS_LAGUERRE_EVAL((SL & kSlFreezeX) == 0);
                 }
             } else {
             for (int it = 0; it < kMaxEigIters; ++it) {
-                MFS_LAGUERRE_EVAL;
+                MFS_LAGUERRE_EVAL(true);
                 if (gall<G>(conv, grp)) break;
             }
             }

@@ -12,17 +12,27 @@
 //     the workgroups it checked and those where it did not hold (g_partner_placement).  Nothing but speed depends on the placement.
 //   * Step t, main wave: predict half from the atoms (no elimination), update half up to wl, p_y, 1 / p_y, mean, dx.  It
 //     writes dx, wl, 1 / p_y, p_y per lane and its own bad bit (predicted moments, mean) into exchange slot t & 1, executes
-//     the step's barrier, reads the partner's flags of round t - 1 and stores the mean.
+//     the step's barrier and issues the read of the partner's flags of round t - 1.  It does not wait for that word there:
+//     it keeps the mean of step t in a register, starts step t + 1 with `dead` as it was, and acts on the word -- update
+//     `dead`, poison mean and scale, store the mean of step t, NaN if flagged -- behind the column sums of the predict half of
+//     step t + 1, the first place of a step that waits for LDS anyway (after the loop for the last step, before the carry).
 //   * Round t, partner wave, after barrier t: reads slot t & 1, forms wl dx^n, reduces, multiplies by 1 / p_y, stores the
 //     step's moments, accumulates nell, runs the pivots-only elimination on the posterior moments and publishes two bits per
 //     filter in flag slot t & 1: "dead after step t" (a moment, the mean or nell of step t was not finite, or the filter was
 //     dead before) and "a pivot of the posterior Hankel matrix of step t was not > 0".
-//   * The main wave therefore runs at most one step ahead of the flag that governs it: it reads the flags of round t - 1
-//     after barrier t, before it stores anything of step t.  Either bit makes the mean of step t NaN and the filter dead, which
-//     is what the NaN propagation through the predict half does in the one-wave builds; the partner, which computed the bits,
-//     NaN-fills the moments and nell of step t and sets first_nan (pivot bit: t; dead bit: already set at t - 1).
+//   * The main wave therefore runs at most one step and one predict half ahead of the flag that governs it: it reads the
+//     flags of round t - 1 after barrier t and acts on them before it stores anything of step t and before it writes the
+//     exchange slot or its bad bit of step t + 1.  Either bit makes the mean of step t NaN and the filter dead, which is what
+//     the NaN propagation through the predict half does in the one-wave builds; the partner, which computed the bits,
+//     NaN-fills the moments and nell of step t and sets first_nan (pivot bit: t; dead bit: already set at t - 1).  A filter
+//     flagged in round t - 1 has by then run the predict half of step t + 1 into its own tile and registers that are
+//     overwritten with NaN; it never enters the update half (the eigenvalue loop sees no such filter), hands nothing over
+//     and stores nothing but NaN means.
 //   * Both slots are double buffers: a slot written before barrier t is read between barriers t and t + 1 and written again
-//     only after barrier t + 1.
+//     only after barrier t + 1.  The late flag keeps that: the word of round t - 1 is written before barrier t; the main
+//     wave's read of it is ISSUED right after barrier t, as before, and LDS serves a wave's accesses in order, so the access
+//     happens before everything the main wave does in step t + 1 and has completed by the `s_waitcnt lgkmcnt(0)` of barrier
+//     t + 1 at the latest; the partner writes that word again only after barrier t + 1.  Only the wait for the register moved.
 //
 // BARRIERS.  Every wave of the workgroup executes two barriers in the prologue and exactly one per time step: the two role
 // bodies below each contain a single `for (t = a.t_begin; t < a.t_end; ++t)` loop without break, continue or return, with
@@ -31,7 +41,8 @@
 //
 // Every floating-point operation that feeds an output is the one-wave build's, in its order: the statements of the two halves
 // are those of filter1d_fast_kernel for a fixed-traits build, split between the roles, and quadrature_fast is called as it is
-// there (the partner's call keeps only the pivots, as the predict half of the one-wave builds does).
+// there (the partner's call keeps only the pivots, as the predict half of the one-wave builds does); the SL bits this variant
+// adds to its calls (kSlFreezeX, kSlPivMin) drop selects and compares whose results nothing reads, no arithmetic.
 // First step of a run (no atoms): the main wave runs the cold full rule on the moments it loads, as the one-wave builds do.
 // Start of a chunk: the partner eliminates the carried moments before the first barrier (the flag of step t_begin).
 // MFS_PREDICT_RULE=recompute keeps the one-wave launcher (capi.hip).
@@ -44,6 +55,19 @@ namespace mfs {
 // the main wave.  (No s_setprio for the main waves: it measured slower.  Both measurements: DESIGN.md section 6.)
 #ifndef MFS_PARTNER_AB_LOGPY
 #define MFS_PARTNER_AB_LOGPY 0
+#endif
+// the step-boundary changes of the main wave, one switch each (0 = the shipped code, 1 = the code it replaced):
+//   MFS_PARTNER_AB_FLAGLATE   the partner's flags are consumed inside the next step (1: waited for right behind the barrier)
+//   MFS_PARTNER_AB_FREEZE     the eigenvalue loop freezes only x of a converged lane (1: lo, hi and prev_step as well)
+//   MFS_PARTNER_AB_PIVMIN     the poison flag from a running minimum of the pivots (1: one compare per pivot)
+#ifndef MFS_PARTNER_AB_FLAGLATE
+#define MFS_PARTNER_AB_FLAGLATE 0
+#endif
+#ifndef MFS_PARTNER_AB_FREEZE
+#define MFS_PARTNER_AB_FREEZE 0
+#endif
+#ifndef MFS_PARTNER_AB_PIVMIN
+#define MFS_PARTNER_AB_PIVMIN 0
 #endif
 
 constexpr int kPartnerMainWaves = 4;                       // main waves per workgroup = SIMDs per compute unit
@@ -83,6 +107,8 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
     constexpr int M2 = L::M2, TLD = L::TLD;
     constexpr int FPW = 64 / G, FPB = kPartnerMainWaves * FPW;
     constexpr bool kLogMain = (MFS_PARTNER_AB_LOGPY != 0);
+    constexpr bool kFlagLate = (MFS_PARTNER_AB_FLAGLATE == 0);
+    constexpr int kSlPivots = (MFS_PARTNER_AB_PIVMIN == 0) ? kSlPivMin : 0;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     // (the wave number as a scalar: the split into roles is a scalar branch, and a wave never walks through the other role's
     //  loop -- and its barriers -- with an empty EXEC mask)
@@ -178,8 +204,22 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
         bool dead = !has || (first_nan >= 0);
         asm volatile("" : "+v"(mean), "+v"(scale), "+v"(nell), "+v"(gA), "+v"(gW), "+v"(first_nan));   // the carry waits, in front of the loop
         double ywin = 0.0;
-        constexpr int kSlUpdate = kSlEigLoop;
+        constexpr int kSlUpdate = kSlEigLoop | ((MFS_PARTNER_AB_FREEZE == 0) ? kSlFreezeX : 0) | kSlPivots;
         constexpr int trans_kind = (SPEC > 0) ? MFS_TRANS_OPERATOR : MFS_TRANS_GAUSSIAN;
+        // the late flag (kFlagLate): the flag word read behind barrier t and the mean of step t, both settled inside step t + 1
+        int fl_prev = 0;
+        double mean_prev = 0.0, nell_next = nell;
+        const auto settle = [&]() __attribute__((always_inline)) {
+            if (dead || fl_prev != 0) {
+                dead = true;
+                mean = qnan; scale = qnan; mean_prev = qnan;
+                if constexpr (kLogMain) nell = qnan;
+            } else {
+                if constexpr (kLogMain) nell = nell_next;
+            }
+            if (st_mean) a.out_mean[o_mean] = mean_prev;
+            o_mean += 1;
+        };
 
         for (int t = a.t_begin; t < a.t_end; ++t) {
             constexpr int YW = 16;
@@ -190,10 +230,10 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
             }
             const double y = __shfl(ywin, tw, YW);
             double* xs = xch + (t & 1) * 4 * G;
-            double nell_next = nell;
+            if constexpr (!kFlagLate) nell_next = nell;
+            int bad = 0;
+            double gB = qnan;
             if (!dead) {
-                int bad = 0;
-                double gB = qnan;
                 // ---- predict half (filter1d_fast_kernel, half 0)
                 auto predict = [&](const auto atoms_ok) __attribute__((always_inline)) {
                     double x, w;
@@ -265,6 +305,14 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
                 };
                 if (have_atoms) predict(std::true_type{});
                 else predict(std::false_type{});   // the first step of a run
+            }
+            // The flags of round t - 1 and the mean of step t - 1.  The column sums above are the first thing of a step that
+            // waits for LDS (the table writes before them only issue), so the flag word, read behind the barrier before any of
+            // that, has arrived and this costs no wait of its own; a wait placed earlier would stand behind the table writes,
+            // because the LDS counter only counts down in order.  Nothing of step t has been handed over or stored yet: a filter
+            // that turns out dead here has computed one predict half for nothing, into its own tile, and stops.
+            if constexpr (kFlagLate) { if (t > a.t_begin) settle(); }
+            if (!dead) {
                 {   // ---- update half (half 1) up to the atoms
                     double x, w;
                     double lam_io = gB;
@@ -300,18 +348,13 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
                 }
             }
             partner_barrier();
-            // the partner's flags of round t - 1 (the opening of a launch for t = t_begin), before any store of step t
-            const int fl = flags[(t + 1) & 1];
-            if (dead || fl != 0) {
-                dead = true;
-                mean = qnan; scale = qnan;
-                if constexpr (kLogMain) nell = qnan;
-            } else {
-                if constexpr (kLogMain) nell = nell_next;
-            }
-            if (st_mean) a.out_mean[o_mean] = mean;
-            o_mean += 1;
+            // the partner's flags of round t - 1 (the opening of a launch for t = t_begin): read here, before the partner can
+            // write the word again, and -- kFlagLate -- waited for and acted on inside step t + 1, or behind the loop
+            fl_prev = flags[(t + 1) & 1];
+            mean_prev = mean;
+            if constexpr (!kFlagLate) settle();
         }
+        if constexpr (kFlagLate) { if (a.t_end > a.t_begin) settle(); }   // the last step's mean, before the carry is written
         if (has) {
             if (a.t_end >= a.T) {
                 if constexpr (kLogMain) { if (l == 0) a.out_nell[b] = nell; }
@@ -341,7 +384,7 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
         wave_sync();
         bool dead = !has || (first_nan >= 0);
         if (!dead && a.t_begin != 0)   // the flag of step t_begin: the elimination the one-wave builds run in its predict half
-            pivot_prev = quadrature_fast<N, G, false>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
+            pivot_prev = quadrature_fast<N, G, false, kSlPivots>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
         flags[(a.t_begin + 1) & 1] = (dead ? kPartnerFlagDead : 0) | (pivot_prev ? kPartnerFlagPivot : 0);
         const bool st_m0 = has && a.out_mom && l < M2, st_m1 = has && a.out_mom && l + G < M2;
         size_t o_mom = ((size_t)b * a.T + a.t_begin) * M2 + l;
@@ -387,7 +430,7 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
                 if constexpr (!kLogMain) bad |= (int)!finite(nell);
                 if (gany<G>(bad != 0, grp)) { dead = true; first_nan = t; }
                 // the poison decision of the next predict half (a dead filter's flag already says everything)
-                pivot_prev = quadrature_fast<N, G, false>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
+                pivot_prev = quadrature_fast<N, G, false, kSlPivots>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
             } else {
                 if (!dead) first_nan = t;   // the pivot flag of the step before: this step is NaN throughout
                 dead = true;
