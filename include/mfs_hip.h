@@ -222,7 +222,7 @@ int mfs_partner_placement(uint64_t* workgroups, uint64_t* mismatches);
  *   model       the value tables, as for mfs_filter_1d (coef_batched / lik_batched: one parameter point per replicate)
  *   dcoef       d coef / d theta_p: [n_par][n_rows][degree + 1], or [B][n_par][n_rows][degree + 1] when coef_batched
  *   dlik        d lik / d theta_p:  [n_par][n_lik], or [B][n_par][n_lik] when lik_batched
- *   n_par       1 .. 4;  N  2 .. 10;  m0, mean0, scale0, ys as for mfs_filter_1d (the initial law does not depend on theta)
+ *   n_par       1 .. 4;  N  2 .. 16;  m0, mean0, scale0, ys as for mfs_filter_1d (the initial law does not depend on theta)
  *   out_nell    [B];  out_grad [B][n_par] = d nell / d theta_p;  out_first_nan [B] or NULL.  Host pointers.
  * A replicate that NaN-poisons returns NaN in both, as the reference's objective would.
  */

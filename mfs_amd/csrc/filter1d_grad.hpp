@@ -20,8 +20,10 @@
 // Prediction and update are the filter's own sums with dual nodes, weights and model tables (value tables + tangent tables
 // d coef / d theta_p supplied by the host tracer); exp / log / tanh / sqrt carry their derivatives.
 //
-// Mapping: one filter per 16-lane group (N <= 15), lane = node; group sums by shuffles.  This kernel serves optimiser
-// loops (a few to a few thousand filters per launch), not the throughput benchmark.
+// Mapping: one filter per lane group, lane = node; group sums by shuffles.  The group is 8 lanes for N <= 8 (eight filters per
+// wave, the Chebyshev algorithm in registers) and 16 lanes for 9 <= N <= 16 (four per wave, the algorithm in LDS; at N = 16
+// every lane of the group owns a root).  Instantiated for N = 2..16, P = 1..4 (filter1d_grad_inst.hip).  This kernel serves
+// optimiser loops (a few to a few thousand filters per launch), not the throughput benchmark.
 #pragma once
 #include "filter1d_kernel.hpp"
 #include "filter1d_fast.hpp"     // static_for

@@ -47,8 +47,10 @@ def test_well_poisson_gradient_matches_differences_of_the_plain_filter():
     # one parameter point per replicate in the same launch: the rows of a multi-start / grid evaluation
     thetas = np.array([[2.2, 2.7], [3.0, 3.0], [1.5, 4.0]])
     nell_r, grad_r = estimation.nell_and_grad_forward(model, thetas, ic.cms, ic.mean, ys)
-    npt.assert_allclose(nell_r[0], nell[0], rtol=1e-13)
-    npt.assert_allclose(grad_r[0], grad[0], rtol=1e-10)
+    # (bit for bit: the traced tables of row 0 are the same numbers, and a replicate's result depends neither on its batch nor
+    #  on whether its tables arrive shared or per replicate -- tests/test_gpu_gradient_envelope.py, geometry and bit equality)
+    npt.assert_array_equal(nell_r[0], nell[0])
+    npt.assert_array_equal(grad_r[0], grad[0])
     n1, g1 = estimation.nell_and_grad_forward(model, thetas[2], ic.cms, ic.mean, ys[2])
     npt.assert_allclose(nell_r[2], n1, rtol=1e-13)
     npt.assert_allclose(grad_r[2], g1, rtol=1e-10)
