@@ -962,13 +962,10 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
 // two halves of a step as two straight-line bodies, each compiled for its half: with the posterior-atoms rule the predict
 // half's elimination keeps only what the poison decision needs (the pivots; no sub-diagonal broadcasts, no pivot
 // reciprocals for the Jacobi matrix).  The arithmetic that feeds an output is the generic build's, operation for operation.
-// (A/B switches of the specialised builds, each measured against the full specialisation on the headline:
-//  MFS_SPEC_AB_TABLE 0 = the table in registers, 1 = the LDS Horner pass; MFS_SPEC_AB_HALVES 0 = two straight-line halves,
-//  1 = the run-time loop over the halves.  DESIGN.md section 6.  The dead rows need no switch: with the number of terms a
-//  compile-time constant the compiler drops their loads and multiply-adds on either table route.)
-// A specialised build also (iii) takes the divergent break out of the update half's eigenvalue iteration:
-//  MFS_SPEC_AB_EIGLOOP 0 = the first Laguerre evaluation straight-line and the rest in a loop whose exit is wave-uniform
-//  (quadrature_fast, kSlEigLoop), 1 = the loop every group leaves on its own.  DESIGN.md sections 3.1 and 6.
+// (With the number of terms a compile-time constant the compiler drops the dead rows' loads and multiply-adds.)
+// A specialised build also (iii) takes the divergent break out of the update half's eigenvalue iteration: the first Laguerre
+// evaluation straight-line and the rest in a loop whose exit is wave-uniform (quadrature_fast, kSlEigLoop).
+// DESIGN.md sections 3.1 and 6.
 // TR = the step traits of a specialised build: the model switches the time loop would otherwise test at every step -- moment
 // mode, u-map, likelihood law -- as compile-time constants (StepTraits<MODE, UMAP, LIK>; the default StepTraits<> leaves all
 // three run-time values of Filter1dArgs and compiles to the code without the parameter).  A fixed-traits build (i) emits one
@@ -977,56 +974,171 @@ __device__ __forceinline__ bool quadrature_fast(const double* __restrict__ mom, 
 // per-lane predicates and running pointers instead of a test of each output pointer at each step.  The plan picks such a
 // build for the combinations the shipped one-wave models reach (registry.hpp, kTraitSets).  Same rule as SPEC: no
 // floating-point operation that feeds an output changes.
-// (A/B switches, each against the full fixed-traits build: MFS_TRAITS_AB_SWITCHES 1 = mode / u-map / law stay run-time
-//  values, MFS_TRAITS_AB_LIKREGS 1 = the likelihood parameters stay in LDS, MFS_TRAITS_AB_CARRYWAIT 1 = the waits for the carry loads stay at their
-//  first uses inside the loop, MFS_TRAITS_AB_OUTPUTS 1 = the per-step tests of
-//  the output pointers.  DESIGN.md section 6.)
-#ifndef MFS_SPEC_AB_TABLE
-#define MFS_SPEC_AB_TABLE 0
-#endif
-#ifndef MFS_SPEC_AB_HALVES
-#define MFS_SPEC_AB_HALVES 0
-#endif
-#ifndef MFS_SPEC_AB_EIGLOOP
-#define MFS_SPEC_AB_EIGLOOP 0
-#endif
-#ifndef MFS_TRAITS_AB_SWITCHES
-#define MFS_TRAITS_AB_SWITCHES 0
-#endif
-#ifndef MFS_TRAITS_AB_LIKREGS
-#define MFS_TRAITS_AB_LIKREGS 0
-#endif
-#ifndef MFS_TRAITS_AB_OUTPUTS
-#define MFS_TRAITS_AB_OUTPUTS 0
-#endif
-#ifndef MFS_TRAITS_AB_CARRYWAIT
-#define MFS_TRAITS_AB_CARRYWAIT 0
-#endif
+// (Each part of SPEC and TR was decided by a leave-one-out build -- compile-time switches MFS_SPEC_AB_* and MFS_TRAITS_AB_*
+//  that existed up to commit ac4d42d; the series recorded in DESIGN.md section 6 were taken with them.)
 template <int MODE = -1, int UMAP = -1, int LIK = -1>
 struct StepTraits {
     static_assert((MODE < 0) == (UMAP < 0) && (MODE < 0) == (LIK < 0), "all three fixed, or all three run-time");
     static constexpr bool fixed = MODE >= 0;
     static constexpr int mode = MODE, umap = UMAP, lik = LIK;
 };
+// ---- the blocks of a filter step, shared by filter1d_fast_kernel and filter1d_partner_kernel (filter1d_partner.hpp), which
+// must stay bit-equal.  Each takes values and tile pointers, contains no barrier, no early exit and no LDS access outside
+// the pointers it is given; the order of the floating-point operations in them is part of the contract.
+
+// live rows of a specialised build's table: the operator terms + the variance row (LDS row MFS_MAX_TERMS), or mean and variance
+template <int SPEC>
+struct SpecRows {
+    static constexpr int SR = (SPEC > 0) ? SPEC + 1 : 2;
+    static constexpr int kVarReg = (SPEC > 0) ? SPEC : -1;     // the register row that holds LDS row MFS_MAX_TERMS
+};
+
+template <int SPEC>
+__device__ __forceinline__ void load_table_regs(const double* coef, double (&tabr)[kSpecTop][SpecRows<SPEC>::SR]) {
+#pragma unroll
+    for (int q = 0; q < kSpecTop; ++q)
+#pragma unroll
+        for (int r = 0; r < SpecRows<SPEC>::SR; ++r)
+            tabr[q][r] = coef[q * kCoefRows + ((r == SpecRows<SPEC>::kVarReg) ? MFS_MAX_TERMS : r)];
+}
+
+__device__ __forceinline__ void load_lik_regs(const double* lp, LikRegs& lpr) {
+#pragma unroll
+    for (int e = 0; e < MFS_MAX_LIK; ++e) lpr.v[e] = lp[e];
+}
+
+// every live row of the register table at u, scattered into the rows of the LDS table's layout
+template <int SPEC>
+__device__ __forceinline__ void table_rows(const double (&tabr)[kSpecTop][SpecRows<SPEC>::SR], const double u,
+                                           double (&rows)[MFS_MAX_TERMS + 1]) {
+    constexpr int SR = SpecRows<SPEC>::SR;
+    double live[SR];
+    horner_regs<kSpecTop, SR>(tabr, u, live);
+#pragma unroll
+    for (int r = 0; r <= MFS_MAX_TERMS; ++r) rows[r] = 0.0;
+#pragma unroll
+    for (int r = 0; r < SR; ++r) rows[(r == SpecRows<SPEC>::kVarReg) ? MFS_MAX_TERMS : r] = live[r];
+}
+
+// conditional mean and variance of the transition at this lane's node
+__device__ __forceinline__ void transition_mu_var(const int trans_kind, const double mean_x_coef, const double x,
+                                                  const double (&rows)[MFS_MAX_TERMS + 1], double& mu, double& var) {
+    if (trans_kind == MFS_TRANS_OPERATOR) {
+        mu = x + rows[0];
+        var = rows[MFS_MAX_TERMS];
+    } else {
+        mu = fma(mean_x_coef, x, rows[0]);
+        var = rows[1];
+    }
+}
+
+// normal closure: E_0 = 1, E_1 = m, E_n = m E_{n-1} + (n-1) v E_{n-2}   (moments.py:70-74), run on
+// F_n = w E_n / s^n directly: F_n = (m/s) F_{n-1} + (n-1) (v/s^2) F_{n-2}, F_0 = w
+template <int M2>
+__device__ __forceinline__ void normal_closure_row(const double w, const double mu, const double var, const double c,
+                                                   const double inv_sc, double* row) {
+    const double ms = (mu - c) * inv_sc, vs = var * inv_sc * inv_sc;
+    double f2 = w, f1 = w * ms, vn = vs;
+    row[0] = f2;
+    row[1] = f1;
+#pragma unroll
+    for (int n = 2; n < M2; ++n) {
+        const double f = fma(ms, f1, vn * f2);
+        row[n] = f;
+        vn += vs;
+        f2 = f1;
+        f1 = f;
+    }
+}
+
+// wl dx^n in four interleaved chains (a dependent multiply costs several issue slots)
+template <int M2, bool EXT>
+__device__ __forceinline__ void power_row(const double wl, const double dx, double* row) {
+    const double dx2 = dx * dx, dx4 = dx2 * dx2;
+    double pw[4] = {wl, wl * dx, wl * dx2, wl * dx2 * dx};
+#pragma unroll
+    for (int n = 0; n < M2; ++n) {
+        row[n] = pw[n & 3];
+        pw[n & 3] *= dx4;
+    }
+    if constexpr (EXT) row[M2] = pw[M2 & 3];    // wl dx^(2N): the row's pad slot (odd moment counts)
+}
+
+// column sums of the contribution table: each lane owns moments l and l + G (2N <= 2G - 2), summed together in three
+// partial sums each -- a dependent add costs several issue slots on one wave.  The update half (half 1) scales its sums by
+// 1 / p_y and, with an odd moment count (EXT, extra), sums the pad column too, by the lane whose slot is order 2N.  (`half`
+// and `extra` are tested in here, where the kernel tested them: evaluated at the call they cost an EXT build a register.)
+template <int N, int G, int M2, int TLD, bool EXT, class H>
+__device__ __forceinline__ void column_sums(const double* TAB, double* mom, const int l, const H half, const double ipy,
+                                            const int extra, int& bad, double& out0, double& out1) {
+    const int n0 = l, n1 = l + G;
+    const bool has0 = n0 < M2, has1 = n1 < M2;
+    const bool tails = EXT && extra && half == 1;
+    const bool tail0 = tails && n0 == M2, tail1 = tails && n1 == M2;
+    const double* t0 = TAB + ((has0 || tail0) ? n0 : 0);
+    const double* t1 = TAB + ((has1 || tail1) ? n1 : 0);
+    double c0[N], c1[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) { c0[i] = t0[i * TLD]; c1[i] = t1[i * TLD]; }
+    __builtin_amdgcn_sched_barrier(0);   // every read in flight before the first add (one LDS latency, not N)
+    double s0[3] = {0.0, 0.0, 0.0}, s1[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < N; ++i) { s0[i % 3] += c0[i]; s1[i % 3] += c1[i]; }
+    double acc0 = (s0[0] + s0[1]) + s0[2], acc1 = (s1[0] + s1[1]) + s1[2];
+    if (half != 0) { acc0 *= ipy; acc1 *= ipy; }
+    if (has0) { mom[n0] = acc0; bad |= !finite(acc0); }
+    if (has1) { mom[n1] = acc1; bad |= !finite(acc1); }
+    out0 = acc0; out1 = acc1;     // (with an odd count out1 of lane 2N - G is the order-2N moment: written out, never carried)
+}
+
+// the posterior atoms in rule units, handed to the next predict half: nodes dx (returned) and weights wl / p_y
+template <int N, int G>
+__device__ __forceinline__ double posterior_atoms(const double x, const double c, const double inv_sc, const double wl,
+                                                  const double ipy, const bool node, double& gA, double& gW) {
+    double dx;
+    {   // not contracted: with the mode a compile-time constant c is visibly the product gsum * ipy and
+        // inv_sc is 1, and x - c would fuse into one multiply-add that the run-time-mode builds cannot form
+#pragma clang fp contract(off)
+        dx = (x - c) * inv_sc;
+    }
+    // the spare lanes shadow the last eigenvalue (the DPP read must run with the node lanes active)
+    const double last = bcast<G, N - 1>(dx);
+    gA = node ? dx : last;
+    gW = wl * ipy;                 // (0 in the spare lanes)
+    return dx;
+}
+
+// measurements: one coalesced 128-byte load per group every 16 steps (G when G < 16), handed out by a lane shuffle
+template <int G>
+__device__ __forceinline__ double y_window(const double* yrow, const bool has, const int l, const int t, const int t_begin,
+                                           const int t_end, double& ywin) {
+    constexpr int YW = (G < 16) ? G : 16;
+    const int tw = (t - t_begin) & (YW - 1);
+    if (tw == 0) {
+        // the loaded window is moved into its own register HERE, so that the wait for the load (vmcnt is an in-order
+        // counter: it also waits for every output store issued before) happens once per window, not at each step
+        const double ld = (has && t + (l & (YW - 1)) < t_end) ? yrow[t + (l & (YW - 1))] : 0.0;
+        asm volatile("v_mov_b64 %0, %1" : "=v"(ywin) : "v"(ld));
+    }
+    return __shfl(ywin, tw, YW);
+}
+
 template <int N, int G, int WPB, int OCC, bool EXT = false, int SPEC = 0, class TR = StepTraits<>>
 __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filter1dArgs a, const int lds_doubles) {
     static_assert(SPEC == 0 || (!EXT && OCC == 1), "specialised builds: plain kernel, one wave per SIMD");
     static_assert(!TR::fixed || SPEC != 0, "fixed step traits: specialised builds only");
     // the model switches a fixed-traits build knows at compile time
-    constexpr bool kFixSwitches = TR::fixed && (MFS_TRAITS_AB_SWITCHES == 0);
-    constexpr bool kLikRegs = TR::fixed && (MFS_TRAITS_AB_LIKREGS == 0);
-    constexpr bool kOutHoist = TR::fixed && (MFS_TRAITS_AB_OUTPUTS == 0);
-    constexpr bool kCarryWait = TR::fixed && (MFS_TRAITS_AB_CARRYWAIT == 0);
     // (read where they are used, as `a.mode` was: a run-time-traits build keeps its device code to the instruction)
-    const auto mode = [&]() __attribute__((always_inline)) { if constexpr (kFixSwitches) return (int)TR::mode; else return a.mode; };
-    const auto umap = [&]() __attribute__((always_inline)) { if constexpr (kFixSwitches) return (int)TR::umap; else return a.umap; };
-    const auto lik_kind = [&]() __attribute__((always_inline)) { if constexpr (kFixSwitches) return (int)TR::lik; else return a.lik_kind; };
+    const auto mode = [&]() __attribute__((always_inline)) { if constexpr (TR::fixed) return (int)TR::mode; else return a.mode; };
+    const auto umap = [&]() __attribute__((always_inline)) { if constexpr (TR::fixed) return (int)TR::umap; else return a.umap; };
+    const auto lik_kind = [&]() __attribute__((always_inline)) { if constexpr (TR::fixed) return (int)TR::lik; else return a.lik_kind; };
     static_assert(SPEC >= -1 && SPEC <= MFS_MAX_TERMS, "table shape");
     using L = FastTile<N, G>;
     constexpr int M2 = L::M2, TLD = L::TLD;
     constexpr int kShift = EXT ? L::kExtShift : 0;
     constexpr int FPW = 64 / G;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (lane / group / slot arithmetic: the same lines open the four kernels of this header and the two of filter1d_kernel.hpp)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / G, l = lane - grp * G;
     const int slot = wave * FPW + grp;
@@ -1038,10 +1150,10 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
     const double* coef = S + L::oCoef + kShift;
     const double* lp = S + L::oLik + kShift;
     double* lfac = S + L::oLfac + kShift;
-    const int J1 = a.degree + 1;
     const int MS = EXT ? M2 + a.extra : M2;        // moments per row of m0 / out_moments
 
-    {   // stage the model tables and the carry
+    {   // stage the model tables (twin: filter1d_partner_kernel; as a shared function it cost the generic builds registers)
+        const int J1 = a.degree + 1;
         const double* src = a.coef + (a.coef_batched ? (size_t)b * a.n_rows * J1 : 0);
         for (int e = l; e < ((a.degree + 4) & ~3) * kCoefRows; e += G) {   // [row][degree] in HBM -> [degree][row] in LDS,
             const int j = e / kCoefRows, r = e - j * kCoefRows;             // zero-padded in both directions
@@ -1074,31 +1186,18 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
     // the table shape a specialised build knows at compile time
     const int trans_kind = (SPEC > 0) ? MFS_TRANS_OPERATOR : (SPEC < 0) ? MFS_TRANS_GAUSSIAN : a.trans_kind;
     const int n_terms = (SPEC > 0) ? SPEC : a.n_terms;
-    constexpr bool kRegTable = (SPEC != 0) && (MFS_SPEC_AB_TABLE == 0);
-    constexpr bool kHalves = (SPEC != 0) && (MFS_SPEC_AB_HALVES == 0);
-    constexpr int kSlUpdate = (kHalves && (MFS_SPEC_AB_EIGLOOP == 0)) ? kSlEigLoop : 0;
-    // live rows: the operator terms + the variance row (LDS row MFS_MAX_TERMS), or mean and variance
-    constexpr int SR = (SPEC > 0) ? SPEC + 1 : 2;
-    constexpr int kVarReg = (SPEC > 0) ? SPEC : -1;     // the register row that holds LDS row MFS_MAX_TERMS
-    double tabr[kSpecTop][SR];
-    if constexpr (kRegTable) {
-#pragma unroll
-        for (int q = 0; q < kSpecTop; ++q)
-#pragma unroll
-            for (int r = 0; r < SR; ++r) tabr[q][r] = coef[q * kCoefRows + ((r == kVarReg) ? MFS_MAX_TERMS : r)];
-    }
+    constexpr int kSlUpdate = (SPEC != 0) ? kSlEigLoop : 0;
+    double tabr[kSpecTop][SpecRows<SPEC>::SR];
+    if constexpr (SPEC != 0) load_table_regs<SPEC>(coef, tabr);
     // the likelihood parameters: like the table, time-invariant for the launch (the staging loop above has been followed by a
     // wave_sync).  The entries a law does not read are dropped by the compiler.
     LikRegs lpr;
-    if constexpr (kLikRegs) {
-#pragma unroll
-        for (int e = 0; e < MFS_MAX_LIK; ++e) lpr.v[e] = lp[e];
-    }
+    if constexpr (TR::fixed) load_lik_regs(lp, lpr);
     // output stores of a fixed-traits build: which lanes store, and where, decided here.  (out_scale is null outside scaled
     // mode: plan_args of capi.hip, the one place that fills Filter1dArgs for a run.)
     bool st_m0 = false, st_m1 = false, st_mean = false, st_scale = false;
     size_t o_mom = ((size_t)b * a.T + a.t_begin) * MS + l, o_mean = (size_t)b * a.T + a.t_begin;   // running element offsets
-    if constexpr (kOutHoist) {
+    if constexpr (TR::fixed) {
         if (a.out_mom) {
             st_m0 = l < MS; st_m1 = l + G < MS;
         }
@@ -1128,7 +1227,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
         gW = a.c_lam[((size_t)b * 2 + 1) * G + l];
         have_atoms = true;
     }
-    if constexpr (kCarryWait) {
+    if constexpr (TR::fixed) {
         // every value loaded from memory above is used HERE, so that its wait is in front of the time loop.  Left to its
         // first use in the loop, the wait is an s_waitcnt vmcnt(0) executed at every step (the counter is in order: it also
         // waits for the output stores of the step before).
@@ -1140,16 +1239,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
 #endif
 
     for (int t = a.t_begin; t < a.t_end; ++t) {
-        // measurements: one coalesced 128-byte load per group every 16 steps, handed out by a lane shuffle
-        constexpr int YW = (G < 16) ? G : 16;
-        const int tw = (t - a.t_begin) & (YW - 1);
-        if (tw == 0) {
-            // the loaded window is moved into its own register HERE, so that the wait for the load (vmcnt is an in-order
-            // counter: it also waits for every output store issued before) happens once per window, not at each step
-            const double ld = (t + (l & (YW - 1)) < a.t_end) ? yrow[t + (l & (YW - 1))] : 0.0;
-            asm volatile("v_mov_b64 %0, %1" : "=v"(ywin) : "v"(ld));
-        }
-        const double y = __shfl(ywin, tw, YW);
+        const double y = y_window<G>(yrow, true, l, t, a.t_begin, a.t_end, ywin);
         double out0 = qnan, out1 = qnan;   // this lane's two moments of the step, kept in registers for the output store
         if (!dead) {
             int bad = 0;
@@ -1188,25 +1278,11 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                     // ---- prediction (filtering.py:76-79 / 144-148 / 221-225)
                     // every row of the model table at this lane's node, in one pass over the degrees
                     double rows[MFS_MAX_TERMS + 1];
-                    if constexpr (kRegTable) {
-                        double live[SR];
-                        horner_regs<kSpecTop, SR>(tabr, u, live);
-#pragma unroll
-                        for (int r = 0; r <= MFS_MAX_TERMS; ++r) rows[r] = 0.0;
-#pragma unroll
-                        for (int r = 0; r < SR; ++r) rows[(r == kVarReg) ? MFS_MAX_TERMS : r] = live[r];
-                    } else {
-                        horner_rows<MFS_MAX_TERMS + 1>(coef, a.degree, u, rows);
-                    }
+                    if constexpr (SPEC != 0) table_rows<SPEC>(tabr, u, rows);
+                    else horner_rows<MFS_MAX_TERMS + 1>(coef, a.degree, u, rows);
                     F1_STAMP(15);
                     double mu, var;
-                    if (trans_kind == MFS_TRANS_OPERATOR) {
-                        mu = x + rows[0];
-                        var = rows[MFS_MAX_TERMS];
-                    } else {
-                        mu = fma(a.mean_x_coef, x, rows[0]);
-                        var = rows[1];
-                    }
+                    transition_mu_var(trans_kind, a.mean_x_coef, x, rows, mu, var);
                     if (mode() != MFS_MODE_RAW) {
                         mean = gsum<G>(w * mu);
                         c = mean;
@@ -1229,24 +1305,11 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                             default: operator_moments<MFS_MAX_TERMS, M2>(rows, x - c, w, inv_sc, node, row); break;
                         }
                     } else {
-                        // normal closure: E_0 = 1, E_1 = m, E_n = m E_{n-1} + (n-1) v E_{n-2}   (moments.py:70-74), run on
-                        // F_n = w E_n / s^n directly: F_n = (m/s) F_{n-1} + (n-1) (v/s^2) F_{n-2}, F_0 = w
-                        const double ms = (mu - c) * inv_sc, vs = var * inv_sc * inv_sc;
-                        double f2 = w, f1 = w * ms, vn = vs;
-                        row[0] = f2;
-                        row[1] = f1;
-#pragma unroll
-                        for (int n = 2; n < M2; ++n) {
-                            const double f = fma(ms, f1, vn * f2);
-                            row[n] = f;
-                            vn += vs;
-                            f2 = f1;
-                            f1 = f;
-                        }
+                        normal_closure_row<M2>(w, mu, var, c, inv_sc, row);
                     }
                 } else {
                     // ---- update (filtering.py:82-85 / 151-157 / 228-236)
-                    const double wl = node ? w * likelihood_sel<kLikRegs>(lik_kind(), lpr, lp, lfac, y, x) : 0.0;
+                    const double wl = node ? w * likelihood_sel<TR::fixed>(lik_kind(), lpr, lp, lfac, y, x) : 0.0;
                     py = gsum<G>(wl);
                     ipy = rcp_nr(py);
                     F1_STAMP(17);
@@ -1258,61 +1321,22 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
                         scale = sqrt(gsum<G>(wl * (x - c) * (x - c)) * ipy);
                         inv_sc = 1.0 / scale;
                     }
-                    double dx;
-                    {   // not contracted: with the mode a compile-time constant c is visibly the product gsum * ipy and
-                        // inv_sc is 1, and x - c would fuse into one multiply-add that the run-time-mode builds cannot form
-#pragma clang fp contract(off)
-                        dx = (x - c) * inv_sc;
-                    }
-                    {   // the spare lanes shadow the last eigenvalue (the DPP read must run with the node lanes active)
-                        const double last = bcast<G, N - 1>(dx);
-                        gA = node ? dx : last;
-                        gW = wl * ipy;                 // (0 in the spare lanes)
-                        have_atoms = true;
-                    }
-                    double* row = TAB + l * TLD;
-                    {   // wl dx^n in four interleaved chains (a dependent multiply costs several issue slots)
-                        const double dx2 = dx * dx, dx4 = dx2 * dx2;
-                        double pw[4] = {wl, wl * dx, wl * dx2, wl * dx2 * dx};
-#pragma unroll
-                        for (int n = 0; n < M2; ++n) {
-                            row[n] = pw[n & 3];
-                            pw[n & 3] *= dx4;
-                        }
-                        if constexpr (EXT) row[M2] = pw[M2 & 3];    // wl dx^(2N): the row's pad slot (odd moment counts)
-                    }
+                    const double dx = posterior_atoms<N, G>(x, c, inv_sc, wl, ipy, node, gA, gW);
+                    have_atoms = true;
+                    power_row<M2, EXT>(wl, dx, TAB + l * TLD);
                     nell -= fast_log(py);
                 }
                 F1_STAMP(5 + half);
                 wave_sync();
-                {   // column sums of the contribution table: each lane owns moments l and l + G (2N <= 2G - 2), summed
-                    // together in three partial sums each -- a dependent add costs several issue slots on one wave
-                    const int n0 = l, n1 = l + G;
-                    const bool has0 = n0 < M2, has1 = n1 < M2;
-                    const bool tails = EXT && a.extra && half == 1;               // odd count: the pad column is summed too,
-                    const bool tail0 = tails && n0 == M2, tail1 = tails && n1 == M2;  // by the lane whose slot is order 2N
-                    const double* t0 = TAB + ((has0 || tail0) ? n0 : 0);
-                    const double* t1 = TAB + ((has1 || tail1) ? n1 : 0);
-                    double c0[N], c1[N];
-#pragma unroll
-                    for (int i = 0; i < N; ++i) { c0[i] = t0[i * TLD]; c1[i] = t1[i * TLD]; }
-                    __builtin_amdgcn_sched_barrier(0);   // every read in flight before the first add (one LDS latency, not N)
-                    double s0[3] = {0.0, 0.0, 0.0}, s1[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int i = 0; i < N; ++i) { s0[i % 3] += c0[i]; s1[i % 3] += c1[i]; }
-                    double acc0 = (s0[0] + s0[1]) + s0[2], acc1 = (s1[0] + s1[1]) + s1[2];
-                    if (half != 0) { acc0 *= ipy; acc1 *= ipy; }
-                    if (has0) { mom[n0] = acc0; bad |= !finite(acc0); }
-                    if (has1) { mom[n1] = acc1; bad |= !finite(acc1); }
-                    out0 = acc0; out1 = acc1;     // (with an odd count out1 of lane 2N - G is the order-2N moment: written out, never carried)
-                }
+                // predicted or posterior moments; with an odd count (EXT) the update half sums the pad column too
+                column_sums<N, G, M2, TLD, EXT>(TAB, mom, l, half, ipy, a.extra, bad, out0, out1);
                 wave_sync();
                 F1_STAMP((half == 0) ? 7 : 8);
 #ifdef MFS_1D_STAMPS
                 if (blockIdx.x == 0 && threadIdx.x == 0) g_1d_stamps[9] += 1;
 #endif
             };
-            if constexpr (kHalves) {
+            if constexpr (SPEC != 0) {
                 if (have_atoms & (a.recompute_rule == 0)) half_step(std::integral_constant<int, 0>{}, std::true_type{});
                 else half_step(std::integral_constant<int, 0>{}, std::false_type{});   // the first step of a run; MFS_PREDICT_RULE=recompute
                 half_step(std::integral_constant<int, 1>{}, std::false_type{});
@@ -1328,7 +1352,7 @@ __global__ __launch_bounds__(WPB * 64, OCC) void filter1d_fast_kernel(const Filt
             mean = qnan; scale = qnan; nell = qnan;
             wave_sync();
         }
-        if constexpr (kOutHoist) {
+        if constexpr (TR::fixed) {
             // (a pointer is formed only under its predicate: an absent output is never the base of an address)
             if (st_m0) a.out_mom[o_mom] = out0;
             if (st_m1) a.out_mom[o_mom + G] = out1;
@@ -1370,6 +1394,7 @@ __global__ __launch_bounds__(WPB * 64) void quadrature1d_fast_kernel(const Quad1
     constexpr int M2 = 2 * N;
     constexpr int FPW = 64 / G;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (lane / group / slot arithmetic: the same lines open the four kernels of this header and the two of filter1d_kernel.hpp)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / G, l = lane - grp * G;
     const int slot = wave * FPW + grp;
@@ -1394,6 +1419,7 @@ __global__ __launch_bounds__(WPB * 64) void quadrature1d_fast_ext_kernel(const Q
     constexpr int M2 = 2 * N, kStride = L::oLik + L::kExtShift;
     constexpr int FPW = 64 / G;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (lane / group / slot arithmetic: the same lines open the four kernels of this header and the two of filter1d_kernel.hpp)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / G, l = lane - grp * G;
     const int slot = wave * FPW + grp;
@@ -1433,6 +1459,7 @@ __global__ __launch_bounds__(WPB * 64) void cf1d_fast_kernel(const Cf1dArgs a) {
     constexpr int M2 = 2 * N;
     constexpr int FPW = 64 / G;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (lane / group / slot arithmetic: the same lines open the four kernels of this header and the two of filter1d_kernel.hpp)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / G, l = lane - grp * G;
     const int slot = wave * FPW + grp;

@@ -421,6 +421,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void filter1d_kernel(const Filter1dArg
     constexpr int M2 = L::M2;
     constexpr int FPW = 64 / G;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (lane / group / slot arithmetic: the same lines open the two kernels of this header and the four of filter1d_fast.hpp)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / G, l = lane - grp * G;
     const int slot = wave * FPW + grp;
@@ -573,6 +574,7 @@ __global__ __launch_bounds__(WPB * 64) void quadrature1d_kernel(const Quad1dArgs
     constexpr int M2 = L::M2;
     constexpr int FPW = 64 / G;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (lane / group / slot arithmetic: the same lines open the two kernels of this header and the four of filter1d_fast.hpp)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / G, l = lane - grp * G;
     const int slot = wave * FPW + grp;

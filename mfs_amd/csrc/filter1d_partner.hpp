@@ -39,8 +39,9 @@
 // one partner_barrier() at the top level of the body.  Whether a filter is live, dead or absent (b >= B) only changes what
 // the lanes do between the barriers; no lane leaves the kernel early.  There is no spin or poll loop.
 //
-// Every floating-point operation that feeds an output is the one-wave build's, in its order: the statements of the two halves
-// are those of filter1d_fast_kernel for a fixed-traits build, split between the roles, and quadrature_fast is called as it is
+// Every floating-point operation that feeds an output is the one-wave build's, in its order: the blocks of the two halves
+// are the functions filter1d_fast_kernel calls for a fixed-traits build (filter1d_fast.hpp, above the kernel), split between
+// the roles -- only the staging of the model tables is a copy -- and quadrature_fast is called as it is
 // there (the partner's call keeps only the pivots, as the predict half of the one-wave builds does); the SL bits this variant
 // adds to its calls (kSlFreezeX, kSlPivMin) drop selects and compares whose results nothing reads, no arithmetic.
 // First step of a run (no atoms): the main wave runs the cold full rule on the moments it loads, as the one-wave builds do.
@@ -51,24 +52,10 @@
 
 namespace mfs {
 
-// leave-one-out switch (Makefile: PARTNERFLAGS), against the full variant: MFS_PARTNER_AB_LOGPY 1 = nell -= log p_y stays on
-// the main wave.  (No s_setprio for the main waves: it measured slower.  Both measurements: DESIGN.md section 6.)
-#ifndef MFS_PARTNER_AB_LOGPY
-#define MFS_PARTNER_AB_LOGPY 0
-#endif
-// the step-boundary changes of the main wave, one switch each (0 = the shipped code, 1 = the code it replaced):
-//   MFS_PARTNER_AB_FLAGLATE   the partner's flags are consumed inside the next step (1: waited for right behind the barrier)
-//   MFS_PARTNER_AB_FREEZE     the eigenvalue loop freezes only x of a converged lane (1: lo, hi and prev_step as well)
-//   MFS_PARTNER_AB_PIVMIN     the poison flag from a running minimum of the pivots (1: one compare per pivot)
-#ifndef MFS_PARTNER_AB_FLAGLATE
-#define MFS_PARTNER_AB_FLAGLATE 0
-#endif
-#ifndef MFS_PARTNER_AB_FREEZE
-#define MFS_PARTNER_AB_FREEZE 0
-#endif
-#ifndef MFS_PARTNER_AB_PIVMIN
-#define MFS_PARTNER_AB_PIVMIN 0
-#endif
+// Decided by leave-one-out builds (compile-time switches MFS_PARTNER_AB_* that existed up to commit ac4d42d; the series of
+// DESIGN.md section 6 were taken with them): log p_y and nell on the partner, the partner's flags consumed inside the next
+// step, an eigenvalue loop that freezes only x of a converged lane (kSlFreezeX), the poison flag from a running minimum of
+// the pivots (kSlPivMin).  (No s_setprio for the main waves: it measured slower.)
 
 constexpr int kPartnerMainWaves = 4;                       // main waves per workgroup = SIMDs per compute unit
 constexpr int kPartnerThreads = 2 * kPartnerMainWaves * 64;
@@ -106,9 +93,6 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
     using P = PartnerTile<N, G>;
     constexpr int M2 = L::M2, TLD = L::TLD;
     constexpr int FPW = 64 / G, FPB = kPartnerMainWaves * FPW;
-    constexpr bool kLogMain = (MFS_PARTNER_AB_LOGPY != 0);
-    constexpr bool kFlagLate = (MFS_PARTNER_AB_FLAGLATE == 0);
-    constexpr int kSlPivots = (MFS_PARTNER_AB_PIVMIN == 0) ? kSlPivMin : 0;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     // (the wave number as a scalar: the split into roles is a scalar branch, and a wave never walks through the other role's
     //  loop -- and its barriers -- with an empty EXEC mask)
@@ -150,8 +134,8 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
         const double* coef = S + L::oCoef;
         const double* lp = S + L::oLik;
         double* lfac = S + L::oLfac;
-        const int J1 = a.degree + 1;
-        if (has) {   // stage the model tables
+        if (has) {   // stage the model tables (twin: filter1d_fast_kernel)
+            const int J1 = a.degree + 1;
             const double* src = a.coef + (a.coef_batched ? (size_t)b * a.n_rows * J1 : 0);
             for (int e = l; e < ((a.degree + 4) & ~3) * kCoefRows; e += G) {
                 const int j = e / kCoefRows, r = e - j * kCoefRows;
@@ -164,7 +148,7 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
             if (TR::lik == MFS_LIK_POISSON_SOFTPLUS)
                 for (int e = l; e <= kLfacMax; e += G) lfac[e] = log_factorial((double)e);
         }
-        double mean = 0.0, scale = 1.0, nell = 0.0;
+        double mean = 0.0, scale = 1.0;
         int first_nan = -1;
         double gA = qnan, gW = 0.0;
         bool have_atoms = false;
@@ -177,7 +161,6 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
                 if (!a.c_lam) for (int n = l; n < M2; n += G) mom[n] = a.c_mom[(size_t)b * M2 + n];   // (no atoms: the cold rule)
                 mean = a.c_mean[b];
                 scale = a.c_scale[b];
-                if constexpr (kLogMain) nell = a.c_nell[b];
                 first_nan = a.c_first_nan[b];
                 if (a.c_lam) {
                     gA = a.c_lam[((size_t)b * 2 + 0) * G + l];
@@ -187,50 +170,34 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
             }
         }
         wave_sync();
-        constexpr int SR = (SPEC > 0) ? SPEC + 1 : 2;
-        constexpr int kVarReg = (SPEC > 0) ? SPEC : -1;
-        double tabr[kSpecTop][SR];
+        double tabr[kSpecTop][SpecRows<SPEC>::SR];
         LikRegs lpr;
         // (an absent filter reads whatever its tile holds: nothing of it is ever stored)
-#pragma unroll
-        for (int q = 0; q < kSpecTop; ++q)
-#pragma unroll
-            for (int r = 0; r < SR; ++r) tabr[q][r] = coef[q * kCoefRows + ((r == kVarReg) ? MFS_MAX_TERMS : r)];
-#pragma unroll
-        for (int e = 0; e < MFS_MAX_LIK; ++e) lpr.v[e] = lp[e];
+        load_table_regs<SPEC>(coef, tabr);
+        load_lik_regs(lp, lpr);
         const bool st_mean = has && a.out_mean && (l == 0);
         size_t o_mean = (size_t)b * a.T + a.t_begin;
         const double* yrow = a.ys + (size_t)b * a.T;
         bool dead = !has || (first_nan >= 0);
-        asm volatile("" : "+v"(mean), "+v"(scale), "+v"(nell), "+v"(gA), "+v"(gW), "+v"(first_nan));   // the carry waits, in front of the loop
+        asm volatile("" : "+v"(mean), "+v"(scale), "+v"(gA), "+v"(gW), "+v"(first_nan));   // the carry waits, in front of the loop
         double ywin = 0.0;
-        constexpr int kSlUpdate = kSlEigLoop | ((MFS_PARTNER_AB_FREEZE == 0) ? kSlFreezeX : 0) | kSlPivots;
+        constexpr int kSlUpdate = kSlEigLoop | kSlFreezeX | kSlPivMin;
         constexpr int trans_kind = (SPEC > 0) ? MFS_TRANS_OPERATOR : MFS_TRANS_GAUSSIAN;
-        // the late flag (kFlagLate): the flag word read behind barrier t and the mean of step t, both settled inside step t + 1
+        // the late flag: the flag word read behind barrier t and the mean of step t, both settled inside step t + 1
         int fl_prev = 0;
-        double mean_prev = 0.0, nell_next = nell;
+        double mean_prev = 0.0;
         const auto settle = [&]() __attribute__((always_inline)) {
             if (dead || fl_prev != 0) {
                 dead = true;
                 mean = qnan; scale = qnan; mean_prev = qnan;
-                if constexpr (kLogMain) nell = qnan;
-            } else {
-                if constexpr (kLogMain) nell = nell_next;
             }
             if (st_mean) a.out_mean[o_mean] = mean_prev;
             o_mean += 1;
         };
 
         for (int t = a.t_begin; t < a.t_end; ++t) {
-            constexpr int YW = 16;
-            const int tw = (t - a.t_begin) & (YW - 1);
-            if (tw == 0) {
-                const double ld = (has && t + (l & (YW - 1)) < a.t_end) ? yrow[t + (l & (YW - 1))] : 0.0;
-                asm volatile("v_mov_b64 %0, %1" : "=v"(ywin) : "v"(ld));
-            }
-            const double y = __shfl(ywin, tw, YW);
+            const double y = y_window<G>(yrow, has, l, t, a.t_begin, a.t_end, ywin);
             double* xs = xch + (t & 1) * 4 * G;
-            if constexpr (!kFlagLate) nell_next = nell;
             int bad = 0;
             double gB = qnan;
             if (!dead) {
@@ -249,58 +216,20 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
                     const double u = (TR::umap == MFS_U_TANH) ? fast_tanh(x) : x;
                     double c = 0.0, inv_sc = 1.0;
                     double rows[MFS_MAX_TERMS + 1];
-                    {
-                        double live[SR];
-                        horner_regs<kSpecTop, SR>(tabr, u, live);
-#pragma unroll
-                        for (int r = 0; r <= MFS_MAX_TERMS; ++r) rows[r] = 0.0;
-#pragma unroll
-                        for (int r = 0; r < SR; ++r) rows[(r == kVarReg) ? MFS_MAX_TERMS : r] = live[r];
-                    }
+                    table_rows<SPEC>(tabr, u, rows);
                     double mu, var;
-                    if (trans_kind == MFS_TRANS_OPERATOR) {
-                        mu = x + rows[0];
-                        var = rows[MFS_MAX_TERMS];
-                    } else {
-                        mu = fma(a.mean_x_coef, x, rows[0]);
-                        var = rows[1];
-                    }
+                    transition_mu_var(trans_kind, a.mean_x_coef, x, rows, mu, var);
                     mean = gsum<G>(w * mu);
                     c = mean;
                     double* row = TAB + l * TLD;
                     if (trans_kind == MFS_TRANS_OPERATOR) {
                         operator_moments<(SPEC > 0) ? SPEC : 2, M2>(rows, x - c, w, inv_sc, node, row);
                     } else {
-                        const double ms = (mu - c) * inv_sc, vs = var * inv_sc * inv_sc;
-                        double f2 = w, f1 = w * ms, vn = vs;
-                        row[0] = f2;
-                        row[1] = f1;
-#pragma unroll
-                        for (int n = 2; n < M2; ++n) {
-                            const double f = fma(ms, f1, vn * f2);
-                            row[n] = f;
-                            vn += vs;
-                            f2 = f1;
-                            f1 = f;
-                        }
+                        normal_closure_row<M2>(w, mu, var, c, inv_sc, row);
                     }
                     wave_sync();
-                    {   // column sums of the contribution table -> predicted moments
-                        const int n0 = l, n1 = l + G;
-                        const bool has0 = n0 < M2, has1 = n1 < M2;
-                        const double* t0 = TAB + (has0 ? n0 : 0);
-                        const double* t1 = TAB + (has1 ? n1 : 0);
-                        double c0[N], c1[N];
-#pragma unroll
-                        for (int i = 0; i < N; ++i) { c0[i] = t0[i * TLD]; c1[i] = t1[i * TLD]; }
-                        __builtin_amdgcn_sched_barrier(0);
-                        double s0[3] = {0.0, 0.0, 0.0}, s1[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-                        for (int i = 0; i < N; ++i) { s0[i % 3] += c0[i]; s1[i % 3] += c1[i]; }
-                        const double acc0 = (s0[0] + s0[1]) + s0[2], acc1 = (s1[0] + s1[1]) + s1[2];
-                        if (has0) { mom[n0] = acc0; bad |= !finite(acc0); }
-                        if (has1) { mom[n1] = acc1; bad |= !finite(acc1); }
-                    }
+                    double pm0, pm1;   // (the predicted moments are no output)
+                    column_sums<N, G, M2, TLD, false>(TAB, mom, l, 0, 1.0, 0, bad, pm0, pm1);
                     wave_sync();
                 };
                 if (have_atoms) predict(std::true_type{});
@@ -311,7 +240,7 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
             // that, has arrived and this costs no wait of its own; a wait placed earlier would stand behind the table writes,
             // because the LDS counter only counts down in order.  Nothing of step t has been handed over or stored yet: a filter
             // that turns out dead here has computed one predict half for nothing, into its own tile, and stops.
-            if constexpr (kFlagLate) { if (t > a.t_begin) settle(); }
+            if (t > a.t_begin) settle();
             if (!dead) {
                 {   // ---- update half (half 1) up to the atoms
                     double x, w;
@@ -323,21 +252,8 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
                     ipy = rcp_nr(py);
                     mean = gsum<G>(wl * x) * ipy;
                     c = mean;
-                    double dx;
-                    {
-#pragma clang fp contract(off)
-                        dx = (x - c) * inv_sc;
-                    }
-                    {
-                        const double last = bcast<G, N - 1>(dx);
-                        gA = node ? dx : last;
-                        gW = wl * ipy;
-                        have_atoms = true;
-                    }
-                    if constexpr (kLogMain) {
-                        nell_next = nell - fast_log(py);
-                        bad |= (int)!finite(nell_next);
-                    }
+                    const double dx = posterior_atoms<N, G>(x, c, inv_sc, wl, ipy, node, gA, gW);
+                    have_atoms = true;
                     bad |= (int)(!finite(mean) || !finite(scale));
                     // hand-over to the partner: slot t & 1
                     xs[0 * G + l] = dx;
@@ -349,21 +265,15 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
             }
             partner_barrier();
             // the partner's flags of round t - 1 (the opening of a launch for t = t_begin): read here, before the partner can
-            // write the word again, and -- kFlagLate -- waited for and acted on inside step t + 1, or behind the loop
+            // write the word again, and waited for and acted on inside step t + 1, or behind the loop
             fl_prev = flags[(t + 1) & 1];
             mean_prev = mean;
-            if constexpr (!kFlagLate) settle();
         }
-        if constexpr (kFlagLate) { if (a.t_end > a.t_begin) settle(); }   // the last step's mean, before the carry is written
+        if (a.t_end > a.t_begin) settle();   // the last step's mean, before the carry is written
         if (has) {
-            if (a.t_end >= a.T) {
-                if constexpr (kLogMain) { if (l == 0) a.out_nell[b] = nell; }
-            } else {
+            if (a.t_end < a.T) {
                 if (a.c_lam) { a.c_lam[((size_t)b * 2 + 0) * G + l] = gA; a.c_lam[((size_t)b * 2 + 1) * G + l] = gW; }
-                if (l == 0) {
-                    a.c_mean[b] = mean; a.c_scale[b] = scale;
-                    if constexpr (kLogMain) a.c_nell[b] = nell;
-                }
+                if (l == 0) { a.c_mean[b] = mean; a.c_scale[b] = scale; }
             }
         }
     } else {
@@ -378,13 +288,13 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
         double xd, wd, lamd = qnan;   // (quadrature_fast's outputs: unused, the call keeps only the pivots)
         if (has && a.t_begin != 0) {
             for (int n = l; n < M2; n += G) pmom[n] = a.c_mom[(size_t)b * M2 + n];
-            if constexpr (!kLogMain) nell = a.c_nell[b];
+            nell = a.c_nell[b];
             first_nan = a.c_first_nan[b];
         }
         wave_sync();
         bool dead = !has || (first_nan >= 0);
         if (!dead && a.t_begin != 0)   // the flag of step t_begin: the elimination the one-wave builds run in its predict half
-            pivot_prev = quadrature_fast<N, G, false, kSlPivots>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
+            pivot_prev = quadrature_fast<N, G, false, kSlPivMin>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
         flags[(a.t_begin + 1) & 1] = (dead ? kPartnerFlagDead : 0) | (pivot_prev ? kPartnerFlagPivot : 0);
         const bool st_m0 = has && a.out_mom && l < M2, st_m1 = has && a.out_mom && l + G < M2;
         size_t o_mom = ((size_t)b * a.T + a.t_begin) * M2 + l;
@@ -396,41 +306,15 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
             if (!dead && !pivot_prev) {
                 int bad = flags[2 + (t & 1)];
                 const double dx = xs[0 * G + l], wl = xs[1 * G + l], ipy = xs[2 * G + l], py = xs[3 * G + l];
-                double* row = PTAB + l * TLD;
-                {   // wl dx^n in four interleaved chains
-                    const double dx2 = dx * dx, dx4 = dx2 * dx2;
-                    double pw[4] = {wl, wl * dx, wl * dx2, wl * dx2 * dx};
-#pragma unroll
-                    for (int n = 0; n < M2; ++n) {
-                        row[n] = pw[n & 3];
-                        pw[n & 3] *= dx4;
-                    }
-                }
-                if constexpr (!kLogMain) nell -= fast_log(py);
+                power_row<M2, false>(wl, dx, PTAB + l * TLD);
+                nell -= fast_log(py);
                 wave_sync();
-                {   // column sums of the contribution table -> posterior moments
-                    const int n0 = l, n1 = l + G;
-                    const bool has0 = n0 < M2, has1 = n1 < M2;
-                    const double* t0 = PTAB + (has0 ? n0 : 0);
-                    const double* t1 = PTAB + (has1 ? n1 : 0);
-                    double c0[N], c1[N];
-#pragma unroll
-                    for (int i = 0; i < N; ++i) { c0[i] = t0[i * TLD]; c1[i] = t1[i * TLD]; }
-                    __builtin_amdgcn_sched_barrier(0);
-                    double s0[3] = {0.0, 0.0, 0.0}, s1[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int i = 0; i < N; ++i) { s0[i % 3] += c0[i]; s1[i % 3] += c1[i]; }
-                    double acc0 = (s0[0] + s0[1]) + s0[2], acc1 = (s1[0] + s1[1]) + s1[2];
-                    acc0 *= ipy; acc1 *= ipy;
-                    if (has0) { pmom[n0] = acc0; bad |= !finite(acc0); }
-                    if (has1) { pmom[n1] = acc1; bad |= !finite(acc1); }
-                    out0 = acc0; out1 = acc1;
-                }
+                column_sums<N, G, M2, TLD, false>(PTAB, pmom, l, 1, ipy, 0, bad, out0, out1);   // posterior moments
                 wave_sync();
-                if constexpr (!kLogMain) bad |= (int)!finite(nell);
+                bad |= (int)!finite(nell);
                 if (gany<G>(bad != 0, grp)) { dead = true; first_nan = t; }
                 // the poison decision of the next predict half (a dead filter's flag already says everything)
-                pivot_prev = quadrature_fast<N, G, false, kSlPivots>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
+                pivot_prev = quadrature_fast<N, G, false, kSlPivMin>(pmom, l, grp, 0.0, 1.0, xd, wd, lamd, false, true, 0.0, PS, 0);
             } else {
                 if (!dead) first_nan = t;   // the pivot flag of the step before: this step is NaN throughout
                 dead = true;
@@ -447,13 +331,13 @@ __global__ __launch_bounds__(kPartnerThreads, 2) void filter1d_partner_kernel(co
         if (has) {
             if (a.t_end >= a.T) {
                 if (l == 0) {
-                    if constexpr (!kLogMain) a.out_nell[b] = nell;
+                    a.out_nell[b] = nell;
                     if (a.out_first_nan) a.out_first_nan[b] = first_nan;
                 }
             } else {
                 for (int n = l; n < M2; n += G) a.c_mom[(size_t)b * M2 + n] = pmom[n];
                 if (l == 0) {
-                    if constexpr (!kLogMain) a.c_nell[b] = nell;
+                    a.c_nell[b] = nell;
                     a.c_first_nan[b] = first_nan;
                 }
             }
