@@ -55,15 +55,12 @@ __device__ unsigned long long g_nd_hist[8][40];   // [test index][-log10(off / d
 
 // Work is handed out by "thread id" = 64 x (the role of the wave) + lane; most phases of a step run on roles 0 or 0..1 only, i.e. on
 // one or two of a workgroup's four waves, and two or three workgroups share a CU.  The role of a wave is NOT its position in the
-// workgroup but a permutation of its SIMD id chosen by the wave slot (MFS_ND_SIMD_ROLES, default on): the waves of a workgroup sit on the four
+// workgroup but a permutation of its SIMD id chosen by the wave slot: the waves of a workgroup sit on the four
 // SIMDs in no fixed order, all on the same wave slot, and co-resident workgroups on different slots (tools/diag/hwid.hip) -- so the
 // busy waves of co-resident workgroups land on DIFFERENT SIMDs instead of queueing on one.  The kernel prologue checks that the four
 // roles are a permutation of 0..3 and falls back to the position in the workgroup otherwise (nd_assign_roles).  Measured, round 3:
 // config 5 11.87 -> 11.36 ms, tme_normal_2 16.95 -> 16.4 ms, B = 2048 35.4 -> 34.3 ms on real batches (-9..12 % when every
 // workgroup runs the same replicate in lock step).  An earlier form that re-read the role from LDS at every use gave the gain back (1 %).
-#ifndef MFS_ND_SIMD_ROLES
-#define MFS_ND_SIMD_ROLES 1
-#endif
 // (The empty volatile asm makes every call a fresh value to the optimiser.  Without it each inlined helper's thread-dependent
 //  LDS addresses are loop invariants of the time loop, get hoisted out of it by the dozen, do not fit in the register budget of
 //  two workgroups per CU and come back as scratch reloads -- a `s_waitcnt vmcnt(0)` in front of every phase -- where
@@ -73,13 +70,9 @@ __device__ __forceinline__ int nd_tid(const int role64) {
     asm volatile("" : "+v"(t));
     return t;
 }
-#ifdef MFS_ND_ROLE_DEBUG
-__device__ unsigned g_nd_role_fallbacks[2];
-#endif
 // Prologue of the kernel: 64 x (the role of this wave), a scalar.  Two barriers; every thread of the workgroup must call it.
 __device__ __forceinline__ int nd_assign_roles(double* misc) {
     const int w = threadIdx.x >> 6;
-#if MFS_ND_SIMD_ROLES
     int* roles = reinterpret_cast<int*>(misc);
     unsigned hw;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
@@ -93,14 +86,7 @@ __device__ __forceinline__ int nd_assign_roles(double* misc) {
     __syncthreads();
     const unsigned seen = (1u << roles[0]) | (1u << roles[1]) | (1u << roles[2]) | (1u << roles[3]);
     __syncthreads();
-#ifdef MFS_ND_ROLE_DEBUG
-    if (threadIdx.x == 0) { atomicAdd(&g_nd_role_fallbacks[0], seen != 15u ? 1u : 0u); atomicAdd(&g_nd_role_fallbacks[1], cand != 0 ? 1u : 0u); }
-#endif
     return __builtin_amdgcn_readfirstlane((seen == 15u) ? cand : w) * 64;
-#else
-    (void)misc;
-    return __builtin_amdgcn_readfirstlane(w) * 64;
-#endif
 }
 // exponents (n0, n1) of moment zi in graded lexicographic order: zi = sd (sd + 1) / 2 + n0, sd = n0 + n1  (zi < 2^20)
 __device__ __forceinline__ void nd_exponents(const int zi, int& n0, int& n1) {
@@ -113,7 +99,7 @@ __device__ __forceinline__ void nd_exponents(const int zi, int& n0, int& n1) {
 struct FilterNdArgs {
     int mode, T, B, stable;
     int t_begin, t_end;       // the steps this launch takes (a chunk of [0, T)); the state crosses launches through `carry`
-    double* carry;            // [B][NdTile::kCarry]: moments, means / scales / nell / first-NaN / flags, eigenvector tiles (or null)
+    double* carry;            // [B][NdTile::kCarry] (or null): the slots NdTile::cMean .. cV name the layout
     int n_terms_used, D;      // coefficient block extent per variable (degree + 1)
     int n_factors, ny;        // likelihood = prod_f lik(kind_f, params_f, y[ycol_f], x[comp_f]);  ys is [B][T][ny]
     int fac_kind[2], fac_comp[2], fac_ycol[2];
@@ -145,24 +131,12 @@ constexpr int kNdTermsLo = 14, kNdTermsHi = 27;
 template <int TK> constexpr int nd_terms() { return (TK == 2) ? kNdTermsHi : kNdTermsLo; }
 template <int TK> constexpr int nd_rows() { return nd_terms<TK>() + 2; }
 template <int TK> constexpr int nd_kmax() { return (TK == 2) ? 6 : 4; }      // highest derivative order per variable
-#ifndef MFS_ND_JACOBI_TOL
-#define MFS_ND_JACOBI_TOL 1e-31
-#endif
 // off-diagonal / diagonal mass (squared Frobenius norms) at which the Jacobi sweeps stop
-constexpr double kNdJacobiTol = MFS_ND_JACOBI_TOL;
-#ifndef MFS_ND_FORCE_JACOBI
-#define MFS_ND_FORCE_JACOBI 0   // 1: updates always diagonalise (A/B against the Chebyshev evaluation)
-#endif
-#ifndef MFS_ND_FINISH_X2
-#define MFS_ND_FINISH_X2 1e-14
-#endif
+constexpr double kNdJacobiTol = 1e-31;
 // squared Frobenius size of the first-order eigenvector correction below which it replaces further sweeps (0: never)
-constexpr double kNdFinishX2 = MFS_ND_FINISH_X2;
-#ifndef MFS_ND_FINISH2_X2
-#define MFS_ND_FINISH2_X2 1e-9
-#endif
+constexpr double kNdFinishX2 = 1e-14;
 // ... below which the SECOND-order correction does (its error is ~ ||X||^3: 3e-14 at 1e-9; 0: never)
-constexpr double kNdFinish2X2 = MFS_ND_FINISH2_X2;
+constexpr double kNdFinish2X2 = 1e-9;
 template <int TK> constexpr int nd_maxd() { return (TK == 2) ? 7 : 6; }   // per-variable extent bound of the coefficient blocks
 __device__ constexpr int kKap0[kNdTermsHi] = {0, 1, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 3, 4, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 6};
 __device__ constexpr int kKap1[kNdTermsHi] = {1, 0, 2, 1, 0, 3, 2, 1, 0, 4, 3, 2, 1, 0, 5, 4, 3, 2, 1, 0, 6, 5, 4, 3, 2, 1, 0};
@@ -207,14 +181,19 @@ struct NdTile {
     static constexpr bool kJoint = (TK == 1) || (TK == 3 && N <= 6);     // (N = 7 with operator tables: a second workgroup per CU matters more)
     static constexpr int oLam = oW + ((TK == 1) ? ((nWt + 1) & ~1) : kJoint ? ((R + 1) & ~1) : 0); // [2][LS]
     static constexpr int ZB = (Z + 15) / 16;         // batches of 16 moments in the transposing reduction
-    static constexpr int RW = 16 * ZB + 6;           // reduction row: moments (padded), flag, 5 scalar sums
+    static constexpr int kRedTail = 16 * ZB;         // within a reduction row: the slot after the padded moments
+    static constexpr int RW = kRedTail + 6;          // reduction row: moments (padded), flag, 5 scalar sums
     static constexpr int oRed = oLam + (kJoint ? 2 * LS : 0);       // [4 waves x 4 DPP rows][RW]
-    static constexpr int nRed = kJoint ? 16 * RW : 16 * ZB + 16;   // (TK = 2: Jacobi test scratch + the flag slot at [16 ZB] only)
+    static constexpr int nRed = kJoint ? 16 * RW : kRedTail + 16;  // (TK = 2: Jacobi test scratch + the flag slot at [kRedTail] only)
+    static constexpr int oHalfFlag = oRed + kRedTail;               // set by a half-step whose moments are not all finite (nd_end_half clears it)
     static constexpr int kTerms = nd_terms<TK>(), kRows = nd_rows<TK>(), kMaxD = nd_maxd<TK>();
     static constexpr bool kOperator = (TK != 1);     // operator-table prediction (TK = 0, 2) or Normal closure (TK = 1)
     static constexpr int FFS = nd_kmax<TK>() + 1;    // falling-factorial table stride: k = 0 .. kmax
     static constexpr int oCoef = oRed + nRed;        // [kRows][D][D]
-    static constexpr int oMisc = oCoef + kRows * kMaxD * kMaxD;  // lik params [4], flags [4]
+    static constexpr int oMisc = oCoef + kRows * kMaxD * kMaxD;  // role scratch of the prologue [4], flags [4]
+    static constexpr int oPoison = oMisc + 4;        // a front end met a pivot that is not > 0, or a Jacobi run a non-finite matrix
+    static constexpr int oFirstNan = oMisc + 5;      // step of the first non-finite result: an int in the low word, -1 = none
+    static constexpr int oChebFail = oMisc + 6;      // cheb_h_nd: the Chebyshev coefficients of a factor did not converge
     // Tournament index tables, built once per launch: which rows / columns a work item touches in round r depends on
     // (r, item) only, and recomputing it cost ~50 integer instructions per thread per round next to ~30 flops.
     //   KT[r][P * HP + Q] = p1 | p2 << 8 | q1 << 16 | q2 << 24  (u32)
@@ -275,7 +254,15 @@ struct NdTile {
     static constexpr int kDoubles = oChG + ((TK == 1) ? kNcpMax : 0);
     static constexpr int oU = oPK;
     static_assert(TK != 1 || 2 * kNcpMax * NP <= 2 * NPW * NP + 2 * NPW * MLD + kUPad, "Chebyshev-grid vectors must fit in the Krylov and moment-array tiles");
-    static constexpr int kCarry = Z + 8 + 2 * NP * LD;   // per-replicate state between the chunk launches of one run
+    // per-replicate state between the chunk launches of one run (restored in the kernel's prologue, parked at its end): the moments [0, Z), eight
+    // scalars, then the eigenvector tiles V_0, V_1 that a warm-started Jacobi reads
+    static constexpr int cMean = Z, cScale = Z + 2;      // [2] each
+    static constexpr int cNell = Z + 4;
+    static constexpr int cFirstNan = Z + 5;              // the word of oFirstNan
+    static constexpr int cDead = Z + 6;                  // 1.0: the replicate has gone non-finite
+    static constexpr int cWarm = Z + 7;                  // warm_mask as a double
+    static constexpr int cV = Z + 8;                     // [2][NP][LD]
+    static constexpr int kCarry = cV + 2 * NP * LD;
     static constexpr int oJs = (TK == 1) ? oW : oM;
     static_assert(S * S <= 2 * NPW * MLD, "Jacobi scratch must fit in the moment-array tiles");
 };
@@ -474,7 +461,7 @@ __device__ __forceinline__ bool front_nd(double* __restrict__ Sm, const int32_t*
     double* mom = Sm + L::oMom;
     double* A = Sm + L::oA;
     double* K = Sm + L::oK;
-    double* flags = Sm + L::oMisc + 4;
+    double* flags = Sm + L::oPoison;
 
     ND_STAMP_BEGIN;
     if (tid == 0) flags[0] = 0.0;
@@ -757,7 +744,7 @@ __device__ void jacobi_nd(double* __restrict__ Sm, const int mbeg, const int men
     double* K = Sm + L::oK;
     double* V = Sm + L::oV;
     double* cs = Sm + L::oCs;
-    double* flags = Sm + L::oMisc + 4;
+    double* flags = Sm + L::oPoison;
     const int nm = mend - mbeg;
     bool warm = true;   // every matrix of the range warm-started
     for (int m = mbeg; m < mend; ++m) warm = warm && ((warm_mask >> m) & 1);
@@ -906,7 +893,7 @@ __device__ void jacobi_nd(double* __restrict__ Sm, const int mbeg, const int men
             double* Z0 = A;                  // [S][LD-strided] (m = 0)
             double* Z1 = Sm + L::oJs;        // [S][S]          (m = 1)
             double* yd = Sm + L::oRed;       // [nm][S] diagonal of Y (the test's scratch slots are free; the flag slot lies beyond)
-            static_assert(2 * S <= 16 * L::ZB, "diagonal corrections must stay below the flag slot of the reduction tile");
+            static_assert(2 * S <= L::kRedTail, "diagonal corrections must stay below the flag slot of the reduction tile");
             for (int e = tid; e < nm * S * S; e += nthr) {      // X over the off-diagonal of K (the diagonal stays)
                 double* Kk = K + (mbeg + e / (S * S)) * NP * LD;
                 const int f = e % (S * S), i = f / S, j = f - i * S;
@@ -1404,7 +1391,7 @@ __device__ void cheb_h_nd(double* __restrict__ Sm, const FilterNdArgs& a, const 
         ND_STAMP(17);
         const int deg = (int)sc[0];
         if (deg < 0) {                            // not converged: tell the block, the caller falls back to Jacobi
-            if (lane == 0) Sm[L::oMisc + 6] = 1.0;
+            if (lane == 0) Sm[L::oChebFail] = 1.0;
             return;
         }
         // ---- h = sum_i c_i T_i(Khat) e_0; row li of Khat is (kr - mid delta) / half
@@ -1550,23 +1537,134 @@ __device__ void cheb_grid_rule_nd(double* __restrict__ Sm, const int ncp, const 
 
 // TK = 0: operator-table transition (sde_cond_moments_tme); TK = 1: Normal closure (tme_normal / Euler--Maruyama)
 // workgroups per CU the register budget is sized for.  Two: a 168-register build (three) spills 234 registers and measured
-// slower at B = 512 (4.1 vs 3.0 ms per 100 steps) AND at B = 2048 (14.2 vs 11.7); MFS_ND_OCC overrides it for A/B runs.
-#ifndef MFS_ND_OCC
-#define MFS_ND_OCC 2
-#endif
-#define ND_TID nd_tid(role64)
+// slower at B = 512 (4.1 vs 3.0 ms per 100 steps) AND at B = 2048 (14.2 vs 11.7).
 // ... and three where the tile is under a third of the CU's 160 KB (TK = 0, N <= 6): without MachineLICM (Makefile) the
 // 168-register build has ONE spilled register, where it had 234
-#ifndef MFS_ND_OCC3
-#define MFS_ND_OCC3 1
-#endif
 template <int N, int TK> constexpr int nd_occ() {
-    return (MFS_ND_OCC3 && MFS_ND_OCC == 2 && TK == 0 && 3 * NdTile<N, TK>::kDoubles * 8 <= 160 * 1024) ? 3 : MFS_ND_OCC;
+    return (TK == 0 && 3 * NdTile<N, TK>::kDoubles * 8 <= 160 * 1024) ? 3 : 2;
+}
+#define ND_TID nd_tid(role64)
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the blocks of a step that more than one half-step (or path of one) uses: ONE definition each, inlined at every call site
+// ---------------------------------------------------------------------------------------------------------------------
+// Node set of a node pass (Normal-closure prediction, joint update): the NCP x NCP Chebyshev grid (cheb_grid_rule_nd; `grid`, Normal
+// closures only) or the reference's s^2 eigen-nodes (both K_k diagonalised by cyclic Jacobi, weights from the eigenvectors).
+// Leaves the coordinates in lam, the weights in W, Rn nodes in rows of Sn, and warm_mask as the next Jacobi run may use it.
+template <int N, int TK>
+__device__ __forceinline__ void nd_node_set(double* __restrict__ Sm, const bool grid, const int ncp, const bool poisoned,
+                                            int& warm_mask, int& Rn, int& Sn, const int role64) {
+    using L = NdTile<N, TK>;
+    Rn = L::R; Sn = L::S;
+    bool on_grid = false;
+    if constexpr (TK == 1) {
+        if (grid) {
+            ND_STAMP_BEGIN;
+            cheb_grid_rule_nd<N, TK>(Sm, ncp, role64);
+            Rn = ncp * ncp; Sn = ncp;
+            warm_mask = 0;        // (the eigenvector tiles were scratch)
+            on_grid = true;
+            ND_STAMP(3);
+        }
+    }
+    if (!on_grid) {
+        jacobi_nd<N, TK>(Sm, 0, 2, poisoned ? 0 : warm_mask, role64);
+        weights_nd<N, TK>(Sm, role64);
+        warm_mask = poisoned ? 0 : 3;
+    }
+}
+
+// A wave whose 64 nodes of the pass at `base` all lie beyond the rule adds zeros: it skips the pass -- at 23 x 23 nodes that is
+// three of the twelve wave-passes, issue slots the co-resident workgroup can use
+__device__ __forceinline__ bool nd_wave_beyond_rule(const int base, const int Rn, const int role64) {
+    return base > 0 && base + (__builtin_amdgcn_readfirstlane(ND_TID) & ~63) >= Rn;
+}
+// (The decode that follows it -- node base + thread id -> inside the rule?, coordinate indices, weight -- stays written out at its
+//  two sites, each naming the other: as a function the <4, 1> kernel's static count of v_fmac_f64 went 2137 -> 1836 and of
+//  v_mul_f64 1120 -> 1026, i.e. the compiler arranged the six extent-specialised copies of the prediction's pass differently.)
+
+// 16-lane emission of a node pass: every thread produces the Z moment terms of its node in the order e(n0, n1) = n0 P -
+// n0 (n0 - 1) / 2 + n1, sixteen at a time go through the transposing row reduction, and lane (class) c of a DPP row keeps entry
+// 16 (e / 16) + c of the row's sum in its slot of `red` ([4 waves x 4 DPP rows][RW]).
+template <int N, int TK>
+__device__ __forceinline__ double* nd_emit_begin(double* __restrict__ Sm, int& lane16, const int role64) {
+    using L = NdTile<N, TK>;
+    lane16 = ND_TID & 15;
+    const int cls = ((lane16 & 1) << 3) | ((lane16 & 2) << 1) | ((lane16 & 4) >> 1) | ((lane16 & 8) >> 3);
+    return Sm + L::oRed + (ND_TID >> 4) * L::RW + cls;
+}
+template <int N, int TK, int e>
+__device__ __forceinline__ void nd_emit(double (&bt)[16], const double vA, const int lane16, double* myred, const int base) {
+    using L = NdTile<N, TK>;
+    bt[e % 16] = vA;
+    if constexpr (e % 16 == 15 || e == L::Z - 1) {
+        if constexpr (e % 16 != 15) static_for<e % 16 + 1, 16>([&](auto Jc) { bt[Jc] = 0.0; });
+        const double v = row_reduce16(bt, lane16);
+        double* slot = myred + 16 * (e / 16);
+        *slot = (base == 0) ? v : *slot + v;
+    }
+}
+// ... and the sum of the 16 partial rows for the moment (n0, n1)
+template <int N, int TK>
+__device__ __forceinline__ double nd_gather_red(const double* __restrict__ Sm, const int n0, const int n1) {
+    using L = NdTile<N, TK>;
+    const double* red = Sm + L::oRed;
+    const int e = n0 * L::P - n0 * (n0 - 1) / 2 + n1;
+    double v = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v += red[q * L::RW + e];
+    return v;
+}
+
+// Publishing moment zi of a half-step: the scaled-mode rescale by `factor()` (each call site keeps its own product order: the
+// running product of a Normal-closure prediction and nd_rescale_ipow round differently), the store, the non-finite flag.
+template <int N, int TK, class F>
+__device__ __forceinline__ void nd_publish_moment(double* __restrict__ Sm, const int zi, double v, const bool scaled, F&& factor) {
+    using L = NdTile<N, TK>;
+    if (scaled) v *= factor();
+    Sm[L::oMom + zi] = v;
+    if (!finite(v)) Sm[L::oHalfFlag] = 1.0;
+}
+__device__ __forceinline__ double nd_rescale_ipow(const double ns0, const double ns1, const int n0, const int n1) {
+    return ipow32(1.0 / ns0, n0) * ipow32(1.0 / ns1, n1);
+}
+
+// End of a half-step: thread 0 writes the new block-uniform state, everybody reads the non-finite flag, thread 0 clears it.
+template <int N, int TK>
+__device__ __forceinline__ void nd_end_half(double* __restrict__ Sm, const bool raw, const bool scaled, const double c0, const double c1,
+                                            const double ns0, const double ns1, bool& bad, const int role64) {
+    using L = NdTile<N, TK>;
+    double* st = Sm + L::oState;
+    if (ND_TID == 0) {
+        if (!raw) { st[0] = c0; st[1] = c1; }
+        if (scaled) { st[2] = ns0; st[3] = ns1; }
+    }
+    __syncthreads();
+    bad = bad || (Sm[L::oHalfFlag] != 0.0);
+    __syncthreads();
+    if (ND_TID == 0) Sm[L::oHalfFlag] = 0.0;
+}
+
+// Posterior shift of an update that formed its sums about the OLD mean in M: p_y = M[0][0], the posterior mean (c0, c1),
+// nell -= log p_y, then the moment array shifted to the posterior mean and divided by p_y.
+template <int N, int TK>
+__device__ __forceinline__ void nd_posterior_shift(double* __restrict__ Sm, const bool raw, const double mean0, const double mean1,
+                                                   double& c0, double& c1, const int role64) {
+    using L = NdTile<N, TK>;
+    constexpr int P = L::P, MLD = L::MLD;
+    const double* M = Sm + L::oM;
+    double* st = Sm + L::oState;
+    const double py = M[0];
+    const double ipy = 1.0 / py;
+    if (!raw) { c0 = fma(M[1 * MLD], ipy, mean0); c1 = fma(M[1], ipy, mean1); }
+    if (ND_TID == 0) st[4] -= fast_log<true>(py);
+    __syncthreads();   // (everybody has read M[0], M[1], M[MLD] before the shift overwrites M)
+    shift_moments_nd<N, TK, P>(Sm, P, P - 1, c0 - mean0, c1 - mean1, ipy, role64);
 }
 template <int N, int TK>
 __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const FilterNdArgs a) {
     using L = NdTile<N, TK>;
-    constexpr int S = L::S, Z = L::Z, P = L::P, NP = L::NP, LD = L::LD, R = L::R, RW = L::RW, ZB = L::ZB;
+    constexpr int S = L::S, Z = L::Z, P = L::P, NP = L::NP, LD = L::LD, RW = L::RW;
     constexpr int NPW = L::NPW, MLD = L::MLD;
     extern __shared__ __attribute__((aligned(16))) double Sm[];
     const int role64 = nd_assign_roles(Sm + L::oMisc);      // 64 x (the role of this wave): a scalar, handed to every helper
@@ -1578,6 +1676,9 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
     double* M = Sm + L::oM;
     const int DD = a.D * a.D;
 
+    // (The set-up below -- tables, then restore or initialise -- and the park at the end stay written out in the kernel: as four
+    //  function templates they kept every static figure, and the operator kernels measured slower with stable = 1, 12.26-12.29 ->
+    //  12.33-12.37 ms on N = 6, T = 500, B = 512; written out again, 12.24-12.27 ms.  profiles/r12_v1/series.txt)
     {
         const double* src = a.coef + (a.coef_batched ? (size_t)b * L::kRows * DD : 0);
         for (int e = tid; e < L::kRows * DD; e += 256) Sm[L::oCoef + e] = src[e];
@@ -1641,7 +1742,7 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
     {
         const double* src = resume ? cw : a.m0 + (a.m0_batched ? (size_t)b * Z : 0);
         for (int e = tid; e < Z; e += 256) mom[e] = src[e];
-        if (resume) for (int e = tid; e < 2 * NP * LD; e += 256) Sm[L::oV + e] = cw[Z + 8 + e];
+        if (resume) for (int e = tid; e < 2 * NP * LD; e += 256) Sm[L::oV + e] = cw[L::cV + e];
     }
     // The block-uniform state (mean, scale, nell) lives in LDS: st[0..4].  Every thread computes the new values identically from
     // LDS data (no broadcast is needed), thread 0 writes them back at the end of a half-step, and each half-step reads them
@@ -1651,15 +1752,14 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
     if (tid == 0) {
         double m0v = 0.0, m1v = 0.0, s0v = 1.0, s1v = 1.0, nl = 0.0;
         if (resume) {
-            m0v = cw[Z]; m1v = cw[Z + 1]; s0v = cw[Z + 2]; s1v = cw[Z + 3]; nl = cw[Z + 4];
+            m0v = cw[L::cMean]; m1v = cw[L::cMean + 1]; s0v = cw[L::cScale]; s1v = cw[L::cScale + 1]; nl = cw[L::cNell];
         } else {
             if (!raw) { const double* m = a.mean0 + (a.m0_batched ? 2 * b : 0); m0v = m[0]; m1v = m[1]; }
             if (scaled) { const double* m = a.scale0 + (a.m0_batched ? 2 * b : 0); s0v = m[0]; s1v = m[1]; }
         }
         st[0] = m0v; st[1] = m1v; st[2] = s0v; st[3] = s1v; st[4] = nl;
     }
-    double* red = Sm + L::oRed;
-    if (tid == 0) { red[16 * ZB] = 0.0; Sm[L::oMisc + 5] = resume ? cw[Z + 5] : __hiloint2double(0, -1); }   // flag slot 1: step of the first non-finite result (an int in the low word)
+    if (tid == 0) { Sm[L::oHalfFlag] = 0.0; Sm[L::oFirstNan] = resume ? cw[L::cFirstNan] : __hiloint2double(0, -1); }   // flag slot 1: step of the first non-finite result (an int in the low word)
     // which matrices an update diagonalises: the components a likelihood factor reads
     // (component 2 = a factor of BOTH components, e.g. a bearing measurement: no bilinear form of matrix functions exists for
     //  it; Normal-closure kernels integrate it over their node set -- Chebyshev grid or eigen-nodes -- like the prediction)
@@ -1688,9 +1788,10 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
             if (tid < ncp) Sm[L::oChG + tid] = cospi(((double)tid + 0.5) / (double)ncp);
         }
     }
+    double* red = Sm + L::oRed;
     __syncthreads();
-    bool dead = resume ? (cw[Z + 6] != 0.0) : false;
-    int warm_mask = resume ? (int)cw[Z + 7] : 0;
+    bool dead = resume ? (cw[L::cDead] != 0.0) : false;
+    int warm_mask = resume ? (int)cw[L::cWarm] : 0;
     const double qnan = __builtin_nan("");
     const double* yrow = a.ys + (size_t)b * a.T * a.ny;
     double* bx = Sm + L::oBx;
@@ -1700,6 +1801,11 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
         if (!dead) {
             bool bad = false;
 
+            // (The four bodies of a step -- operator prediction, Normal-closure prediction, joint update, separable update -- stay
+            //  written out below.  As function templates each was inlined back, yet the compiler laid several kernels out
+            //  differently: the operator prediction changed the static v_mfma count of <7, 2> 21 -> 28, the joint update
+            //  v_fmac_f64 of <5, 1> 2566 -> 2594, the separable update raised the scratch of <6, 3> 56 -> 100 bytes, and cut at
+            //  its stamp into two functions it moved v_fmac_f64 of <5, 0> 1376 -> 1496.  profiles/r12_v1 has the figures.)
             // The two half-steps share ONE call site of the front end (inlined there: as a called function it saved and
             // restored two dozen callee-saved registers through scratch on every call, and twice inlined it doubles the
             // largest piece of straight-line code in the kernel).
@@ -1856,10 +1962,8 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                         if ((ND_TID & 127) < Z) part[pair * Z + (ND_TID & 127)] = v;
                         __syncthreads();
                         if (ND_TID < Z) {
-                            double v = (part[ND_TID] + part[Z + ND_TID]) + M[zn0 * MLD + zn1];
-                            if (scaled) v *= ipow32(1.0 / ns0, zn0) * ipow32(1.0 / ns1, zn1);
-                            mom[ND_TID] = v;
-                            if (!finite(v)) red[16 * ZB] = 1.0;
+                            const double v = (part[ND_TID] + part[Z + ND_TID]) + M[zn0 * MLD + zn1];
+                            nd_publish_moment<N, TK>(Sm, ND_TID, v, scaled, [&] { return nd_rescale_ipow(ns0, ns1, zn0, zn1); });
                         }
                     }
                     ND_STAMP(6);
@@ -1868,18 +1972,8 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                     //      Stein recursion (equal to raw_moments_mvn_kan(mu(x) - c, S(x), (a, b)), moments.py:110-154)
                     //      -- or, when the degree of the integrands allows, the Chebyshev grid with the weights of the same
                     //      bilinear form (cheb_grid_rule_nd: no eigen-decomposition)
-                    int Rn = R, Sn = S;
-                    if (ncp > 0) {
-                        ND_STAMP_BEGIN;
-                        cheb_grid_rule_nd<N, TK>(Sm, ncp, role64);
-                        Rn = ncp * ncp; Sn = ncp;
-                        warm_mask = 0;        // (the eigenvector tiles were scratch)
-                        ND_STAMP(3);
-                    } else {
-                        jacobi_nd<N, TK>(Sm, 0, 2, poisoned ? 0 : warm_mask, role64);
-                        weights_nd<N, TK>(Sm, role64);
-                        warm_mask = poisoned ? 0 : 3;
-                    }
+                    int Rn, Sn;
+                    nd_node_set<N, TK>(Sm, ncp > 0, ncp, poisoned, warm_mask, Rn, Sn, role64);
                     ND_STAMP_BEGIN;
                     constexpr int LS = L::LS;
                     const double* lam = Sm + L::oLam;
@@ -1902,12 +1996,12 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                     s0 = wave_sum64(s0); s1 = wave_sum64(s1);
                     if (scaled) { s2 = wave_sum64(s2); s3 = wave_sum64(s3); }
                     if ((ND_TID & 63) == 0) {
-                        double* r3 = red + 4 * RW * (ND_TID >> 6) + 16 * ZB;
+                        double* r3 = red + 4 * RW * (ND_TID >> 6) + L::kRedTail;
                         r3[1] = s0; r3[2] = s1; r3[4] = s2; r3[5] = s3;
                     }
                     __syncthreads();
                     {
-                        const double* q = red + 16 * ZB;
+                        const double* q = red + L::kRedTail;
                         s0 = q[1] + q[4 * RW + 1] + q[8 * RW + 1] + q[12 * RW + 1];
                         s1 = q[2] + q[4 * RW + 2] + q[8 * RW + 2] + q[12 * RW + 2];
                         s2 = q[4] + q[4 * RW + 4] + q[8 * RW + 4] + q[12 * RW + 4];
@@ -1916,20 +2010,17 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                     if (!raw) { c0 = s0; c1 = s1; }
                     if (scaled) { ns0 = sqrt(s2); ns1 = sqrt(s3); }
                     ND_STAMP(6);
-                    const int lane16 = ND_TID & 15;
-                    const int cls = ((lane16 & 1) << 3) | ((lane16 & 2) << 1) | ((lane16 & 4) >> 1) | ((lane16 & 8) >> 3);
-                    double* myred = red + (ND_TID >> 4) * RW + cls;
+                    int lane16;
+                    double* myred = nd_emit_begin<N, TK>(Sm, lane16, role64);
                     //   M(0,b) = m_1 M(0,b-1) + (b-1) S_11 M(0,b-2)
                     //   M(a,b) = m_0 M(a-1,b) + (a-1) S_00 M(a-2,b) + b S_01 M(a-1,b-1)
                     // three rows of the table live at a time; entries are emitted row by row: slot e(a, b) = a P - a(a-1)/2 + b
                     dispatch_extent<L::kMaxD>(a.D, [&](auto Dc) {
                     for (int base = 0; base < Rn; base += 256) {
-                        // (a wave whose 64 nodes of this pass all lie beyond the rule adds zeros: it skips the pass -- at 23 x 23
-                        //  nodes that is three of the twelve wave-passes, issue slots the co-resident workgroup can use)
-                        if (base > 0 && base + (__builtin_amdgcn_readfirstlane(ND_TID) & ~63) >= Rn) continue;
+                        if (nd_wave_beyond_rule(base, Rn, role64)) continue;
                         double wA, mA0, mA1, sA00, sA01, sA11;
                         {
-                            const int eA = base + ND_TID;
+                            const int eA = base + ND_TID;       // (node decode: twin in the joint update's node pass)
                             const bool okA = eA < Rn;
                             const int iA0 = okA ? eA / Sn : 0, iA1 = okA ? eA - iA0 * Sn : 0;
                             wA = okA ? W[eA] : 0.0;
@@ -1958,14 +2049,7 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                                     if constexpr (n1 >= 1) vA = fma((double)n1 * sA01, MA[r1][n1 - 1], vA);
                                 }
                                 MA[r][n1] = vA;
-                                constexpr int e = n0 * P - n0 * (n0 - 1) / 2 + n1;
-                                bt[e % 16] = vA;
-                                if constexpr (e % 16 == 15 || e == Z - 1) {
-                                    if constexpr (e % 16 != 15) static_for<e % 16 + 1, 16>([&](auto Jc) { bt[Jc] = 0.0; });
-                                    const double v = row_reduce16(bt, lane16);
-                                    double* slot = myred + 16 * (e / 16);
-                                    *slot = (base == 0) ? v : *slot + v;
-                                }
+                                nd_emit<N, TK, n0 * P - n0 * (n0 - 1) / 2 + n1>(bt, vA, lane16, myred, base);
                             });
                         });
                     }
@@ -1973,31 +2057,18 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                     __syncthreads();
                     if (ND_TID < Z) {
                         int zn0, zn1; nd_exponents(min(ND_TID & 127, Z - 1), zn0, zn1);    // the moment this thread owns (ND_TID & 127 < Z)
-                        const int zi = ND_TID, n0 = zn0, n1 = zn1;
-                        const int e = n0 * P - n0 * (n0 - 1) / 2 + n1;    // predictions of a Normal closure emit row by row
-                        double v = 0.0;
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) v += red[q * RW + e];
-                        if (scaled) {
+                        const double v = nd_gather_red<N, TK>(Sm, zn0, zn1);
+                        nd_publish_moment<N, TK>(Sm, ND_TID, v, scaled, [&] {     // (a running product, not nd_rescale_ipow: it rounds differently)
                             const double i0 = 1.0 / ns0, i1 = 1.0 / ns1;
                             double f = 1.0;
-                            for (int q = 0; q < n0; ++q) f *= i0;
-                            for (int q = 0; q < n1; ++q) f *= i1;
-                            v *= f;
-                        }
-                        mom[zi] = v;
-                        if (!finite(v)) red[16 * ZB] = 1.0;  // slot Z of the first row flags a non-finite moment
+                            for (int q = 0; q < zn0; ++q) f *= i0;
+                            for (int q = 0; q < zn1; ++q) f *= i1;
+                            return f;
+                        });
                     }
                     ND_STAMP(7);
                 }
-                if (ND_TID == 0) {
-                    if (!raw) { st[0] = c0; st[1] = c1; }
-                    if (scaled) { st[2] = ns0; st[3] = ns1; }
-                }
-                __syncthreads();
-                bad = bad || (red[16 * ZB] != 0.0);
-                __syncthreads();
-                if (ND_TID == 0) red[16 * ZB] = 0.0;
+                nd_end_half<N, TK>(Sm, raw, scaled, c0, c1, ns0, ns1, bad, role64);
             }
             // =========================================================================================================
             // update (filtering.py:268-275 / :333-339 / :192-202): bilinear form with h_k = lik_k(X_k) e_0
@@ -2008,7 +2079,7 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                 // Cyclic Jacobi + spectral evaluation (and a binomial shift of the moment array) only if the coefficients of
                 // some factor have not converged.
                 ND_STAMP_BEGIN;
-                if (ND_TID == 0) Sm[L::oMisc + 6] = 0.0;
+                if (ND_TID == 0) Sm[L::oChebFail] = 0.0;
                 // this step's measurements (loaded at the top of the step -- 1.5 k cycles earlier -- they cost four registers
                 // across the prediction and the front end, and the pass got 3 % slower)
                 double ypre[MFS_ND_MAX_FACTORS];
@@ -2026,31 +2097,17 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                     //      the weights Omega of the rule's bilinear form, exact for polynomial integrands only -- l is interpolated
                     //      on a Gershgorin box, which on the same example costs the odd high moments five digits (7e-5)
                     done_joint = true;
-                    int Rn = R, Sn = S;
-                    bool on_grid = false;
-                    if constexpr (TK == 1) {
-                        if (a.joint_grid && ncp > 0) {
-                            cheb_grid_rule_nd<N, TK>(Sm, ncp, role64);
-                            Rn = ncp * ncp; Sn = ncp;
-                            warm_mask = 0;
-                            on_grid = true;
-                        }
-                    }
-                    if (!on_grid) {
-                        jacobi_nd<N, TK>(Sm, 0, 2, poisoned ? 0 : warm_mask, role64);
-                        weights_nd<N, TK>(Sm, role64);
-                        warm_mask = poisoned ? 0 : 3;
-                    }
+                    int Rn, Sn;
+                    nd_node_set<N, TK>(Sm, a.joint_grid && ncp > 0, ncp, poisoned, warm_mask, Rn, Sn, role64);
                     constexpr int LS = L::LS;
                     const double* lam = Sm + L::oLam;
                     const double* W = Sm + L::oW;
                     const double yv = ypre[0];
-                    const int lane16 = ND_TID & 15;
-                    const int cls = ((lane16 & 1) << 3) | ((lane16 & 2) << 1) | ((lane16 & 4) >> 1) | ((lane16 & 8) >> 3);
-                    double* myred = red + (ND_TID >> 4) * RW + cls;
+                    int lane16;
+                    double* myred = nd_emit_begin<N, TK>(Sm, lane16, role64);
                     for (int base = 0; base < Rn; base += 256) {
-                        if (base > 0 && base + (__builtin_amdgcn_readfirstlane(ND_TID) & ~63) >= Rn) continue;     // (as in the prediction's node pass)
-                        const int eA = base + ND_TID;
+                        if (nd_wave_beyond_rule(base, Rn, role64)) continue;
+                        const int eA = base + ND_TID;           // (node decode: twin in the Normal-closure prediction's node pass)
                         const bool okA = eA < Rn;
                         const int iA0 = okA ? eA / Sn : 0, iA1 = okA ? eA - iA0 * Sn : 0;
                         const double xi0 = lam[iA0] * scale0, xi1 = lam[LS + iA1] * scale1;      // node - mean
@@ -2064,40 +2121,23 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                                 if constexpr (n0 == 0) { if constexpr (n1 == 0) vA = wl; else vA = xi1 * MA[0][n1 - 1]; }
                                 else vA = xi0 * MA[r1][n1];
                                 MA[r][n1] = vA;
-                                constexpr int e = n0 * P - n0 * (n0 - 1) / 2 + n1;
-                                bt[e % 16] = vA;
-                                if constexpr (e % 16 == 15 || e == Z - 1) {
-                                    if constexpr (e % 16 != 15) static_for<e % 16 + 1, 16>([&](auto Jc) { bt[Jc] = 0.0; });
-                                    const double v = row_reduce16(bt, lane16);
-                                    double* slot = myred + 16 * (e / 16);
-                                    *slot = (base == 0) ? v : *slot + v;
-                                }
+                                nd_emit<N, TK, n0 * P - n0 * (n0 - 1) / 2 + n1>(bt, vA, lane16, myred, base);
                             });
                         });
                     }
                     __syncthreads();
                     if (ND_TID < Z) {          // the sums about the OLD mean into the moment array
                         int zn0, zn1; nd_exponents(min(ND_TID & 127, Z - 1), zn0, zn1);    // the moment this thread owns (ND_TID & 127 < Z)
-                        const int n0 = zn0, n1 = zn1;
-                        const int e = n0 * P - n0 * (n0 - 1) / 2 + n1;
-                        double v = 0.0;
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) v += red[q * RW + e];
-                        M[n0 * MLD + n1] = v;
+                        M[zn0 * MLD + zn1] = nd_gather_red<N, TK>(Sm, zn0, zn1);
                     }
                     __syncthreads();
-                    const double py = M[0];
-                    const double ipy = 1.0 / py;
-                    if (!raw) { c0 = fma(M[1 * MLD], ipy, mean0); c1 = fma(M[1], ipy, mean1); }
-                    if (ND_TID == 0) st[4] -= fast_log<true>(py);
-                    __syncthreads();   // (everybody has read M[0], M[1], M[MLD] before the shift overwrites M)
-                    shift_moments_nd<N, TK, P>(Sm, P, P - 1, c0 - mean0, c1 - mean1, ipy, role64);
+                    nd_posterior_shift<N, TK>(Sm, raw, mean0, mean1, c0, c1, role64);
                   }
                 }
                 if (!done_joint) {
-                cheb_h_nd<N, TK>(Sm, a, (MFS_ND_FORCE_JACOBI || a.force_eigen) ? 0 : lik_mask, ypre, mean0, mean1, scale0, scale1, role64);
+                cheb_h_nd<N, TK>(Sm, a, a.force_eigen ? 0 : lik_mask, ypre, mean0, mean1, scale0, scale1, role64);
                 __syncthreads();
-                if (MFS_ND_FORCE_JACOBI || a.force_eigen || Sm[L::oMisc + 6] != 0.0) {
+                if (a.force_eigen || Sm[L::oChebFail] != 0.0) {
                     jacobi_nd<N, TK>(Sm, ubeg, uend, poisoned ? 0 : warm_mask, role64);
                     warm_mask = poisoned ? 0 : (warm_mask | lik_mask);
                     __syncthreads();
@@ -2148,12 +2188,7 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                     ND_STAMP(15);
                     bilinear_moments_nd<N, TK>(Sm, P, P - 1, scale0, scale1, 1.0, role64);
                     __syncthreads();
-                    const double py = M[0];
-                    const double ipy = 1.0 / py;
-                    if (!raw) { c0 = fma(M[1 * MLD], ipy, mean0); c1 = fma(M[1], ipy, mean1); }
-                    if (ND_TID == 0) st[4] -= fast_log<true>(py);
-                    __syncthreads();   // (everybody has read M[0], M[1], M[MLD] before the shift overwrites M)
-                    shift_moments_nd<N, TK, P>(Sm, P, P - 1, c0 - mean0, c1 - mean1, ipy, role64);
+                    nd_posterior_shift<N, TK>(Sm, raw, mean0, mean1, c0, c1, role64);
                 } else {
                     // p_y = h_0 . h_1 and the first moments (K_0 h_0) . h_1, h_0 . (K_1 h_1): every wave forms them itself (lane
                     // products and three wave sums), so no broadcast is needed
@@ -2179,21 +2214,10 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
                 double ns0 = 1.0, ns1 = 1.0;
                 if (scaled) { ns0 = sqrt(M[2 * MLD]); ns1 = sqrt(M[2]); }   // posterior standard deviations (:195-197)
                 if (ND_TID < Z) {
-                    const int zi = ND_TID;
                     int zn0, zn1; nd_exponents(min(ND_TID & 127, Z - 1), zn0, zn1);    // the moment this thread owns (ND_TID & 127 < Z)
-                    double v = M[zn0 * MLD + zn1];
-                    if (scaled) v *= ipow32(1.0 / ns0, zn0) * ipow32(1.0 / ns1, zn1);
-                    mom[zi] = v;
-                    if (!finite(v)) red[16 * ZB] = 1.0;
+                    nd_publish_moment<N, TK>(Sm, ND_TID, M[zn0 * MLD + zn1], scaled, [&] { return nd_rescale_ipow(ns0, ns1, zn0, zn1); });
                 }
-                if (ND_TID == 0) {
-                    if (!raw) { st[0] = c0; st[1] = c1; }
-                    if (scaled) { st[2] = ns0; st[3] = ns1; }
-                }
-                __syncthreads();
-                bad = bad || (red[16 * ZB] != 0.0);
-                __syncthreads();
-                if (ND_TID == 0) red[16 * ZB] = 0.0;
+                nd_end_half<N, TK>(Sm, raw, scaled, c0, c1, ns0, ns1, bad, role64);
                 ND_STAMP(7);
 #ifdef MFS_ND_STAMPS
                 if (blockIdx.x == 0 && nd_tid(role64) == 0) g_nd_stamps[9] += 1;
@@ -2201,7 +2225,7 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
             }
             }   // half
             bad = bad || !finite(st[4]) || !finite(st[0]) || !finite(st[1]) || !finite(st[2]) || !finite(st[3]);
-            if (bad) { dead = true; if (tid == 0) Sm[L::oMisc + 5] = __hiloint2double(0, t); }
+            if (bad) { dead = true; if (tid == 0) Sm[L::oFirstNan] = __hiloint2double(0, t); }
         } else {
             for (int zi = tid; zi < Z; zi += 256) mom[zi] = qnan;
             if (tid == 0) {
@@ -2225,14 +2249,14 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
     }
     if (a.t_end < a.T && cw) {      // not the last chunk: park the state
         for (int e = tid; e < Z; e += 256) cw[e] = mom[e];
-        for (int e = tid; e < 2 * NP * LD; e += 256) cw[Z + 8 + e] = Sm[L::oV + e];
+        for (int e = tid; e < 2 * NP * LD; e += 256) cw[L::cV + e] = Sm[L::oV + e];
         if (tid == 0) {
-            cw[Z] = st[0]; cw[Z + 1] = st[1]; cw[Z + 2] = st[2]; cw[Z + 3] = st[3]; cw[Z + 4] = st[4];
-            cw[Z + 5] = Sm[L::oMisc + 5]; cw[Z + 6] = dead ? 1.0 : 0.0; cw[Z + 7] = (double)warm_mask;
+            cw[L::cMean] = st[0]; cw[L::cMean + 1] = st[1]; cw[L::cScale] = st[2]; cw[L::cScale + 1] = st[3]; cw[L::cNell] = st[4];
+            cw[L::cFirstNan] = Sm[L::oFirstNan]; cw[L::cDead] = dead ? 1.0 : 0.0; cw[L::cWarm] = (double)warm_mask;
         }
     } else if (tid == 0) {
         a.out_nell[b] = st[4];
-        if (a.out_first_nan) a.out_first_nan[b] = __double2loint(Sm[L::oMisc + 5]);
+        if (a.out_first_nan) a.out_first_nan[b] = __double2loint(Sm[L::oFirstNan]);
     }
 }
 

@@ -43,10 +43,6 @@ int run(int argc, char** argv) {
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms = 0; hipEventElapsedTime(&ms, e0, e1);
         printf("B = %d, T = %d: %.3f ms per pass (diagnostic build), lds %d B\n", B, T, ms / 3, lds);
-#ifdef MFS_ND_ROLE_DEBUG
-        unsigned fb[2]; hipMemcpyFromSymbol(fb, HIP_SYMBOL(g_nd_role_fallbacks), sizeof(fb));
-        printf("role fallbacks %u, workgroups whose wave 0 is not role 0: %u (of %d launched)\n", fb[0], fb[1], 4 * B);
-#endif
         return 0;
     }
 #ifndef MFS_ND_STAMPS
