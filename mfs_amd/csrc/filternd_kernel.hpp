@@ -27,7 +27,8 @@
 //            separable: it is integrated on an NCP x NCP Chebyshev grid with the weights Omega_pq = (l_p(X_0) e_0)^T (l_q(X_1) e_0)
 //            of the same bilinear form (cheb_grid_rule_nd) -- exact, because NCP exceeds the integrands' degree per variable --
 //            and the Stein recursion runs per grid point, 16 moments at a time through a transposing DPP row reduction.  Only
-//            when NCP would not fit its table are the reference's s^2 eigen-nodes formed (both K_k diagonalised by cyclic Jacobi).
+//            when NCP would not fit its table, or at N = 7 exceeds kNcpGrid (a larger grid loses the degree-13 moments), are the
+//            reference's s^2 eigen-nodes formed (both K_k diagonalised by cyclic Jacobi).
 //   update, a likelihood of BOTH components (fac_component = 2; examples/2d_bearing_only.ipynb): Normal-closure kernels only --
 //            sum_ij W_ij l(y, x_ij) xi_0^a xi_1^b over the reference's own s^2 eigen-nodes (filtering.py:263-275).
 // Front end of every rule (front_nd): H_k = P_k G+ with G+ the Gram matrix extended by the degree-N monomials, so
@@ -159,6 +160,15 @@ struct NdTile {
     static constexpr int LD = NP + 1;
     static constexpr int R = S * S;                  // tensor-product nodes
     static constexpr int kNcpMax = (N <= 6) ? 34 : 28;     // largest Chebyshev grid per variable; 34 = 3 (2 N - 1) + 1 at N = 6: TME-normal-3 of a quadratic drift
+    // The largest grid a prediction takes.  The grid spans the box of the spectra, where the degree-(2N - 1) integrands reach
+    // (R / sigma)^(2N - 1) times the moment they sum to, and the grid's weights change sign; the loss grows with N and with NCP.
+    // Measured against the oracle (tests/test_gpu_nd_envelope.py), worst moment: N <= 6 at most 7e-8 (NCP = 34); N = 7 1.2e-6 with
+    // mean and covariance of degree 2 (lv2's Euler closure, NCP = 27), past the 1e-6 parity bar, and 3.6e-7 with a linear mean
+    // (lin2, NCP = 14); the eigen-nodes, whose weights do not cancel, give 1.5e-10 and 3.9e-9 but cost two Jacobi runs per rule
+    // (lv2 Euler, N = 7, B = 512, T = 100: 46.3 ms a call against 10.3 ms on its 27-point grid; a 14-point grid: 6.6 ms).  So at
+    // N = 7 only NCP <= 14 (degree 1 per variable in the mean, 2 in the covariance) keeps its grid, inside the bar; every other
+    // closure takes the eigen-nodes.
+    static constexpr int kNcpGrid = (N <= 6) ? kNcpMax : 14;
     static constexpr int oMom = 0;
     static constexpr int oK = (Z + 1) & ~1;          // [2][NP][LD]
     static constexpr int oV = oK + 2 * NP * LD;      // [2][NP][LD]
@@ -1780,6 +1790,7 @@ __global__ __launch_bounds__(256, (nd_occ<N, TK>())) void filternd_kernel(const 
         ncp = g * (P - 1) + 1;
         if (joint && a.joint_grid) ncp = L::kNcpMax;     // (A/B: a joint likelihood on the same grid -- take all the tables hold)
         if (ncp > L::kNcpMax || a.force_eigen) ncp = 0;   // (table size)
+        else if (ncp > L::kNcpGrid && !(joint && a.joint_grid)) ncp = 0;   // (accuracy of the high moments, N = 7)
         if (ncp > 0) {
             for (int e = tid; e < ncp * ncp; e += 256) {
                 const int aa = e / ncp, pp = e - aa * ncp;
