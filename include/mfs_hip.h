@@ -482,6 +482,45 @@ int mfs_grid_filter_1d(int n, int T, int B, int substeps, int use_power,
                        const double* init_ps, int init_batched, const double* ys,
                        double* out_pdfs, double* out_means, double* out_vars,
                        double* out_nell, int32_t* out_first_nan, int device, void* stream);
+/*
+ * The same filter, and on request the characteristic function of every posterior: the `true_filtering_cfs` that
+ * dardel/benes_bernoulli/post_processing_brute_force.py:27-50 takes with characteristic_from_pdf (mfs/one_dim/moments.py:340-343)
+ * of the downloaded pdfs, the ground truth of the cf errors of dardel/benes_bernoulli/compute_errs.py:103-113:
+ *   out_cfs[b][t][k] = sum_i w_i exp(i zs[k] x_i) p_{b,t}(x_i)                  (w = the weights of jnp.trapz(., xs))
+ * as one more product per measurement on the matrix core, with a table of w_i cos(zs[k] x_i) and w_i sin(zs[k] x_i) built
+ * once per call from fp64 sincos of the rounded product (any finite zs: no spacing is assumed).
+ *   nz, zs       frequencies, 0 .. MFS_GRID_MAX_NZ of them; zs [nz], finite.  nz = 0: zs and out_cfs may be NULL, and the
+ *                call is mfs_grid_filter_1d (which forwards here), bit for bit
+ *   out_cfs      [B][T][nz][2] = (re, im) pairs, i.e. a C-contiguous complex128 array.  Nothing of that size exists on the
+ *                device: the pairs leave in blocks of a few steps while the next steps are computed
+ *   every other argument as in mfs_grid_filter_1d; the other outputs do not depend on nz.
+ * A replicate whose normaliser was zero or not finite at step t has NaN in both parts from step t on (out_first_nan), and only
+ * that replicate.  The sum over i runs in ascending order in one wave: two calls return the same bits, and a replicate's cfs
+ * do not depend on the batch it is in.  MFS_EINVAL, besides those of mfs_grid_filter_1d: nz < 0, nz > 0 with zs or out_cfs
+ * NULL, a zs entry that is not finite.  MFS_EUNSUPPORTED: nz > MFS_GRID_MAX_NZ (the table is 2 nz n doubles, padded: 1 GB at
+ * 8192 x 8192).
+ */
+#define MFS_GRID_MAX_NZ 8192
+int mfs_grid_filter_1d_cf(int n, int T, int B, int substeps, int use_power,
+                          const double* xs, const double* trans_mean, const double* trans_sd,
+                          int lik_kind, int n_lik, const double* lik, int lik_batched,
+                          const double* init_ps, int init_batched, const double* ys,
+                          int nz, const double* zs,
+                          double* out_pdfs, double* out_means, double* out_vars, double* out_cfs /* [B][T][nz][2] */,
+                          double* out_nell, int32_t* out_first_nan, int device, void* stream);
+/*
+ * characteristic_from_pdf (mfs/one_dim/moments.py:340-343) on its own, for densities that did not come from the filter (a saved
+ * run, a reconstructed pdf): out[c][k] = sum_i w_i exp(i zs[k] xs[i]) ps[c][i], the trapezoid rule on xs.  Same table kernel and
+ * same GEMM as mfs_grid_filter_1d_cf, with the table transposed so that the densities are used as they lie.
+ *   n, xs        grid points (2 .. MFS_GRID_MAX_N), [n] finite and strictly increasing (uneven spacing allowed)
+ *   count, ps    densities, [count][n];  nz, zs as above;  out [count][nz][2] = (re, im) pairs
+ * Host pointers; the densities are staged in chunks of rows, so the device holds the table and one chunk whatever `count` is.
+ * Rows are independent: a NaN in ps[c] makes out[c] NaN and nothing else.  Two calls return the same bits.  count = 0 or nz = 0
+ * returns at once.  MFS_EINVAL: n < 2, count < 0, nz < 0, a NULL buffer, xs not strictly increasing, a zs entry that is not
+ * finite.  MFS_EUNSUPPORTED: n > MFS_GRID_MAX_N, nz > MFS_GRID_MAX_NZ.
+ */
+int mfs_cf_from_pdf_1d(int n, int count, int nz, const double* xs, const double* zs, const double* ps /* [count][n] */,
+                       double* out /* [count][nz][2] */, int device, void* stream);
 /* diagnostic: the filter's fp64 matrix-core GEMM on its own, C[M][N] = A[M][K] B[K][N], row-major DEVICE pointers, enqueued
  * on `stream`.  M and N must be multiples of 64 and K of 16 (the filter pads its buffers to that), C distinct from A and B:
  * MFS_EINVAL otherwise.  The sum over k runs in ascending order in one wave: bit-reproducible. */

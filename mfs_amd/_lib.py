@@ -15,6 +15,7 @@ UMAP = {'x': 0, 'tanh': 1}
 LIK = {'bernoulli_logistic': 0, 'poisson_softplus': 1, 'gaussian': 2, 'bearing_gaussian': 3}
 MAX_N = 32
 GRID_MAX_N = 8192   # MFS_GRID_MAX_N: grid points of the brute-force grid filter
+GRID_MAX_NZ = 8192  # MFS_GRID_MAX_NZ: frequencies of its characteristic functions
 PF_MAX_PARTICLES = 1 << 20   # MFS_PF_MAX_PARTICLES: particles per replicate of the bootstrap particle filter
 PF_MAX_MIX = 8               # MFS_PF_MAX_MIX: components of its initial mixture
 RESAMPLE = {'stratified': 0, 'systematic': 1}   # MFS_RESAMPLE_*
@@ -153,6 +154,9 @@ _SIGNATURES = [
     ('mfs_elementary', _i, [_i, _i, _vp, _vp, _i]),
     ('mfs_grid_filter_1d', _i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ('mfs_grid_filter_1d_cf', _i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    ('mfs_cf_from_pdf_1d', _i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     ('mfs_grid_gemm_dev', _i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     ('mfs_particle_filter_1d', _i, [C.POINTER(MfsModel1d), _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

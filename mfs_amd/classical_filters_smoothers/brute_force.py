@@ -17,7 +17,7 @@ from mfs_amd.one_dim.filtering import _trace_likelihood
 from mfs_amd.one_dim.moments import _trace_sde
 from mfs_amd.tme_poly import TransitionTables, euler_tables, tme_tables
 
-__all__ = ['brute_force_filter', 'GridFilterResult', 'transition_on_grid']
+__all__ = ['brute_force_filter', 'GridFilterResult', 'GridFilterCFResult', 'transition_on_grid']
 
 _LIK_KINDS = ('bernoulli_logistic', 'poisson_softplus', 'gaussian')
 
@@ -31,6 +31,30 @@ class GridFilterResult(NamedTuple):
     variances: np.ndarray
     nell: np.ndarray
     first_nan: np.ndarray
+
+
+class GridFilterCFResult(NamedTuple):
+    """The five fields of `GridFilterResult`, then cfs (B, T, m) complex128: the characteristic function of each posterior at
+    the frequencies `zs`, trapezoid rule on the grid; NaN in both parts for a replicate from its `first_nan` on."""
+    pdfs: Optional[np.ndarray]
+    means: np.ndarray
+    variances: np.ndarray
+    nell: np.ndarray
+    first_nan: np.ndarray
+    cfs: np.ndarray
+
+
+def _check_zs(zs) -> np.ndarray:
+    """The frequencies of a characteristic function on the grid as a contiguous (m,) float64 array."""
+    zs = np.asarray(zs, dtype=np.float64)
+    if zs.ndim != 1 or zs.shape[0] < 1:
+        raise ValueError(f'zs must have shape (m,) with m >= 1, got {zs.shape}')
+    zs = np.ascontiguousarray(zs)
+    if zs.shape[0] > _lib.GRID_MAX_NZ:
+        raise ValueError(f'm = {zs.shape[0]} frequencies exceed the supported {_lib.GRID_MAX_NZ}')
+    if not np.all(np.isfinite(zs)):
+        raise ValueError('zs must be finite')
+    return zs
 
 
 def _transition_tables(drift: Callable, dispersion: Callable, ddt: float, pred_method: str) -> TransitionTables:
@@ -68,7 +92,8 @@ def transition_on_grid(drift: Callable, dispersion: Callable, xs, dt: float, int
 
 def brute_force_filter(drift: Callable, dispersion: Callable, measurement_cond_pdf: Callable, init_ps, xs, ys, dt,
                        integration_steps: int = 1, pred_method: str = 'chapman-tme-2', *,
-                       return_pdfs: bool = True, return_summaries: bool = False, route: str = 'auto', device: int = 0):
+                       return_pdfs: bool = True, return_summaries: bool = False, route: str = 'auto', device: int = 0,
+                       zs=None):
     """Brute-force computing the true filtering solution of a 1-D state on a grid
     (mfs/classical_filters_smoothers/brute_force.py:26-136, the 'chapman-euler' and 'chapman-tme-k' predictors).
 
@@ -84,12 +109,19 @@ def brute_force_filter(drift: Callable, dispersion: Callable, measurement_cond_p
                            when S > 1
     return_pdfs            False: nothing of size B * T * n is allocated, on the host or the device
     return_summaries       True: return a `GridFilterResult`
+    zs                     (m,) frequencies: also compute the characteristic function of every posterior on the device,
+                           trapz(exp(i z x) p, x) -- the `true_filtering_cfs` of
+                           dardel/benes_bernoulli/post_processing_brute_force.py:27-50 -- and return a `GridFilterCFResult`
+                           (implies return_summaries; with return_pdfs=False the pdfs never leave the device)
 
-    Returns the (T, n) or (B, T, n) filtering pdfs, as the reference does, or a `GridFilterResult`.  A replicate whose
-    normaliser is zero or not finite is NaN from that step on (see `first_nan`); the others are unaffected.
+    Returns the (T, n) or (B, T, n) filtering pdfs, as the reference does, or a `GridFilterResult` / `GridFilterCFResult`.
+    A replicate whose normaliser is zero or not finite is NaN from that step on (see `first_nan`); the others are unaffected.
     """
     if route not in ('auto', 'power', 'stepwise'):
         raise ValueError(f"route must be 'auto', 'power' or 'stepwise', got {route!r}")
+    if zs is not None:
+        zs = _check_zs(zs)
+        return_summaries = True
     if not (return_pdfs or return_summaries):
         raise ValueError('nothing to return: return_pdfs and return_summaries are both False')
     S = int(integration_steps)
@@ -128,14 +160,16 @@ def brute_force_filter(drift: Callable, dispersion: Callable, measurement_cond_p
     means, variances = np.empty((B, T)), np.empty((B, T))
     nell, first_nan = np.empty((B,)), np.empty((B,), dtype=np.int32)
     use_power = int(route == 'power' or (route == 'auto' and S > 1))
-    _lib.check(_lib.lib().mfs_grid_filter_1d(
+    nz = 0 if zs is None else zs.shape[0]
+    cfs = _lib.pinned_empty((B, T, nz), dtype=np.complex128, device=device) if nz else None
+    _lib.check(_lib.lib().mfs_grid_filter_1d_cf(
         n, T, B, S, use_power, _lib.ptr(xs), _lib.ptr(trans_mean), _lib.ptr(trans_sd),
         _lib.LIK[lik.kind], lp.shape[-1], _lib.ptr(lp), int(lp.ndim != 1), _lib.ptr(init_ps), int(init_ps.ndim == 2),
-        _lib.ptr(ys2), _lib.ptr(pdfs), _lib.ptr(means), _lib.ptr(variances), _lib.ptr(nell), _lib.ptr(first_nan),
-        device, None))
+        _lib.ptr(ys2), nz, _lib.ptr(zs), _lib.ptr(pdfs), _lib.ptr(means), _lib.ptr(variances), _lib.ptr(cfs), _lib.ptr(nell),
+        _lib.ptr(first_nan), device, None))
     if not return_summaries:
         return pdfs[0] if squeeze else pdfs
-    outs = [pdfs, means, variances, nell, first_nan]
+    outs = [pdfs, means, variances, nell, first_nan] + ([cfs] if nz else [])
     if squeeze:
         outs = [None if o is None else o[0] for o in outs]
-    return GridFilterResult(*outs)
+    return (GridFilterCFResult if nz else GridFilterResult)(*outs)

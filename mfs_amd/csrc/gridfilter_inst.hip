@@ -28,4 +28,24 @@ hipError_t launch_grid_update(const GridUpdateArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_grid_cf_table(int n, int nz, int n_pad, int m_pad, int transposed, const double* d_xs, const double* d_w,
+                                const double* d_zs, double* d_E, hipStream_t s) {
+    const dim3 grid = transposed ? dim3(m_pad / 64, n_pad) : dim3(n_pad / 64, m_pad);
+    hipLaunchKernelGGL(grid_cf_table, grid, dim3(64), 0, s, n, nz, n_pad, m_pad, transposed, d_xs, d_w, d_zs, d_E);
+    return hipGetLastError();
+}
+
+hipError_t launch_grid_cf_store(int nz, int B, int m_pad, int ldp, int S, int slot, const double* d_C, const int32_t* d_first_nan,
+                                double* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(grid_cf_store, dim3(ldp / kGridCfTile, m_pad / kGridCfTile), dim3(256), 0, s, nz, B, m_pad, ldp, S, slot,
+                       d_C, d_first_nan, reinterpret_cast<double2*>(d_out));
+    return hipGetLastError();
+}
+
+hipError_t launch_grid_cf_store_rows(int rows, int nz, int m_pad, const double* d_C, double* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(grid_cf_store_rows, dim3(m_pad / 64, rows), dim3(64), 0, s, nz, m_pad, d_C,
+                       reinterpret_cast<double2*>(d_out));
+    return hipGetLastError();
+}
+
 }  // namespace mfs

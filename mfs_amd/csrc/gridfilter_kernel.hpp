@@ -7,6 +7,8 @@
 //             route: K^S once, by binary exponentiation) and propagates the batch (P <- M P, n x n x B, P stored [n][B])
 //   update    per replicate column: l_i = p(y | x_i) P[i][b], z = sum_i w_i l_i, P[i][b] = l_i / z, nell_b -= log z, and the
 //             posterior mean and central variance as trapezoid integrals (brute_force.py:133)
+//   cf        on request, the characteristic function of every posterior at given frequencies: a table of weighted cosines
+//             and sines, one more product with the same GEMM per measurement, and a store (at the end of this file)
 //
 // Every matrix lives in a library-owned buffer padded with zeros to a multiple of kGridTile in both dimensions, so the GEMM
 // has no edge branches and no out-of-range access for any n or B; padded rows and columns stay zero under every product.
@@ -190,6 +192,90 @@ __global__ void __launch_bounds__(256) grid_update(const GridUpdateArgs a) {
         a.out_vars[(size_t)b * a.T + a.t] = var;
         a.nell[b] = ok ? a.nell[b] - log(z) : qnan;
         if (!ok && a.first_nan[b] < 0) a.first_nan[b] = a.t;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Characteristic function of a density on the grid, cf(z_k) = sum_i w_i exp(i z_k x_i) p_i
+// (characteristic_from_pdf, mfs/one_dim/moments.py:340-343, as post_processing_brute_force.py:27-50 takes it of every
+// posterior), as a product with a table of trapezoid-weighted cosines and sines:
+//
+//   table     E[k][i] = w_i cos(z_k x_i), E[m_pad + k][i] = w_i sin(z_k x_i): fp64 sincos of the rounded product z_k x_i at
+//             every entry (no rotation recurrence, so `zs` needs no spacing), zero outside m x n.  Built once per call
+//   gemm      grid_gemm as it is: C[2 m_pad][ldp] = E[2 m_pad][n_pad] P[n_pad][ldp] after the update of a step (the filter),
+//             or C[rows][2 m_pad] = Ps[rows][n_pad] E^T[n_pad][2 m_pad] for densities stored by rows (mfs_cf_from_pdf_1d: the
+//             table is written transposed, the densities are not)
+//   store     (re, im) pairs out of the two halves of C, 16 bytes per thread, a row of frequencies contiguous
+//
+// m_pad = grid_pad(nz), n_pad = grid_pad(n), ldp = grid_pad(B).  Device working set of the filter's cf: the table,
+// 2 m_pad n_pad doubles (256 MB at n = nz = 4096, 1 GB at the limits 8192 x 8192, the order of the power route's three n x n
+// buffers); one product buffer, 2 m_pad ldp doubles (33 MB at nz = 2000, B = 1000); and two output blocks of S steps each,
+// B S nz pairs, with S chosen so that a block stays within 64 MB (one step if a step is larger): while one block travels to
+// the host the next S steps fill the other, whatever T is.
+// The table is finite, so a NaN of P stays in its own column (row) of the product; the filter's store writes NaN for a
+// poisoned replicate explicitly all the same.
+// ---------------------------------------------------------------------------------------------------------------
+// grid (cols / 64, rows), 64 threads.  transposed = 0: row k < m_pad, column i < n_pad, E[k][i] and E[m_pad + k][i] with
+// ld = n_pad.  transposed = 1: row i < n_pad, column k < m_pad, E^T[i][k] and E^T[i][m_pad + k] with ld = 2 m_pad.
+__global__ void __launch_bounds__(64) grid_cf_table(const int n, const int nz, const int n_pad, const int m_pad,
+                                                    const int transposed, const double* __restrict__ xs,
+                                                    const double* __restrict__ w, const double* __restrict__ zs,
+                                                    double* __restrict__ E) {
+    const int slow = blockIdx.y, fast = blockIdx.x * 64 + threadIdx.x;
+    const int k = transposed ? fast : slow, i = transposed ? slow : fast;
+    double c = 0.0, s = 0.0;
+    if (k < nz && i < n) {
+        const double arg = zs[k] * xs[i];
+        sincos(arg, &s, &c);
+        c *= w[i];
+        s *= w[i];
+    }
+    if (transposed) {
+        E[(size_t)i * (2 * (size_t)m_pad) + k] = c;
+        E[(size_t)i * (2 * (size_t)m_pad) + m_pad + k] = s;
+    } else {
+        E[(size_t)k * n_pad + i] = c;
+        E[((size_t)m_pad + k) * n_pad + i] = s;
+    }
+}
+
+// The filter's store: out[b][slot][k] = (C[k][b], C[m_pad + k][b]), out being a block of [B][S][nz] pairs and `slot` the step's
+// place in it; NaN in both parts if the replicate is poisoned (first_nan[b] >= 0: the update of this step has run).
+// grid (ldp / 32, m_pad / 32), 256 threads: a 32 x 32 tile of each half goes through LDS, read with b fastest (256-byte
+// segments of C), written with k fastest (512-byte segments of out).
+constexpr int kGridCfTile = 32;
+
+__global__ void __launch_bounds__(256) grid_cf_store(const int nz, const int B, const int m_pad, const int ldp, const int S,
+                                                     const int slot, const double* __restrict__ Cm,
+                                                     const int32_t* __restrict__ first_nan, double2* __restrict__ out) {
+    __shared__ double re[kGridCfTile][kGridCfTile + 1], im[kGridCfTile][kGridCfTile + 1];
+    const int k0 = blockIdx.y * kGridCfTile, b0 = blockIdx.x * kGridCfTile;
+    const int f = threadIdx.x & (kGridCfTile - 1), q = threadIdx.x >> 5;
+#pragma unroll
+    for (int j = 0; j < kGridCfTile / 8; ++j) {
+        const int kk = q + 8 * j;                      // C rows k0 + kk < m_pad, columns b0 + f < ldp: inside the padded buffer
+        re[kk][f] = Cm[(size_t)(k0 + kk) * ldp + b0 + f];
+        im[kk][f] = Cm[((size_t)m_pad + k0 + kk) * ldp + b0 + f];
+    }
+    __syncthreads();
+    const double qnan = __builtin_nan("");
+#pragma unroll
+    for (int j = 0; j < kGridCfTile / 8; ++j) {
+        const int bb = q + 8 * j, b = b0 + bb, k = k0 + f;
+        if (b < B && k < nz) {
+            const bool bad = first_nan[b] >= 0;
+            out[((size_t)b * S + slot) * nz + k] = bad ? double2{qnan, qnan} : double2{re[f][bb], im[f][bb]};
+        }
+    }
+}
+
+// The store of densities by rows: out[c][k] = (C[c][k], C[c][m_pad + k]) for c < rows, k < nz.  grid (m_pad / 64, rows), 64 threads.
+__global__ void __launch_bounds__(64) grid_cf_store_rows(const int nz, const int m_pad, const double* __restrict__ Cm,
+                                                         double2* __restrict__ out) {
+    const int c = blockIdx.y, k = blockIdx.x * 64 + threadIdx.x;
+    if (k < nz) {
+        const double* row = Cm + (size_t)c * (2 * (size_t)m_pad);
+        out[(size_t)c * nz + k] = double2{row[k], row[m_pad + k]};
     }
 }
 

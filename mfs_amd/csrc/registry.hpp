@@ -135,6 +135,14 @@ hipError_t launch_grid_init_p(int n, int n_pad, int B, int ldp, const double* d_
                               hipStream_t s);
 hipError_t launch_grid_gemm(int M, int N, int Kd, const double* d_A, const double* d_B, double* d_C, hipStream_t s);
 hipError_t launch_grid_update(const GridUpdateArgs& a, hipStream_t s);
+// the characteristic function of densities on the grid: the table of weighted cosines and sines ([2 m_pad][n_pad], or its
+// transpose [n_pad][2 m_pad]), and the two stores of a product with it -- the filter's ([2 m_pad][ldp] -> place `slot` of a
+// block of [B][S][nz] pairs, NaN where first_nan[b] >= 0) and the one of densities by rows ([rows][2 m_pad] -> [rows][nz] pairs)
+hipError_t launch_grid_cf_table(int n, int nz, int n_pad, int m_pad, int transposed, const double* d_xs, const double* d_w,
+                                const double* d_zs, double* d_E, hipStream_t s);
+hipError_t launch_grid_cf_store(int nz, int B, int m_pad, int ldp, int S, int slot, const double* d_C, const int32_t* d_first_nan,
+                                double* d_out, hipStream_t s);
+hipError_t launch_grid_cf_store_rows(int rows, int nz, int m_pad, const double* d_C, double* d_out, hipStream_t s);
 
 // ---- bootstrap particle filter (particle_inst.hip): plain launchers, like the grid filter's.  One measurement is five launches
 // on one stream -- propagate (with the block scan of the weights), offsets, resample, cf (with the variance), finalize -- and

@@ -55,3 +55,34 @@ def save_pf_errs(filename, errs):
 
 def load_pf_errs(filename):
     return np.load(filename)['errs']
+
+
+def save_brute_force_summary(filename, true_trajs, true_filtering_means, true_filtering_cfs):
+    """The packed ground truth dardel/benes_bernoulli/post_processing_brute_force.py:53-55 writes and compute_errs.py:39-44
+    reads: the simulated trajectories (runs, T), the grid filter's means (runs, T) and the characteristic functions of its
+    posteriors (runs, T, m) complex128."""
+    np.savez_compressed(filename, true_trajs=np.asarray(true_trajs), true_filtering_means=np.asarray(true_filtering_means),
+                        true_filtering_cfs=np.asarray(true_filtering_cfs))
+
+
+def load_brute_force_summary(filename):
+    data = np.load(filename)
+    return data['true_trajs'], data['true_filtering_means'], data['true_filtering_cfs']
+
+
+# the sixteen arrays of dardel/benes_bernoulli/compute_errs.py:115-128, in its order
+BENES_BERNOULLI_ERR_KEYS = (
+    'true_trajs_vs_true_means_abs', 'true_trajs_vs_mf_means_abs', 'true_trajs_vs_ghf_means_abs', 'true_trajs_vs_pf_means_abs',
+    'true_means_vs_mf_means_abs', 'true_means_vs_ghf_means_abs', 'true_means_vs_pf_means_abs',
+    'true_cfs_vs_mf_l1', 'true_cfs_vs_mf_l2', 'true_cfs_vs_mf_sup',
+    'true_cfs_vs_ghf_l1', 'true_cfs_vs_ghf_l2', 'true_cfs_vs_ghf_sup',
+    'true_cfs_vs_pf_l1', 'true_cfs_vs_pf_l2', 'true_cfs_vs_pf_sup')
+
+
+def save_benes_bernoulli_errs(filename, **errs):
+    """The error file of dardel/benes_bernoulli/compute_errs.py:115-128: exactly its sixteen keys, each given by name."""
+    if set(errs) != set(BENES_BERNOULLI_ERR_KEYS):
+        missing, extra = set(BENES_BERNOULLI_ERR_KEYS) - set(errs), set(errs) - set(BENES_BERNOULLI_ERR_KEYS)
+        raise ValueError(f'the error file has the keys {BENES_BERNOULLI_ERR_KEYS}; missing {sorted(missing)}, '
+                         f'unknown {sorted(extra)}')
+    np.savez_compressed(filename, **{k: np.asarray(errs[k]) for k in BENES_BERNOULLI_ERR_KEYS})

@@ -14,7 +14,8 @@ from mfs_amd.tme_poly import TransitionTables, tme_tables, euler_tables, normal_
 
 __all__ = ['central_moment_of_normal', 'raw_moment_of_standard_normal', 'raw_moment_of_normal', 'raw_to_central',
            'central_to_raw', 'raw_to_scaled', 'scaled_to_central', 'sde_cond_moments_tme',
-           'sde_cond_moments_tme_normal', 'sde_cond_moments_euler', 'sde_cond_moments_normal', 'characteristic_fn']
+           'sde_cond_moments_tme_normal', 'sde_cond_moments_euler', 'sde_cond_moments_normal', 'characteristic_fn',
+           'characteristic_from_pdf', 'cf_errors']
 
 
 def central_moment_of_normal(variance: float, p: int) -> float:
@@ -187,3 +188,50 @@ def characteristic_fn(z, ms, mean=0., scale=1., *, device: int = 0):
                                                 device, None))
     out = out.reshape(lead + z_arr.shape)
     return out[..., 0] if np.ndim(z) == 0 else out
+
+
+def characteristic_from_pdf(z, ps, xs, *, device: int = 0):
+    """Characteristic function computed by the probability density function, trapz(exp(i z xs) ps, xs)
+    (mfs/one_dim/moments.py:340-343), on the device.  Vectorised the way the reference's post-processing vmaps it
+    (dardel/benes_bernoulli/post_processing_brute_force.py:27-30): `z` scalar or (m,), `ps` (n,) or (..., n) on the grid
+    `xs` (n,), strictly increasing; returns complex128 of shape ps.shape[:-1] + z.shape.  A NaN in one density makes that
+    density's values NaN and no other's."""
+    from mfs_amd import _lib
+    z_in = np.asarray(z, dtype=np.float64)
+    if z_in.ndim > 1 or z_in.size < 1:
+        raise ValueError(f'z must be a scalar or have shape (m,) with m >= 1, got {z_in.shape}')
+    z_arr = np.ascontiguousarray(np.atleast_1d(z_in))
+    if z_arr.shape[0] > _lib.GRID_MAX_NZ:
+        raise ValueError(f'm = {z_arr.shape[0]} frequencies exceed the supported {_lib.GRID_MAX_NZ}')
+    if not np.all(np.isfinite(z_arr)):
+        raise ValueError('z must be finite')
+    xs = np.ascontiguousarray(xs, dtype=np.float64)
+    if xs.ndim != 1 or xs.shape[0] < 2:
+        raise ValueError(f'xs must have shape (n,) with n >= 2, got {xs.shape}')
+    if not np.all(np.isfinite(xs)) or not np.all(np.diff(xs) > 0.):
+        raise ValueError('xs must be finite and strictly increasing')
+    n = xs.shape[0]
+    if n > _lib.GRID_MAX_N:
+        raise ValueError(f'n = {n} grid points exceed the supported {_lib.GRID_MAX_N}')
+    ps = np.asarray(ps, dtype=np.float64)
+    if ps.ndim < 1 or ps.shape[-1] != n:
+        raise ValueError(f'ps must have shape (..., {n}) like xs, got {ps.shape}')
+    lead = ps.shape[:-1]
+    ps2 = np.ascontiguousarray(ps.reshape(-1, n))
+    out = np.empty((ps2.shape[0], z_arr.shape[0]), dtype=np.complex128)
+    _lib.check(_lib.lib().mfs_cf_from_pdf_1d(n, ps2.shape[0], z_arr.shape[0], _lib.ptr(xs), _lib.ptr(z_arr), _lib.ptr(ps2),
+                                             out.ctypes.data_as(_lib.C.c_void_p), device, None))
+    out = out.reshape(lead + z_arr.shape)
+    return out[..., 0] if z_in.ndim == 0 else out
+
+
+def cf_errors(true_cfs, cfs, zs):
+    """(l1, l2, sup) distances between characteristic functions sampled at `zs` along the last axis, as
+    dardel/benes_bernoulli/compute_errs.py:103-105 takes them between the true filtering cf and a filter's: the trapezoid
+    integral of |d|, the root of that of |d|^2, and the maximum of |d|, with d = true_cfs - cfs.  Host arithmetic."""
+    trapezoid = getattr(np, 'trapezoid', None) or np.trapz   # NumPy 2 renamed it
+    zs = np.asarray(zs, dtype=np.float64)
+    d = np.abs(np.asarray(true_cfs) - np.asarray(cfs))
+    if zs.ndim != 1 or d.ndim < 1 or d.shape[-1] != zs.shape[0]:
+        raise ValueError(f'the last axis of the cfs ({d.shape}) must match zs ({zs.shape})')
+    return trapezoid(d, zs, axis=-1), np.sqrt(trapezoid(d ** 2, zs, axis=-1)), np.max(d, axis=-1)

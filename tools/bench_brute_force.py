@@ -8,7 +8,10 @@ at 2048^3 as TFLOP/s and as a fraction of the 78.6 TFLOP/s fp64 matrix peak, and
 rocblas_dgemm at the same shape as a yardstick.  `bench.py` stays the project's flagship measurement; this tool is for
 DESIGN.md section 6.
 
-    python tools/bench_brute_force.py [--batches 1,64,1000] [--repeats 3] [--quick]
+With --nz m the call is mfs_grid_filter_1d_cf at zs = linspace(-2, 2, m) (the driver's frequencies at m = 2000): the time
+then includes the table, one more product per measurement and the download of the (B, T, m) complex cfs into pinned memory.
+
+    python tools/bench_brute_force.py [--batches 1,64,1000] [--repeats 3] [--quick] [--nz 0] [--routes power,stepwise] [--no-gemm]
 """
 import argparse
 import ctypes as C
@@ -50,7 +53,7 @@ class Timer:
         return float(ms.value)
 
 
-def bench_filter(timer, n, S, T, B, route, repeats):
+def bench_filter(timer, n, S, T, B, route, repeats, nz=0):
     L = _lib.lib()
     dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli()
     xs = np.linspace(GRID_LO, GRID_HI, n)
@@ -61,7 +64,16 @@ def bench_filter(timer, n, S, T, B, route, repeats):
     lik = np.array([0., 0., 0., 0.2])      # logistic(x^3 / 5)
     means, variances, nell, fn = np.empty((B, T)), np.empty((B, T)), np.empty(B), np.empty(B, dtype=np.int32)
 
+    zs = np.linspace(-2., 2., nz) if nz else None
+    cfs = _lib.pinned_empty((B, T, nz), dtype=np.complex128) if nz else None
+
     def run(stream):
+        if nz:
+            _lib.check(L.mfs_grid_filter_1d_cf(n, T, B, S, int(route == 'power'), _lib.ptr(xs), _lib.ptr(mean), _lib.ptr(sd),
+                                               _lib.LIK['bernoulli_logistic'], 4, _lib.ptr(lik), 0, _lib.ptr(init_ps), 0,
+                                               _lib.ptr(ys), nz, _lib.ptr(zs), None, _lib.ptr(means), _lib.ptr(variances),
+                                               _lib.ptr(cfs), _lib.ptr(nell), _lib.ptr(fn), 0, stream))
+            return
         _lib.check(L.mfs_grid_filter_1d(n, T, B, S, int(route == 'power'), _lib.ptr(xs), _lib.ptr(mean), _lib.ptr(sd),
                                         _lib.LIK['bernoulli_logistic'], 4, _lib.ptr(lik), 0, _lib.ptr(init_ps), 0,
                                         _lib.ptr(ys), None, _lib.ptr(means), _lib.ptr(variances), _lib.ptr(nell), _lib.ptr(fn),
@@ -72,10 +84,15 @@ def bench_filter(timer, n, S, T, B, route, repeats):
     n_pad, b_pad = -(-n // 64) * 64, -(-B // 64) * 64
     squarings = (S.bit_length() - 1) + (bin(S).count('1') - 1) if route == 'power' and S > 1 else 0
     flop = 2. * n_pad ** 3 * squarings + 2. * n_pad * n_pad * b_pad * T * (1 if route == 'power' and S > 1 else S)
-    return dict(case='benes_bernoulli_grid_filter', n=n, substeps=S, T=T, B=B, route=route, pred_method='chapman-tme-3',
-                grid=f'linspace({GRID_LO}, {GRID_HI}, {n})', ms_median=float(np.median(ms)), ms_all=[round(v, 3) for v in ms],
-                padded_gemm_tflop=flop / 1e12, tflops_padded=flop / 1e9 / float(np.median(ms)),
-                nell_first=float(nell[0]), any_nan=bool((fn >= 0).any()), pdfs_returned=False)
+    row = dict(case='benes_bernoulli_grid_filter', n=n, substeps=S, T=T, B=B, route=route, pred_method='chapman-tme-3',
+               grid=f'linspace({GRID_LO}, {GRID_HI}, {n})', ms_median=float(np.median(ms)), ms_all=[round(v, 3) for v in ms],
+               padded_gemm_tflop=flop / 1e12, tflops_padded=flop / 1e9 / float(np.median(ms)),
+               nell_first=float(nell[0]), any_nan=bool((fn >= 0).any()), pdfs_returned=False)
+    if nz:
+        m_pad = -(-nz // 64) * 64
+        row.update(nz=nz, zs=f'linspace(-2, 2, {nz})', cf_padded_gemm_tflop=2. * 2 * m_pad * n_pad * b_pad * T / 1e12,
+                   cfs_gigabytes=cfs.nbytes / 1e9, cf_abs_max=float(np.nanmax(np.abs(cfs[0]))))
+    return row
 
 
 def bench_gemm(timer, size, iters):
@@ -140,15 +157,20 @@ def main():
     ap.add_argument('--batches', default='1,64,1000')
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--quick', action='store_true', help='a small shape (n = 256, S = 10, T = 10): checks the tool, not the device')
+    ap.add_argument('--nz', type=int, default=0, help='frequencies of the posteriors\' characteristic functions (0: none, '
+                                                      'mfs_grid_filter_1d as before)')
+    ap.add_argument('--routes', default='power,stepwise')
+    ap.add_argument('--no-gemm', action='store_true', help='skip the GEMM-alone rows')
     a = ap.parse_args()
     n, S, T, size, iters = (256, 10, 10, 256, 2) if a.quick else (2000, 100, 100, 2048, 200)
     timer = Timer()
     print(json.dumps(dict(case='device', name=_lib.device_name(0))), flush=True)
     for B in [int(v) for v in a.batches.split(',')]:
-        for route in ('power', 'stepwise'):
-            print(json.dumps(bench_filter(timer, n, S, T, B, route, a.repeats)), flush=True)
-    for row in bench_gemm(timer, size, iters):
-        print(json.dumps(row), flush=True)
+        for route in a.routes.split(','):
+            print(json.dumps(bench_filter(timer, n, S, T, B, route, a.repeats, a.nz)), flush=True)
+    if not a.no_gemm:
+        for row in bench_gemm(timer, size, iters):
+            print(json.dumps(row), flush=True)
 
 
 if __name__ == '__main__':
