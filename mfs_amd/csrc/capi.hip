@@ -1,5 +1,5 @@
 // capi.hip -- the C ABI of libmfs_hip.so (include/mfs_hip.h): argument checking, device staging, chunked launches,
-// hipGraph capture.  No compute lives here; the kernels are in filter1d_kernel.hpp.
+// hipGraph capture.  No compute lives here and no kernel header is included: launchers and argument structs come from registry.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -12,9 +12,6 @@
 #include <string>
 #include <vector>
 
-#include "filternd_kernel.hpp"
-#include "filternd3_kernel.hpp"
-#include "filter1d_grad.hpp"
 #include "registry.hpp"
 #include "staging.hpp"
 

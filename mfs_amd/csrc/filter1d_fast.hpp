@@ -31,7 +31,7 @@
 #pragma once
 #include <type_traits>
 
-#include "filter1d_kernel.hpp"
+#include "filter1d_kernel.hpp"   // the dense `quadrature` (EXT variant runs it in place); brings device_util.hpp, likelihood.hpp, kernel_args.hpp
 
 namespace mfs {
 
@@ -44,14 +44,6 @@ __device__ unsigned long long g_1d_stamps[32];
 #define F1_STAMP(slot) do {} while (0)
 #define F1_STAMP_BEGIN do {} while (0)
 #endif
-
-template <int I, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < E) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, E>(f);
-    }
-}
 
 // value of `v` held by lane J of this lane's group
 template <int G, int J>
@@ -155,31 +147,6 @@ __device__ __forceinline__ void nmul_bcast(double& acc, const double u, const do
     }
 }
 
-// v_min_f64 / v_max_f64 as single instructions: fmin() / fmax() compile to a canonicalising v_max_f64 x, x in front of
-// each (signalling-NaN quieting), which doubles the cost of the Gershgorin bounds; the operands here are results of
-// arithmetic, and a NaN among them has already poisoned the rule.
-__device__ __forceinline__ double vmin_f64(const double a, const double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double vmax_f64(const double a, const double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// sum over the G lanes of the group, result in every lane.  G = 16 is one DPP row: xor-1, xor-2 inside quads,
-// then half-row mirror and row mirror -- 2 v_mov_b32_dpp + 1 v_add_f64 per stage at VALU latency instead of
-// ds_bpermute round trips through the LDS crossbar.
-template <int CTRL>
-__device__ __forceinline__ double dpp_move(double v) {
-    // (bound_ctrl set: these patterns give every lane a source, and with it the compiler needs no pass-through value)
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 // gfx950 lane swaps: v_permlane16_swap on (v, copy of v) leaves the even DPP row's data in both rows of a pair in one
 // result and the odd row's in the other; v_permlane32_swap does the same with the two 32-lane halves of the wave
 __device__ __forceinline__ void row_dup(const double v, double& even_rows, double& odd_rows) {
@@ -197,6 +164,9 @@ __device__ __forceinline__ void half_dup(const double v, double& lower, double& 
     upper = __hiloint2double(rh[1], rl[1]);
 }
 
+// sum over the G lanes of the group, result in every lane.  G = 16 is one DPP row: xor-1, xor-2 inside quads,
+// then half-row mirror and row mirror -- 2 v_mov_b32_dpp + 1 v_add_f64 per stage at VALU latency instead of
+// ds_bpermute round trips through the LDS crossbar.
 template <int G>
 __device__ __forceinline__ double gsum(double v) {
     if constexpr (G == 32 || G == 64) {
@@ -291,99 +261,6 @@ __device__ __forceinline__ void horner_regs(const double (&tab)[TOPD][R], const 
         for (int r = 0; r < R; ++r) acc[r] = fma(acc[r], u, tab[q][r]);
 }
 
-__device__ __forceinline__ double rcp_nr(const double v) {
-    double y = __builtin_amdgcn_rcp(v);
-    y = fma(fma(-v, y, 1.0), y, y);
-    y = fma(fma(-v, y, 1.0), y, y);
-    return y;
-}
-
-// the same, but 1 / (+-inf) = 0 like a true divide (the Newton steps alone turn it into NaN)
-__device__ __forceinline__ double rcp_sat(const double v) {
-    const double y0 = __builtin_amdgcn_rcp(v);
-    double y = fma(fma(-v, y0, 1.0), y0, y0);
-    y = fma(fma(-v, y, 1.0), y, y);
-    return (y0 == 0.0) ? y0 : y;
-}
-
-__device__ __forceinline__ double rsq_nr(const double v) {
-    double y = __builtin_amdgcn_rsq(v);
-    y = fma(y, fma(-0.5 * v * y, y, 0.5), y);
-    y = fma(y, fma(-0.5 * v * y, y, 0.5), y);
-    return y;
-}
-
-// ---- elementary functions of the step, written for instruction count (the kernel is VALU-issue bound on one wave per
-// SIMD): ~22 / 33 / 34 VALU instructions for exp / tanh / log against 34 / 155 / 90 for the ocml routines.  Absolute
-// accuracy ~1-2 ulp of the result's magnitude scale; tanh keeps ABSOLUTE (not relative) accuracy near zero, which is
-// what a polynomial in tanh x needs.
-// (SC: the polynomial's constants as SCALAR operands of `v_fma_f64`.  The plain form compiles to `v_fmac_f64`, whose
-//  addend is the destination, so every constant is first copied into a vector register pair -- loop-invariant copies that
-//  get hoisted out of the time loop.  The 1-D kernels have the registers for that; the N-D kernel does not, spilled them and
-//  reloaded each one from scratch between two dependent multiply-adds: ten serialised `s_waitcnt vmcnt(0)` per exponential.)
-template <bool SC>
-__device__ __forceinline__ double fma_const(const double p, const double r, const double c) {
-    if constexpr (SC) {
-        double o;
-        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(p), "v"(r), "s"(c));
-        return o;
-    } else {
-        return fma(p, r, c);
-    }
-}
-// (Default of the 1-D kernels: off.  MFS_EXP_SC=1 frees ~20 vector registers there -- N = 7: 229 -> 207 -- but they have no
-//  spills to cure and the pass times do not move: headline 6.76 against 6.69 ms, config-4 shard 54.3 against 54.6.)
-#ifndef MFS_EXP_SC
-#define MFS_EXP_SC 0
-#endif
-template <bool SC = (MFS_EXP_SC != 0)>
-__device__ __forceinline__ double fast_exp(const double y) {
-    // e^y = 2^k e^r, k = rint(y / ln 2), |r| <= ln 2 / 2, Taylor to degree 13 (r^14 / 14! < 5e-18)
-    const double yc = vmin_f64(vmax_f64(y, -745.5), 710.0);     // e^710 = +inf as in libm (the clamp would swallow a NaN: restored below)
-    const double k = __builtin_rint(yc * 1.4426950408889634);
-    double r = fma(k, -0.6931471803691238, yc);                  // ln 2 split: hi part has 21 trailing zero bits
-    r = fma(k, -1.9082149292705877e-10, r);
-    double p = 1.6059043836821613e-10;                           // 1 / 13!
-    p = fma_const<SC>(p, r, 2.08767569878681e-09);
-    p = fma_const<SC>(p, r, 2.505210838544172e-08);
-    p = fma_const<SC>(p, r, 2.755731922398589e-07);
-    p = fma_const<SC>(p, r, 2.7557319223985893e-06);
-    p = fma_const<SC>(p, r, 2.48015873015873e-05);
-    p = fma_const<SC>(p, r, 0.0001984126984126984);
-    p = fma_const<SC>(p, r, 0.001388888888888889);
-    p = fma_const<SC>(p, r, 0.008333333333333333);
-    p = fma_const<SC>(p, r, 0.041666666666666664);
-    p = fma_const<SC>(p, r, 0.16666666666666666);
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    const double e = ldexp(p, (int)k);
-    return (y != y) ? y : e;
-}
-
-__device__ __forceinline__ double fast_tanh(const double x) {
-    const double a2 = vmin_f64(fabs(x) + fabs(x), 40.0);        // tanh(20) rounds to 1
-    const double e = fast_exp(a2);
-    const double t = fma(-2.0, rcp_nr(e + 1.0), 1.0);            // 1 - 2 / (e^{2|x|} + 1)
-    return (x != x) ? x : copysign(t, x);
-}
-
-// natural logarithm of a positive finite number (anything else gives a non-finite result, which is all the caller needs:
-// a non-finite negative log-likelihood poisons the replicate)
-template <bool SC = (MFS_EXP_SC != 0)>
-__device__ __forceinline__ double fast_log(const double v) {
-    // v = m 2^e, m in [0.5, 1): ln m from the fp32 hardware log as a seed y0 and one exact correction
-    // ln m = y0 + log1p(m e^{-y0} - 1), |m e^{-y0} - 1| ~ 1e-7
-    const double m = __builtin_amdgcn_frexp_mant(v);
-    const int ex = __builtin_amdgcn_frexp_exp(v);
-    const double y0 = (double)(__builtin_amdgcn_logf((float)m) * 0.6931471805599453f);
-    const double d = fma(m, fast_exp<SC>(-y0), -1.0);
-    const double lnm = y0 + fma(-0.5 * d, d, d);
-    const double r = fma((double)ex, 0.6931471805599453, lnm);
-    const double inf = __builtin_inf();
-    return (v == 0.0) ? -inf : (v == inf) ? inf : r;      // log 0 = -inf, log inf = inf as in libm
-}
-
 // weighted TME moments of one node for all orders n < M2 (see the call site); KT = number of operator terms.
 //   f_n = sum_{k <= KT} q_k C(n, k) dx^(n-k),   q_0 = 1, q_k = k! Q_k.
 // With G^(j)_n = sum_k C(n, k) q_{k+j} dx^(n-k) (so f_n = G^(0)_n, G^(j)_0 = q_j, G^(KT)_n = q_KT dx^n), Pascal's rule gives
@@ -428,48 +305,10 @@ struct FastTile {
 };
 
 constexpr int kMaxEigIters = 64;
-constexpr int kLfacMax = 32;
 #ifndef MFS_LAG_STOP
 #define MFS_LAG_STOP 1e-6
 #endif
 constexpr double kLagStop = MFS_LAG_STOP;
-
-// likelihood parameters held by value: the fixed-traits one-wave builds read them from LDS once, before the time loop
-struct LikRegs { double v[MFS_MAX_LIK]; };
-__device__ __forceinline__ double lik_at(const double* lp, const int i) { return lp[i]; }
-__device__ __forceinline__ double lik_at(const LikRegs* lp, const int i) { return lp->v[i]; }
-__device__ __forceinline__ const double* lik_ptr(const double* lp) { return lp; }
-__device__ __forceinline__ const double* lik_ptr(const LikRegs* lp) { return lp->v; }
-
-// Poisson pmf with log(y!) looked up for the counts that actually occur (y <= 32) instead of a sum of logs per step
-// (LP: double -- the parameters in the LDS staging area -- or LikRegs)
-template <class LP>
-__device__ __forceinline__ double likelihood_fast(const int kind, const LP* __restrict__ lp,
-                                                  const double* __restrict__ lfac, const double y, const double x) {
-    if (kind == MFS_LIK_POISSON_SOFTPLUS) {
-        const double rate = fast_log(1.0 + fast_exp(lik_at(lp, 0) * x));
-        const double lf = (y >= 0.0 && y <= (double)kLfacMax && y == floor(y)) ? lfac[(int)y] : log_factorial(y);
-        return fast_exp(y * fast_log(rate) - rate - lf);
-    }
-    if (kind == MFS_LIK_BERNOULLI_LOGISTIC) {
-        const double z = lik_at(lp, 0) + x * (lik_at(lp, 1) + x * (lik_at(lp, 2) + x * lik_at(lp, 3)));
-        const double p = rcp_sat(1.0 + fast_exp(-z));   // e^{-z} may be +inf: p = 0, as 1 / (1 + inf) upstream
-        return (y > 0.5) ? p : 1.0 - p;
-    }
-    if (kind == MFS_LIK_GAUSSIAN) {
-        const double r = y - fma(lik_at(lp, 0), x, lik_at(lp, 1));
-        return fast_exp(-0.5 * r * r * rcp_nr(lik_at(lp, 2))) * rsq_nr(6.283185307179586476925 * lik_at(lp, 2));
-    }
-    return likelihood(kind, lik_ptr(lp), y, x);
-}
-
-// the parameters from registers (REGS) or from their LDS staging area
-template <bool REGS>
-__device__ __forceinline__ double likelihood_sel(const int kind, const LikRegs& lpr, const double* __restrict__ lp,
-                                                 const double* __restrict__ lfac, const double y, const double x) {
-    if constexpr (REGS) return likelihood_fast(kind, &lpr, lfac, y, x);
-    else return likelihood_fast(kind, lp, lfac, y, x);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // stable = 1 (mfs/utils.py:525-538), the rule of a COMPLETED factor.  R = L diag(f_k), f_k = d_k < 0 ? eps : sqrt(d_k),
@@ -1445,15 +1284,6 @@ __global__ __launch_bounds__(WPB * 64) void quadrature1d_fast_ext_kernel(const Q
 // moment vector: the rule comes from quadrature_fast, every lane then holds all N (x, w) pairs and walks the z grid
 // lane-parallel, so the complex outputs of a group are 16 consecutive 16-byte elements (coalesced stores).
 // ---------------------------------------------------------------------------------------------------------------
-struct Cf1dArgs {
-    int count, nz;
-    const double* ms;     // [count][2N]
-    const double* mean;   // [count] or null
-    const double* scale;  // [count] or null
-    const double* zs;     // [nz]
-    double* out;          // [count][nz][2]  (re, im)
-};
-
 template <int N, int G, int WPB>
 __global__ __launch_bounds__(WPB * 64) void cf1d_fast_kernel(const Cf1dArgs a) {
     constexpr int M2 = 2 * N;

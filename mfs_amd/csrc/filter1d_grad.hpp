@@ -25,8 +25,12 @@
 // every lane of the group owns a root).  Instantiated for N = 2..16, P = 1..4 (filter1d_grad_inst.hip).  This kernel serves
 // optimiser loops (a few to a few thousand filters per launch), not the throughput benchmark.
 #pragma once
-#include "filter1d_kernel.hpp"
-#include "filter1d_fast.hpp"     // static_for
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/mfs_hip.h"
+#include "device_util.hpp"   // static_for, wave_sync, group_sum, group_or, finite, log_factorial
+#include "kernel_args.hpp"   // Filter1dGradArgs, kCoefDoubles
 
 namespace mfs {
 
@@ -106,14 +110,6 @@ __device__ __forceinline__ Dual<P> dgroup_sum(Dual<P> a) {
     for (int p = 0; p < P; ++p) a.d[p] = group_sum<G>(a.d[p]);
     return a;
 }
-
-struct Filter1dGradArgs {
-    Filter1dArgs f;          // the plain filter's arguments (model tables, inputs; out_mom / out_mean unused)
-    int n_par;               // P
-    const double* dcoef;     // [P][n_rows][degree + 1] (or [B][P][...] when coef_batched): d coef / d theta_p
-    const double* dlik;      // [P][n_lik] (or [B][P][n_lik]): d (likelihood parameters) / d theta_p
-    double* out_grad;        // [B][P]: d nell / d theta_p
-};
 
 // polynomial with dual coefficients at a dual argument
 template <int P>

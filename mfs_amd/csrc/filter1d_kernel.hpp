@@ -16,57 +16,19 @@
 // VALU issue + LDS latency.  HBM traffic is one y in and 2N(+2) doubles out per step.
 //
 // Everything a group shares goes through its private LDS region; groups never talk to each other, so the only
-// synchronisation is the wave-level ordering of LDS instructions (wave_sync() below), never s_barrier.
+// synchronisation is the wave-level ordering of LDS instructions (wave_sync(), device_util.hpp), never s_barrier.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
 #include "../../include/mfs_hip.h"
+#include "device_util.hpp"
+#include "kernel_args.hpp"   // Filter1dArgs, Quad1dArgs, kCoefDoubles
+#include "likelihood.hpp"
 
 namespace mfs {
 
-struct Filter1dArgs {
-    int mode, T, B, stable;
-    int extra;   // 1: the moment vectors carry 2N + 1 entries (dense path only; the order-2N moment is an output, never an input)
-    int t_begin, t_end;
-    // model
-    int trans_kind, umap, n_terms, degree, n_rows, coef_batched, lik_kind, n_lik, lik_batched;
-    double mean_x_coef;
-    const double* coef;
-    const double* lik;
-    // inputs
-    const double* m0;
-    int m0_batched;
-    const double* mean0;
-    const double* scale0;
-    const double* ys;
-    // carry between chunks: [B][2N], [B], [B], [B], [B]
-    double* c_mom;
-    double* c_mean;
-    double* c_scale;
-    double* c_nell;
-    int32_t* c_first_nan;
-    double* c_lam;  // [B][2][G] nodes (in rule units) and weights of the posterior atoms, i.e. the next predict-half rule (fast
-                    // path, chunked runs only)
-    int recompute_rule;   // 1: the predict-half rule is recomputed from the posterior moments (MFS_PREDICT_RULE=recompute)
-    // outputs (any may be null except out_nell)
-    double* out_mom;
-    double* out_mean;
-    double* out_scale;
-    double* out_nell;
-    int32_t* out_first_nan;
-};
-
-struct Quad1dArgs {
-    int B, stable;
-    const double* ms;
-    const double* mean;
-    const double* scale;
-    double* out_w;
-    double* out_x;
-};
-
 constexpr int kMaxSweeps = 40;
-constexpr int kCoefDoubles = (MFS_MAX_TERMS + 1) * (MFS_MAX_DEGREE + 1);
 
 template <int N>
 struct Tile {
@@ -87,30 +49,6 @@ struct Tile {
     static constexpr int oTab = oA;                // [N][2N] per-node moment contributions, aliases A and K tiles
     static_assert(N * M2 <= 2 * NP * LD, "contribution table must fit in the two tiles");
 };
-
-__device__ __forceinline__ void wave_sync() {
-    // Orders this wave's LDS traffic for cross-lane hand-offs inside one wavefront: LDS executes a wave's
-    // instructions in order, so all that is needed is to stop the compiler from moving accesses across this point.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-
-template <int G>
-__device__ __forceinline__ int group_or(int v) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v |= __shfl_xor(v, o, G);
-    return v;
-}
-
-__device__ __forceinline__ bool finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Gauss quadrature from 2N moments: fills S[oX] (nodes) and S[oW] (weights).  l = lane within the group.
@@ -294,43 +232,8 @@ __device__ __forceinline__ void quadrature(double* __restrict__ S, const int l, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// model pieces
+// model pieces (horner: device_util.hpp; likelihood: likelihood.hpp)
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double horner(const double* __restrict__ row, const int degree, const double u) {
-    double acc = row[degree];
-    for (int j = degree - 1; j >= 0; --j) acc = fma(acc, u, row[j]);
-    return acc;
-}
-
-// log(y!) for a Poisson count y (a non-negative integer stored as a double).  ocml's lgamma costs ~130 VGPRs when
-// inlined into the hot loop; counts are small, so a short sum of logs (exact to rounding) does the job, with the
-// Stirling series taking over for large y where it is accurate to < 1 ulp.
-__device__ __forceinline__ double log_factorial(const double y) {
-    if (y < 32.5) {
-        double acc = 0.0;
-        for (double k = 2.0; k <= y + 0.5; k += 1.0) acc += log(k);
-        return acc;
-    }
-    const double z = y + 1.0, iz = 1.0 / z, iz2 = iz * iz;
-    const double series = iz * (1.0 / 12.0 - iz2 * (1.0 / 360.0 - iz2 * (1.0 / 1260.0 - iz2 * (1.0 / 1680.0 - iz2 * (1.0 / 1188.0)))));
-    return (z - 0.5) * log(z) - z + 0.91893853320467274178 + series;
-}
-
-__device__ __forceinline__ double likelihood(const int kind, const double* __restrict__ lp, const double y,
-                                             const double x) {
-    if (kind == MFS_LIK_BERNOULLI_LOGISTIC) {
-        const double z = lp[0] + x * (lp[1] + x * (lp[2] + x * lp[3]));
-        const double p = 1.0 / (1.0 + exp(-z));
-        return (y > 0.5) ? p : 1.0 - p;
-    } else if (kind == MFS_LIK_POISSON_SOFTPLUS) {
-        const double rate = log(1.0 + exp(lp[0] * x));
-        return exp(y * log(rate) - rate - log_factorial(y));
-    } else {
-        const double r = y - (lp[0] * x + lp[1]);
-        return exp(-0.5 * r * r / lp[2]) * rsqrt(6.283185307179586476925 * lp[2]);
-    }
-}
-
 // Per-node transition moments, written as weighted contributions TAB[i][n] = w_i E[((X' - c) / sc)^n | x_i].
 // Also returns this lane's partial sums of w mu(x) and w var(x) through mu_part / var_part when asked.
 template <int N, int G>
@@ -591,9 +494,5 @@ __global__ __launch_bounds__(WPB * 64) void quadrature1d_kernel(const Quad1dArgs
         a.out_x[(size_t)b * N + i] = S[L::oX + i];
     }
 }
-
-// specialised one-wave builds of the fast kernel (filter1d_fast.hpp, SPEC): tables of at most kSpecTop padded degrees (their
-// launcher types and tables, like every other, are declared in registry.hpp)
-constexpr int kSpecTop = 4;
 
 }  // namespace mfs

@@ -27,69 +27,16 @@
 // A replicate whose rule fails (non-positive pivot, non-finite K) or whose moments turn non-finite is NaN-poisoned from that
 // step on; out_first_nan reports the step.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
 #include <utility>
 
-#include "filternd_kernel.hpp"   // likelihood_nd (the factor kinds of the d = 2 kernel, same arithmetic)
+#include "../../include/mfs_hip.h"
+#include "kernel_args.hpp"   // FilterNd3Args, FilterNd3Joint, nd3_count / nd3_index / nd3_exp / nd3_perm / nd3_kappa_row
+#include "likelihood.hpp"    // likelihood_nd, lik_density
 
 namespace mfs {
-
-struct FilterNd3Args {
-    int mode, T, B, stable;
-    int trans_kind;           // MFS_ND_TRANS_*
-    int D;                    // coefficient block extent per variable
-    int ext[MFS_ND3_ROWS];    // true extents of each block: ea | eb << 8 | ec << 16 (0 = empty block)
-    int n_factors, ny;
-    int fac_kind[MFS_ND3_MAX_FACTORS], fac_comp[MFS_ND3_MAX_FACTORS], fac_ycol[MFS_ND3_MAX_FACTORS];
-    int coef_batched, lik_batched;
-    const double* coef;       // [MFS_ND3_ROWS][D][D][D] (or [B][...]): operator rows 0..33 Q_kappa, 34..36 variances; Gaussian rows 0..8
-    const double* lik;        // [n_factors][MFS_MAX_LIK] (or [B][...])
-    const int32_t* inds;      // [4][s][s]
-    const double* m0;         // [z] or [B][z]
-    int m0_batched;
-    const double* mean0;      // [3] or [B][3]
-    const double* scale0;     // [3] or [B][3]
-    const double* ys;         // [B][T][ny]
-    double* out_mom;          // [B][T][z] or null
-    double* out_mean;         // [B][T][3] or null
-    double* out_scale;        // [B][T][3] or null
-    double* out_nell;         // [B]
-    int32_t* out_first_nan;   // [B] or null
-};
-
-// joint likelihood factors (mfs_joint_nd3): a second kernel argument of the J = 1 instantiations only
-struct FilterNd3Joint {
-    int n, E, batched;
-    int kind[MFS_ND3_MAX_JOINT], link[MFS_ND3_MAX_JOINT], ycol[MFS_ND3_MAX_JOINT];
-    int ext[MFS_ND3_MAX_JOINT][2];   // true extents of p and q, packed as FilterNd3Args::ext
-    const double* coef;              // [n][2][E][E][E] (or [B][...])
-    const double* par;               // [n] (or [B][n]): Gaussian variance
-};
-
-// graded-lexicographic multi-indices in three variables (multi_indices.py:139-177): by total degree, each degree in ascending
-// tuple order.  Position of (a, b, c), count of |n| <= deg, and the exponents of position i -- all usable at compile time.
-__host__ __device__ constexpr int nd3_count(int deg) { return (deg + 1) * (deg + 2) * (deg + 3) / 6; }
-__host__ __device__ constexpr int nd3_index(int a, int b, int c) {
-    return nd3_count(a + b + c - 1) + a * (a + b + c + 1) - a * (a - 1) / 2 + b;
-}
-__host__ __device__ constexpr int nd3_exp(int i, int k) {
-    int idx = 0;
-    for (int d = 0; d < 64; ++d)
-        for (int a = 0; a <= d; ++a)
-            for (int b = 0; b <= d - a; ++b) {
-                if (idx == i) return k == 0 ? a : k == 1 ? b : d - a - b;
-                ++idx;
-            }
-    return -1;
-}
-__host__ __device__ constexpr int nd3_perm(int n, int k) {   // n! / (n - k)!
-    int r = 1;
-    for (int m = 0; m < k; ++m) r *= n - m;
-    return r;
-}
-// operator row of kappa: its graded-lex position minus one (kappa = 0 is implicit) -- the order of mfs_amd._lib.ND3_KAPPAS
-__host__ __device__ constexpr int nd3_kappa_row(int a, int b, int c) { return nd3_index(a, b, c) - 1; }
-static_assert(nd3_count(4) - 1 == MFS_ND3_TERMS, "34 operator terms with 1 <= |kappa| <= 4");
-static_assert(nd3_kappa_row(0, 0, 1) == 0 && nd3_kappa_row(1, 0, 0) == 2 && nd3_kappa_row(4, 0, 0) == MFS_ND3_TERMS - 1, "kappa order");
 
 template <class F, int... I>
 __device__ __forceinline__ void nd3_fold(F&& f, std::integer_sequence<int, I...>) {
@@ -148,7 +95,7 @@ __device__ __forceinline__ double nd3_poly(const double* __restrict__ c, const i
     return r;
 }
 
-// one joint factor at a node: the link u of p and q, then the kind applied to u with the arithmetic of likelihood_nd.
+// one joint factor at a node: the link u of p and q, then the kind's density of u (lik_density, likelihood.hpp).
 // sqrt of a negative value is NaN; a non-finite u gives NaN, which poisons the replicate through p(y).
 __device__ __forceinline__ double nd3_joint_factor(const int kind, const int link, const double* __restrict__ c, const int E,
                                                    const int extp, const int extq, const double par, const double y,
@@ -162,16 +109,7 @@ __device__ __forceinline__ double nd3_joint_factor(const int kind, const int lin
         u = atan2(p, (link == MFS_ND3_LINK_ATAN2_SQRT) ? sqrt(q) : q);
     }
     if (!__builtin_isfinite(u)) return __builtin_nan("");
-    if (kind == MFS_LIK_BERNOULLI_LOGISTIC) {
-        const double pr = rcp_sat(1.0 + fast_exp<true>(-u));
-        return (y > 0.5) ? pr : 1.0 - pr;
-    }
-    if (kind == MFS_LIK_POISSON_SOFTPLUS) {
-        const double rate = fast_log<true>(1.0 + fast_exp<true>(u));
-        return fast_exp<true>(y * fast_log<true>(rate) - rate - log_factorial(y));
-    }
-    const double r = y - u;
-    return fast_exp<true>(-0.5 * r * r * rcp_nr(par)) * rsq_nr(6.283185307179586476925 * par);
+    return lik_density<true>(kind, u, par, y);
 }
 
 // The quadrature rule of the moments in LDS (oMom) around the centre / scale in misc (mode): on return the node coordinates

@@ -39,7 +39,9 @@
 // and, in a Normal-closure prediction, the cardinal vectors and the grid weights (cheb_grid_rule_nd) -- are 16 x 16 tiles of
 // v_mfma_f64_16x16x4_f64; everything else is matrix-VECTOR work in a sequential chain (DPP multiply-adds, dpp_matvec).
 #pragma once
-#include "filter1d_fast.hpp"
+#include "filter1d_fast.hpp"   // bcast, row_dup, half_dup (the 1-D family's DPP / lane-swap helpers), kMaxSweeps
+#include "kernel_args.hpp"     // FilterNdArgs
+#include "likelihood.hpp"      // likelihood_nd, likelihood_joint_nd
 
 namespace mfs {
 
@@ -96,34 +98,6 @@ __device__ __forceinline__ void nd_exponents(const int zi, int& n0, int& n1) {
     sd -= (sd * (sd + 1) / 2 > zi) ? 1 : 0;
     n0 = zi - sd * (sd + 1) / 2; n1 = sd - n0;
 }
-
-struct FilterNdArgs {
-    int mode, T, B, stable;
-    int t_begin, t_end;       // the steps this launch takes (a chunk of [0, T)); the state crosses launches through `carry`
-    double* carry;            // [B][NdTile::kCarry] (or null): the slots NdTile::cMean .. cV name the layout
-    int n_terms_used, D;      // coefficient block extent per variable (degree + 1)
-    int n_factors, ny;        // likelihood = prod_f lik(kind_f, params_f, y[ycol_f], x[comp_f]);  ys is [B][T][ny]
-    int fac_kind[2], fac_comp[2], fac_ycol[2];
-    int coef_batched, lik_batched;
-    int force_eigen;          // 1: every update diagonalises K_k (the checked fallback of the Chebyshev evaluation, as the only route)
-    int joint_grid;           // 1: a likelihood of both components is integrated over the Chebyshev grid instead of the eigen-nodes (A/B)
-    int ext[32];              // per-block true extents (ea | eb << 8) of the coefficient blocks; 0 = empty block
-    const double* coef;       // [rows][D][D] (or [B][...]), rows = terms + 2 with terms = 14 or 27 (see nd_terms): Q_kappa in the
-                              // fixed kappa order below (zeros where the model has no term), then the conditional variances
-                              // of X'_0, X'_1 (scaled mode)
-    const double* lik;        // [n_factors][4] (or [B][n_factors][4])
-    const int32_t* inds;      // [3][s][s]
-    const double* m0;         // [z] or [B][z]
-    int m0_batched;
-    const double* mean0;      // [2] or [B][2]
-    const double* scale0;     // [2] or [B][2] (scaled mode)
-    const double* ys;         // [B][T][ny]
-    double* out_mom;          // [B][T][z]
-    double* out_mean;         // [B][T][2]
-    double* out_scale;        // [B][T][2] (scaled mode)
-    double* out_nell;
-    int32_t* out_first_nan;
-};
 
 // derivative multi-indices kappa, graded-lex order (the order the host fills `coef` in): 1 <= |kappa| <= 4 (TME order <= 2:
 // 14 terms, TK = 0) or <= 6 (TME order 3: 27 terms, TK = 2).  The coefficient table has two more rows, the conditional
@@ -372,34 +346,6 @@ __device__ __forceinline__ double poly2d_full(const double* __restrict__ c, cons
 template <int DMAX, class F>
 __device__ __forceinline__ void dispatch_extent(const int D, F&& f) {
     static_for<1, DMAX + 1>([&](auto Dc) { if (D == Dc) f(Dc); });
-}
-
-// the likelihood kinds of include/mfs_hip.h with the in-line exponential / logarithm in their scalar-constant form
-// (fast_exp<true>: see there); Bernoulli-logistic is mfs/multi_dims/ss_models.py:63-67
-__device__ __forceinline__ double likelihood_nd(const int kind, const double* __restrict__ lp, const double y,
-                                                const double x) {
-    if (kind == MFS_LIK_BERNOULLI_LOGISTIC) {
-        const double z = lp[0] + x * (lp[1] + x * (lp[2] + x * lp[3]));
-        const double p = rcp_sat(1.0 + fast_exp<true>(-z));
-        return (y > 0.5) ? p : 1.0 - p;
-    }
-    if (kind == MFS_LIK_POISSON_SOFTPLUS) {
-        const double rate = fast_log<true>(1.0 + fast_exp<true>(lp[0] * x));
-        return fast_exp<true>(y * fast_log<true>(rate) - rate - log_factorial(y));
-    }
-    const double r = y - fma(lp[0], x, lp[1]);
-    return fast_exp<true>(-0.5 * r * r * rcp_nr(lp[2])) * rsq_nr(6.283185307179586476925 * lp[2]);
-}
-
-// a factor of BOTH state components (fac_component = 2).  MFS_LIK_BEARING_GAUSSIAN: y ~ N(atan2(x_1, x_0), lp[0]) -- the
-// bearing-only measurement of /root/reference/examples/2d_bearing_only.ipynb cell 7, norm.pdf(y, arctan2(x[1], x[0]), sd)
-__device__ __forceinline__ double likelihood_joint_nd(const int kind, const double* __restrict__ lp, const double y,
-                                                      const double x0, const double x1) {
-    if (kind == MFS_LIK_BEARING_GAUSSIAN) {
-        const double r = y - atan2(x1, x0);
-        return fast_exp<true>(-0.5 * r * r * rcp_nr(lp[0])) * rsq_nr(6.283185307179586476925 * lp[0]);
-    }
-    return __builtin_nan("");
 }
 
 // acc[j] -= u * (v of lane j - OFF of this lane's DPP row) for j = J0 .. J1 - 1 as blocks of 8 / 4 / 2 / 1 fused DPP

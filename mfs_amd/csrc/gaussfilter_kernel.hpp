@@ -19,20 +19,10 @@
 #include <stdint.h>
 
 #include "../../include/mfs_hip.h"
-#include "registry.hpp"   // GfArgs, kGfThreads
+#include "device_util.hpp"   // finite, group_sum, gf_pivot_ok, gf_poly2, gf_poly2_grad, gf_chol2
+#include "registry.hpp"      // GfArgs (kernel_args.hpp), kGfThreads
 
 namespace mfs {
-
-__device__ __forceinline__ bool gf_finite(const double v) { return fabs(v) <= 1.79769313486231570e308; }
-// a legal Cholesky pivot: zero is (a point mass, as in the reference), negative and non-finite are not
-__device__ __forceinline__ bool gf_pivot_ok(const double v) { return v >= 0.0 && gf_finite(v); }
-
-template <int L>
-__device__ __forceinline__ double gf_sum(double v) {
-#pragma unroll
-    for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, L);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // measurement moments: mean h(x), variance Xi(x) and (DERIV) d h / d x of the likelihood kinds of include/mfs_hip.h
@@ -157,8 +147,8 @@ __global__ void __launch_bounds__(kGfThreads) gf_filter_1d(const GfArgs a) {
                 s0 += w * mu;
                 s1 += w * (mu * mu + var);
             }
-            mp = gf_sum<L>(s0);
-            vp = gf_sum<L>(s1) - mp * mp;
+            mp = group_sum<L>(s0);
+            vp = group_sum<L>(s1) - mp * mp;
             ok = ok && gf_pivot_ok(vp);
             const double sdp = sqrt(vp);
             double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -170,11 +160,11 @@ __global__ void __launch_bounds__(kGfThreads) gf_filter_1d(const GfArgs a) {
                 a1 += w * (q.h * q.h + q.xi);
                 a2 += w * (x * q.h);
             }
-            pred = gf_sum<L>(a0);
-            S = gf_sum<L>(a1) - pred * pred;
-            C = gf_sum<L>(a2) - mp * pred;
+            pred = group_sum<L>(a0);
+            S = group_sum<L>(a1) - pred * pred;
+            C = group_sum<L>(a2) - mp * pred;
         }
-        ok = ok && S > 0.0 && gf_finite(S);
+        ok = ok && S > 0.0 && finite(S);
         if (ok) {
             const double K = C / S, r = y - pred;
             m = mp + K * r;
@@ -199,46 +189,6 @@ __global__ void __launch_bounds__(kGfThreads) gf_filter_1d(const GfArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 // d = 2
 // ---------------------------------------------------------------------------------------------------------------
-// sum_{a, b < D} c[a][b] x0^a x1^b by nested Horner
-__device__ __forceinline__ double gf_poly2(const double* __restrict__ c, const int D, const double x0, const double x1) {
-    double acc = 0.0;
-    for (int a = D - 1; a >= 0; --a) {
-        double row = c[a * D + D - 1];
-        for (int b = D - 2; b >= 0; --b) row = row * x1 + c[a * D + b];
-        acc = acc * x0 + row;
-    }
-    return acc;
-}
-
-// the same with both partial derivatives
-__device__ __forceinline__ double gf_poly2_grad(const double* __restrict__ c, const int D, const double x0, const double x1,
-                                                double& d0, double& d1) {
-    double acc = 0.0;
-    d0 = 0.0;
-    d1 = 0.0;
-    for (int a = D - 1; a >= 0; --a) {
-        double row = c[a * D + D - 1], drow = 0.0;
-        for (int b = D - 2; b >= 0; --b) {
-            drow = drow * x1 + row;
-            row = row * x1 + c[a * D + b];
-        }
-        d0 = d0 * x0 + acc;
-        acc = acc * x0 + row;
-        d1 = d1 * x0 + drow;
-    }
-    return acc;
-}
-
-// lower Cholesky factor of [[p00, p01], [p01, p11]] in closed form; false if a pivot is negative or not finite
-__device__ __forceinline__ bool gf_chol2(const double p00, const double p01, const double p11, double& l00, double& l10,
-                                         double& l11) {
-    l00 = sqrt(p00);
-    l10 = p01 / l00;
-    const double d1 = p11 - l10 * l10;
-    l11 = sqrt(d1);
-    return gf_pivot_ok(p00) && gf_pivot_ok(d1);
-}
-
 template <int L, bool EKF>
 __global__ void __launch_bounds__(kGfThreads) gf_filter_2d(const GfArgs a) {
     extern __shared__ double gf_lds[];
@@ -315,11 +265,11 @@ __global__ void __launch_bounds__(kGfThreads) gf_filter_2d(const GfArgs a) {
                 s01 += w * (mu0 * mu1 + gf_poly2(c_s01, D, x0, x1));
                 s11 += w * (mu1 * mu1 + gf_poly2(c_s11, D, x0, x1));
             }
-            mp0 = gf_sum<L>(s0);
-            mp1 = gf_sum<L>(s1);
-            q00 = gf_sum<L>(s00) - mp0 * mp0;
-            q01 = gf_sum<L>(s01) - mp0 * mp1;
-            q11 = gf_sum<L>(s11) - mp1 * mp1;
+            mp0 = group_sum<L>(s0);
+            mp1 = group_sum<L>(s1);
+            q00 = group_sum<L>(s00) - mp0 * mp0;
+            q01 = group_sum<L>(s01) - mp0 * mp1;
+            q11 = group_sum<L>(s11) - mp1 * mp1;
             const bool okp = gf_chol2(q00, q01, q11, l00, l10, l11);
             ok = ok && okp;
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
@@ -332,12 +282,12 @@ __global__ void __launch_bounds__(kGfThreads) gf_filter_2d(const GfArgs a) {
                 a2 += w * (x0 * q.h);
                 a3 += w * (x1 * q.h);
             }
-            pred = gf_sum<L>(a0);
-            S = gf_sum<L>(a1) - pred * pred;
-            C0 = gf_sum<L>(a2) - mp0 * pred;
-            C1 = gf_sum<L>(a3) - mp1 * pred;
+            pred = group_sum<L>(a0);
+            S = group_sum<L>(a1) - pred * pred;
+            C0 = group_sum<L>(a2) - mp0 * pred;
+            C1 = group_sum<L>(a3) - mp1 * pred;
         }
-        ok = ok && S > 0.0 && gf_finite(S);
+        ok = ok && S > 0.0 && finite(S);
         if (ok) {
             const double K0 = C0 / S, K1 = C1 / S, r = y - pred;
             m_0 = mp0 + K0 * r;

@@ -21,8 +21,8 @@
 #include <stdint.h>
 
 #include "../../include/mfs_hip.h"
-#include "filter1d_kernel.hpp"   // likelihood(), finite()
-#include "registry.hpp"          // kGridTile, kGridBK, GridUpdateArgs
+#include "likelihood.hpp"   // likelihood(); device_util.hpp: finite()
+#include "registry.hpp"     // kGridTile, kGridBK; GridUpdateArgs (kernel_args.hpp)
 
 namespace mfs {
 

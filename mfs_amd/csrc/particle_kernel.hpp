@@ -2,7 +2,7 @@
 // mfs/classical_filters_smoothers/smc.py:26-84 with the stratified / systematic resamplers of resampling.py:43-59, for B
 // replicates x n particles in fp64.  The particles live in HBM ([B][n]); a replicate spans pf_blocks(n) workgroups.
 //
-// One measurement t is five launches on one stream (PfArgs, registry.hpp):
+// One measurement t is five launches on one stream (PfArgs, kernel_args.hpp):
 //   propagate  x_i <- mu(x_i) + sqrt(var(x_i)) z_i (the model tables of MFS_TRANS_GAUSSIAN), w_i = p(y_t | x_i), and the
 //              block-local inclusive prefix sums of w: per thread over its kPfItems consecutive particles, then the block scan
 //              (pf_weight_scan, particle_stream.hpp).  Block total -> wpart
@@ -25,9 +25,9 @@
 #include <stdint.h>
 
 #include "../../include/mfs_hip.h"
-#include "filter1d_kernel.hpp"   // likelihood(), horner(), finite()
+#include "likelihood.hpp"        // likelihood(); device_util.hpp: horner(), finite()
 #include "particle_stream.hpp"   // the stream, the ordered sums, pf_weight_scan, pf_ancestor, pf_mixture_pick
-#include "registry.hpp"          // PfArgs, PfOffsetsArgs, kPf*
+#include "registry.hpp"          // kPf*; PfArgs, PfOffsetsArgs (kernel_args.hpp)
 
 namespace mfs {
 

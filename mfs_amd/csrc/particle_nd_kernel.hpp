@@ -4,7 +4,7 @@
 // particles in fp64.  The particles live in HBM as [B][2][n], component-major, so every pass over them is coalesced; a
 // replicate spans pf_blocks(n) workgroups.
 //
-// One measurement t is five launches on one stream (PfNdArgs, registry.hpp):
+// One measurement t is five launches on one stream (PfNdArgs, kernel_args.hpp):
 //   propagate  mu, S from the five polynomials of MFS_ND_TRANS_GAUSSIAN at (x_0, x_1) (the table, this replicate's if batched,
 //              staged in LDS); L the closed-form lower Cholesky factor of S; x'_0 = mu_0 + l_00 z_0, x'_1 = mu_1 + l_10 z_0 +
 //              l_11 z_1, both NaN if a pivot is negative or not finite; w_i = prod_f lik_f(y_t[ycol_f], x'_i[component_f]); and
@@ -25,10 +25,9 @@
 #include <stdint.h>
 
 #include "../../include/mfs_hip.h"
-#include "filter1d_kernel.hpp"      // likelihood(), finite()
-#include "gaussfilter_kernel.hpp"   // gf_poly2(), gf_chol2()
+#include "likelihood.hpp"           // likelihood(); device_util.hpp: finite(), gf_poly2(), gf_chol2()
 #include "particle_stream.hpp"      // the stream, the ordered sums, pf_weight_scan, pf_ancestor, pf_mixture_pick
-#include "registry.hpp"             // PfNdArgs, kPf*
+#include "registry.hpp"             // kPf*; PfNdArgs (kernel_args.hpp)
 
 namespace mfs {
 

@@ -1,21 +1,13 @@
 // registry.hpp -- every launcher type and launcher table of the library, declared once.  The *_inst.hip translation units
 // fill the tables from static registrars; capi.hip reads them.  A null launcher means "not compiled / does not exist".
-// Host-only: the argument structs are only named here (their definitions live with the kernels; the grid filter's, the
-// particle filter's and the Gaussian filters' are the exceptions).
+// Host-only; the argument structs the launchers take are defined in kernel_args.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/mfs_hip.h"
+#include "kernel_args.hpp"
 
 namespace mfs {
-
-struct Filter1dArgs;
-struct Quad1dArgs;
-struct Cf1dArgs;
-struct Filter1dGradArgs;
-struct FilterNdArgs;
-struct FilterNd3Args;
-struct FilterNd3Joint;
 
 // ---- 1-D: dense (LDS-tile) and fast (register-resident) paths
 using Filter1dLaunch = hipError_t (*)(const Filter1dArgs&, int grid, int lds_bytes, hipStream_t);
@@ -107,28 +99,12 @@ extern Nd3Entry g_nd3_table[MFS_ND3_MAX_N + 1];   // defined in filternd3_inst.h
 
 // ---- brute-force grid filter (gridfilter_inst.hip): one build of each kernel, so plain launchers and no table.  Every
 // matrix is row-major in a buffer padded to multiples of 64 (n_pad, ldp); the GEMM takes padded sizes only and refuses
-// anything else, and C must not alias A or B.  (GridUpdateArgs is defined here, not just named: its kernels are not templates,
-// so their header can be included by gridfilter_inst.hip alone.)
+// anything else, and C must not alias A or B.
 constexpr int kGridTile = 64;   // the GEMM's block tile in M and N; every padded dimension is a multiple of it
 constexpr int kGridBK = 16;     // ... and its k-slice
 
 inline int grid_pad(const int v) { return (v + kGridTile - 1) / kGridTile * kGridTile; }
 
-struct GridUpdateArgs {
-    int n, T, B, t;          // grid points, steps, replicates, the step this launch updates
-    int ldp;                 // leading dimension of P (the padded B)
-    int lik_kind, n_lik, lik_batched;
-    const double* xs;        // [n]
-    const double* w;         // [n] trapezoid weights
-    const double* lik;       // [n_lik] or [B][n_lik]
-    const double* ys;        // [B][T]
-    double* P;               // [n_pad][ldp]: predicted densities in, posteriors out
-    double* out_pdfs;        // [B][T][n] or null
-    double* out_means;       // [B][T]
-    double* out_vars;        // [B][T]
-    double* nell;            // [B], accumulated over the steps
-    int32_t* first_nan;      // [B], -1 until a step's normaliser is zero or not finite
-};
 hipError_t launch_grid_build_k(int n, int n_pad, const double* d_xs, const double* d_mean, const double* d_sd,
                                const double* d_w, double* d_K, hipStream_t s);
 hipError_t launch_grid_init_p(int n, int n_pad, int B, int ldp, const double* d_init, int init_batched, double* d_P,
@@ -156,47 +132,6 @@ constexpr int kPfMaxF = 8;                         // frequencies per thread of 
 inline int pf_blocks(const int n) { return (n + kPfChunk - 1) / kPfChunk; }
 inline int pf_segments(const int n) { return (n + kPfSeg - 1) / kPfSeg; }
 
-struct PfArgs {
-    int n, T, B, t;          // particles, steps, replicates, the step this launch works on
-    int nblk, nseg;          // pf_blocks(n), pf_segments(n)
-    int resampling;          // MFS_RESAMPLE_*
-    int umap, degree, coef_batched, lik_kind, n_lik, lik_batched;
-    double mean_x_coef;
-    const double* coef;      // [2][degree + 1] or [B][2][degree + 1]: P_m, P_v of MFS_TRANS_GAUSSIAN
-    const double* lik;       // [n_lik] or [B][n_lik]
-    const double* ys;        // [B][T]
-    const uint64_t* seeds;   // [B]
-    int n_mix, init_batched; // initial law: a mixture of n_mix Normals drawn on the device, or (n_mix = 0) given samples
-    const double* mix_cumw;  // [n_mix] each
-    const double* mix_mean;
-    const double* mix_var;
-    const double* init;      // [n] or [B][n]
-    int nz, z_uniform;       // frequencies of the cf; 1: zs is uniformly spaced with step dz
-    double dz;
-    const double* zs;        // [nz]
-    double* x;               // [B][n] the particles: propagated in place, read by the resampler
-    double* x2;              // [B][n] the resampled particles (the host swaps x and x2 after every step)
-    double* wscan;           // [B][n] block-local inclusive prefix sums of the weights
-    double* wpart;           // [B][nblk] block totals of the weights
-    double* woffs;           // [B][nblk] their exclusive prefix sums in index order
-    double* wtot;            // [B] sum of the weights
-    double* xpart;           // [B][nblk] block totals of the resampled particles
-    double* vpart;           // [B][nseg] segment totals of (x' - mean)^2
-    double* cfpart;          // [B][nseg][nz][2] segment totals of exp(i z x'), or null
-    double* out_samples;     // [B][T][n] or null
-    double* out_means;       // [B][T]
-    double* out_vars;        // [B][T]
-    double* out_cfs;         // [B][T][nz][2] or null
-};
-// what the `offsets` kernel reads and writes: the same kernel for every state dimension
-struct PfOffsetsArgs {
-    int n, B, t, nblk;       // particles, replicates, the step this launch works on, pf_blocks(n)
-    double* wpart;           // [B][nblk] block totals of the weights (read)
-    double* woffs;           // [B][nblk] their exclusive prefix sums in index order
-    double* wtot;            // [B] sum of the weights
-    double* nell;            // [B], accumulated over the steps
-    int32_t* first_nan;      // [B], -1 until a step's weight sum is zero or not finite
-};
 hipError_t launch_pf_init(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_propagate(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_offsets(const PfOffsetsArgs& a, hipStream_t s);
@@ -206,36 +141,7 @@ hipError_t launch_pf_finalize(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_draws(uint64_t seed, int t, int tag, int draw, int count, double* d_uniform, double* d_normal, hipStream_t s);
 
 // ---- bootstrap particle filter, d = 2 (particle_nd_inst.hip).  The same five launches per measurement, the same constants
-// and the same `offsets` kernel (launch_pf_offsets with a PfOffsetsArgs); the particles are [B][2][n], component-major, so
-// every particle pass is coalesced.
-struct PfNdArgs {
-    int n, T, B, t;          // particles, steps, replicates, the step this launch works on
-    int nblk, nseg;          // pf_blocks(n), pf_segments(n)
-    int resampling;          // MFS_RESAMPLE_*
-    int extent, coef_stride, coef_batched;   // D; doubles between two replicates' tables (rows D D); 1: one table per replicate
-    int n_factors, ny, lik_batched;
-    int fac_kind[MFS_ND_MAX_FACTORS], fac_component[MFS_ND_MAX_FACTORS], fac_ycol[MFS_ND_MAX_FACTORS];
-    const double* coef;      // [rows][D][D] or [B][rows][D][D]; blocks 0..4 = mu_0, mu_1, S_00, S_01, S_11
-    const double* lik;       // [n_factors][MFS_MAX_LIK] or [B][n_factors][MFS_MAX_LIK]
-    const double* ys;        // [B][T][ny]
-    const uint64_t* seeds;   // [B]
-    int n_mix, init_batched; // initial law: a mixture of n_mix Normals drawn on the device, or (n_mix = 0) given samples
-    const double* mix_cumw;  // [n_mix]
-    const double* mix_mean;  // [n_mix][2]
-    const double* mix_chol;  // [n_mix][2][2], lower factors
-    const double* init;      // [n][2] or [B][n][2]
-    double* x;               // [B][2][n] the particles: propagated in place, read by the resampler
-    double* x2;              // [B][2][n] the resampled particles (the host swaps x and x2 after every step)
-    double* wscan;           // [B][n] block-local inclusive prefix sums of the weights
-    double* wpart;           // [B][nblk] block totals of the weights
-    double* woffs;           // [B][nblk] their exclusive prefix sums in index order
-    double* wtot;            // [B] sum of the weights
-    double* xpart;           // [B][2][nblk] block totals of the resampled particles, per component
-    double* cpart;           // [B][3][nseg] segment totals of d_0 d_0, d_0 d_1, d_1 d_1, d = x' - mean
-    double* out_samples;     // [B][T][n][2] or null
-    double* out_means;       // [B][T][2]
-    double* out_covs;        // [B][T][2][2]
-};
+// and the same `offsets` kernel (launch_pf_offsets with a PfOffsetsArgs).
 hipError_t launch_pfnd_init(const PfNdArgs& a, hipStream_t s);
 hipError_t launch_pfnd_propagate(const PfNdArgs& a, hipStream_t s);
 hipError_t launch_pfnd_resample(const PfNdArgs& a, hipStream_t s);
@@ -255,29 +161,6 @@ inline int gf_lanes(const int n_points) {
     return L;
 }
 
-struct GfArgs {
-    int d, method;           // 1 or 2; MFS_GF_*
-    int n_points, lanes;     // sigma points (0 for the EKF) and lanes per replicate (1 for the EKF)
-    int T, B;
-    // d = 1 (mfs_model_1d, MFS_TRANS_GAUSSIAN): coef [2][degree + 1] or [B][2][degree + 1]; lik [n_lik] or [B][n_lik]
-    int umap, degree, coef_batched, lik_kind, n_lik, lik_batched;
-    double mean_x_coef;
-    // d = 2 (mfs_model_nd, MFS_ND_TRANS_GAUSSIAN): coef [rows][extent][extent], blocks 0..4 = mu_0, mu_1, S_00, S_01, S_11; one
-    // likelihood factor of kind lik_kind on state component `component`, lik [MFS_MAX_LIK] or [B][MFS_MAX_LIK]
-    int extent, component;
-    const double* coef;
-    const double* lik;
-    const double* xi;        // [n_points][d]
-    const double* w;         // [n_points]
-    const double* m0;        // [d] or [B][d]
-    const double* P0;        // [d][d] or [B][d][d]
-    int init_batched;
-    const double* ys;        // [B][T]
-    double* out_means;       // [B][T][d] or null
-    double* out_covs;        // [B][T][d][d] or null
-    double* out_nells;       // [B][T], the running sum
-    int32_t* out_first_nan;  // [B] or null
-};
 int gf_lds_bytes(const GfArgs& a);   // dynamic LDS of one block
 hipError_t launch_gauss_filter(const GfArgs& a, hipStream_t s);
 
