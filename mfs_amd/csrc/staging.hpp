@@ -1,6 +1,6 @@
-// staging.hpp -- the device staging of one host-pointer call (capi.hip): blocks leased from the pool (pool.hpp), uploads,
-// downloads and the closing synchronisation, with one sticky hipError_t: after the first failure every later step is a
-// no-op, and finish() reports it.  Host-only code.
+// staging.hpp -- the device staging of one host-pointer call (the capi*.hip units): blocks leased from the pool (pool.hpp), inputs
+// uploaded as they are leased, outputs recorded as they are leased and downloaded together, and the closing synchronisation,
+// with one sticky hipError_t: after the first failure every later step is a no-op, and finish() reports it.  Host-only code.
 #pragma once
 #include "../../include/mfs_hip.h"
 #include "pool.hpp"
@@ -15,12 +15,45 @@ public:
     hipStream_t s = nullptr;        // where the call's copies and launches go
     CallContext* cx = nullptr;      // with_context only: s = the caller's stream if it gave one, else cx->compute
 
+    // how out() treats a block: kStreamed -- leased, not recorded (the entry copies it out itself, e.g. run_streaming_out);
+    // kAlways -- leased even without a host pointer (the kernel writes it whether the caller wants it or not)
+    enum : unsigned { kStreamed = 1, kAlways = 2 };
+    static constexpr int kMaxOutputs = 6;   // the 1-D particle filter's: samples, means, variances, cfs, nell, first_nan
+
     // with_context = false: the call runs on the caller's stream as it is (null included)
     Staging(int device, void* stream, bool with_context) : s((hipStream_t)stream), lease_(device) {
         if (with_context && (err = lease_.context(&cx)) == hipSuccess && !s) s = cx->compute;
     }
+    // a block and nothing copied: work space, or a block that is filled from several host arrays (h2d) or zeroed on the device
+    template <typename T = double>
+    T* work(size_t bytes) {
+        T* d = nullptr;
+        if (err == hipSuccess) err = lease_.device_block(&d, bytes);
+        return d;
+    }
+    // an input: a block of bytes + pad, and the upload of `bytes` where the caller gave the array
     template <typename T>
-    void alloc(T** d, size_t bytes) { if (err == hipSuccess) err = lease_.device_block(d, bytes); }
+    T* in(const T* h, size_t bytes, size_t pad = 0) {
+        T* d = work<T>(bytes + pad);
+        if (h) h2d(d, h, bytes);
+        return d;
+    }
+    // an output: null when the caller does not want it (but see kAlways); else a block of bytes + pad, whose first `bytes`
+    // download() copies to `h`
+    template <typename T>
+    T* out(T* h, size_t bytes, size_t pad = 0, unsigned how = 0) {
+        if (!h && !(how & kAlways)) return nullptr;
+        T* d = work<T>(bytes + pad);
+        if (h && !(how & kStreamed) && err == hipSuccess) {
+            if (n_out_ == kMaxOutputs) err = hipErrorInvalidValue;     // (a new entry with more outputs: raise kMaxOutputs)
+            else outs_[n_out_++] = Output{h, d, bytes};
+        }
+        return d;
+    }
+    // the recorded outputs, in the order they were recorded
+    void download() {
+        for (int k = 0; k < n_out_; ++k) d2h(outs_[k].h, outs_[k].d, outs_[k].bytes);
+    }
     void h2d(void* d, const void* h, size_t bytes) {
         if (err == hipSuccess && bytes) err = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
     }
@@ -39,7 +72,10 @@ public:
     }
 
 private:
+    struct Output { void* h; const void* d; size_t bytes; };
     Lease lease_;
+    Output outs_[kMaxOutputs];
+    int n_out_ = 0;
 };
 
 // A run of T steps whose moments ([B][T][width] doubles, on the device and at the host) are streamed out: the run is cut

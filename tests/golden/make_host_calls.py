@@ -52,7 +52,7 @@ def _addressed(p, n):
 
 
 def _tables_of(name, structs, args):
-    """The arrays the descriptors point to, with the element counts mfs_amd/csrc/capi.hip computes for its uploads."""
+    """The arrays the descriptors point to, with the element counts the host units (mfs_amd/csrc/capi_*.hip) compute for their uploads."""
     m = structs[0]
     nb = args[7 if name == 'mfs_filter_1d_grad' else 3 + len(structs)]
     if isinstance(m, _lib.MfsModel1d):

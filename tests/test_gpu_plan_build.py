@@ -1,4 +1,4 @@
-"""Which kernel build a 1-D plan picks (csrc/capi.hip: pick_slot for the path and lane group, resolve_launch for the
+"""Which kernel build a 1-D plan picks (csrc/capi_1d.hip: pick_slot for the path and lane group, resolve_launch for the
 build), read back through mfs_plan_1d_kernel_build and mfs_plan_1d_geometry.  The expected codes are written down from
 those rules: a dense slot runs the dense build; a fast slot runs, with at most four blocks per compute unit, the
 specialised one-wave build if the plain kernel has one for the table shape (N = 14..16, 2 / 4 / 6 operator terms or a

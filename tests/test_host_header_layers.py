@@ -1,5 +1,6 @@
 """The include layers of mfs_amd/csrc: device code that several kernel families use lives in the shared headers, no kernel
-header includes another family's, and capi.hip (the host layer) includes no kernel header at all.
+header includes another family's, and the host layer (capi.hip and the capi_*.hip units, one per filter family) includes no
+kernel header at all.
 
 For every translation unit of csrc/Makefile the preprocessor lists what it reaches (`hipcc -MM`, no compilation); the
 project headers among them must be the unit's own family's kernel headers plus the shared layer.  No GPU and no library."""
@@ -16,12 +17,14 @@ CSRC = os.path.join(ROOT, 'mfs_amd', 'csrc')
 # owned by no kernel family: any unit may reach these
 SHARED = {'device_util.hpp', 'likelihood.hpp', 'kernel_args.hpp', 'particle_stream.hpp', 'registry.hpp', 'launch_util.hpp'}
 # the host layer's own
-HOST_ONLY = {'staging.hpp', 'pool.hpp'}
+HOST_ONLY = {'staging.hpp', 'pool.hpp', 'host_run.hpp'}
+# the host units: the core of the C ABI and one unit per filter family
+HOST_UNITS = {'capi.hip', 'capi_1d.hip', 'capi_nd.hip', 'capi_grid.hip', 'capi_classical.hip'}
 # the 1-D fast kernel runs the dense `quadrature` in place (its extended variant), so the two headers are one family
 FAST_1D = {'filter1d_fast.hpp', 'filter1d_kernel.hpp'}
 # unit -> (the -D set of one of its Makefile rules, the kernel headers of its family)
 UNITS = {
-    'capi.hip': ([], set()),
+    **{unit: ([], set()) for unit in HOST_UNITS},
     'filter1d_inst.hip': (['-DMFS_NLO=14', '-DMFS_NHI=16'], FAST_1D),
     'filter1d_spec_inst.hip': (['-DMFS_SPEC_N=15'], FAST_1D),
     'filter1d_partner_inst.hip': (['-DMFS_SPEC_N=15'], FAST_1D | {'filter1d_partner.hpp'}),
@@ -69,9 +72,9 @@ def test_every_translation_unit_is_listed():
 def test_unit_reaches_only_its_family_and_the_shared_layer(unit):
     defines, family = UNITS[unit]
     reached = _reached(unit, defines)
-    if unit == 'capi.hip':
+    if unit in HOST_UNITS:
         # the host layer: launchers and argument structs through registry.hpp, no device code
-        assert reached == {'registry.hpp', 'kernel_args.hpp', 'staging.hpp', 'pool.hpp'}
+        assert reached == {'registry.hpp', 'kernel_args.hpp'} | HOST_ONLY
     else:
         assert not reached & HOST_ONLY
         assert reached - SHARED == family
