@@ -659,7 +659,9 @@ int mfs_particle_filter_nd(const mfs_model_nd* model, int n, int T, int B, int r
  *   out_first_nan [B] or NULL.  The reference's Cholesky of a matrix that is not positive definite is NaN: a replicate whose
  *                Cholesky pivot is negative or not finite (zero is legal), or whose S is not finite and > 0, is NaN in every
  *                output from that step on, and that step is its first_nan (-1 if none).  Only that replicate.  The EKF takes
- *                no Cholesky, so only the rule on S applies to it.
+ *                no Cholesky, so only the rule on S applies to it.  A measurement y_t that is not finite (NaN or +-inf) poisons
+ *                its replicate at step t in the same way, in both methods.  At d = 2 the zero that is legal is the second
+ *                pivot (P = diag(v, 0)): a zero first pivot divides P01 by zero, and that step is the replicate's first_nan.
  * A group of L lanes owns a replicate, L the smallest power of two >= n_points, at most 64 (one lane for the EKF); the sums are
  * butterfly reductions in an order fixed by n_points alone and there are no atomics: two calls with the same inputs return the
  * same bits, and replicate b of a batch returns the bits of a B = 1 call.

@@ -208,7 +208,8 @@ def sgp_filter(state_cond_m_cov, measurement_cond_m_cov, sgps: SigmaPoints, m0, 
 
     Returns (mfs (T, dx), vfs (T, dx, dx), nells (T,)) with `nells` the running sum, as the reference's scan returns it; with a
     replicate axis on `ys` each has a leading B.  return_first_nan=True appends (B,) int32: the first step at which a Cholesky
-    pivot was negative or the innovation variance not positive, from which on that replicate is NaN, or -1.
+    pivot was negative, the innovation variance not positive or the measurement not finite, from which on that replicate is
+    NaN, or -1.
     """
     return _run(GF_SIGMA_POINT, state_cond_m_cov, measurement_cond_m_cov, sgps, m0, v0, dt, ys, return_first_nan, device)
 

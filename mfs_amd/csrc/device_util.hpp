@@ -211,7 +211,8 @@ __device__ __forceinline__ double gf_poly2_grad(const double* __restrict__ c, co
 // a legal Cholesky pivot: zero is (a point mass, as in the reference), negative and non-finite are not
 __device__ __forceinline__ bool gf_pivot_ok(const double v) { return v >= 0.0 && finite(v); }
 
-// lower Cholesky factor of [[p00, p01], [p01, p11]] in closed form; false if a pivot is negative or not finite
+// lower Cholesky factor of [[p00, p01], [p01, p11]] in closed form; false if a pivot is negative or not finite.  A zero
+// second pivot is legal (P = diag(v, 0)); a zero first pivot is not: l10 = p01 / 0 is NaN or +-inf, and so is the second pivot
 __device__ __forceinline__ bool gf_chol2(const double p00, const double p01, const double p11, double& l00, double& l10,
                                          double& l11) {
     l00 = sqrt(p00);

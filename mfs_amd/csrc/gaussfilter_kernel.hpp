@@ -12,8 +12,8 @@
 // once per group.  A group past the batch recomputes replicate B - 1 and stores nothing, so every lane reaches every shuffle.
 //
 // NaN rule (the reference's Cholesky of a non-positive-definite matrix is NaN): a pivot that is negative or not finite, or an
-// innovation variance S that is not finite and > 0, makes mean, covariance and nell NaN; NaN then fails the same tests at
-// every later step, so the replicate stays NaN, and the first such step is its first_nan.
+// innovation variance S that is not finite and > 0, or a measurement y_t that is not finite, makes mean, covariance and nell
+// NaN; NaN then fails the same tests at every later step, so the replicate stays NaN, and the first such step is its first_nan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(kGfThreads) gf_filter_1d(const GfArgs a) {
             S = group_sum<L>(a1) - pred * pred;
             C = group_sum<L>(a2) - mp * pred;
         }
-        ok = ok && S > 0.0 && finite(S);
+        ok = ok && S > 0.0 && finite(S) && finite(y);
         if (ok) {
             const double K = C / S, r = y - pred;
             m = mp + K * r;
@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(kGfThreads) gf_filter_2d(const GfArgs a) {
             C0 = group_sum<L>(a2) - mp0 * pred;
             C1 = group_sum<L>(a3) - mp1 * pred;
         }
-        ok = ok && S > 0.0 && finite(S);
+        ok = ok && S > 0.0 && finite(S) && finite(y);
         if (ok) {
             const double K0 = C0 / S, K1 = C1 / S, r = y - pred;
             m_0 = mp0 + K0 * r;

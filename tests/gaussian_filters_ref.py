@@ -119,7 +119,7 @@ def gaussian_filter_ref(tables, lik, method, sgps, m0, v0, ys) -> GaussianFilter
                 pred = float(sgps.w @ h)
                 S = float(sgps.w @ (h * h + Xi)) - pred * pred
                 C = sgps.w @ (chi * h[:, None]) - mp * pred
-            ok = ok and bool(np.isfinite(S) and S > 0.)
+            ok = ok and bool(np.isfinite(S) and S > 0.) and bool(np.isfinite(ys[t]))      # a measurement that is not finite poisons
             if ok:
                 K = C / S
                 m = mp + K * (ys[t] - pred)

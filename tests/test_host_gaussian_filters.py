@@ -2,6 +2,7 @@
 restatement of the two filters (tests/gaussian_filters_ref.py) pinned to the exact Kalman filter and to central differences,
 the descriptors, and the Python layer's argument handling (nothing here calls the device)."""
 import math
+import os
 
 import numpy as np
 import numpy.testing as npt
@@ -18,6 +19,7 @@ from mfs_amd.one_dim.moments import _trace_sde
 from mfs_amd.sym import Poly
 from mfs_amd.tme_poly import normal_tables, tme_tables
 from tests import brute_force_ref as R
+from tests import gaussian_filters_exact as X
 from tests import gaussian_filters_ref as G
 
 
@@ -274,3 +276,173 @@ def test_initial_shape_rules():
     assert m.shape == (3, 2) and v.shape == (3, 2, 2) and batched and np.all(m == [1., 2.])
     m, v, batched = gfs._initial([[1.], [2.]], [[[3.]], [[4.]]], 1, 2, False)
     assert batched and m[1, 0] == 2. and v[1, 0, 0] == 4.
+
+
+# =====================================================================================================================
+# the 50-digit arbiter (tests/gaussian_filters_exact.py) and its fixture (tests/golden/gaussian_filters_exact.npz)
+# =====================================================================================================================
+AGREE = 1e-40
+
+
+@pytest.fixture(scope='module')
+def frozen():
+    with np.load(os.path.join(os.path.dirname(__file__), 'golden', X.FIXTURE)) as npz:
+        return {k: npz[k] for k in npz.files}
+
+
+def _linear_case(component):
+    rng = np.random.default_rng([7, component])
+    model = X.Model(2, X.linear_table2(), 'gaussian', X.LINEAR_LIK, 'x', 0., component)
+    return model, np.array([0.3, -0.2]), np.array([[0.4, -0.05], [0.1, 0.3]]), 0.6 * rng.standard_normal(12)
+
+
+# ---- B.1 the arbiter against the matrix Kalman filter, d = 2, full F and Q, either component measured
+@pytest.mark.parametrize('component', [0, 1])
+def test_arbiter_equals_the_matrix_kalman_filter(component):
+    model, m0, P0, ys = _linear_case(component)
+    H = np.zeros(2)
+    H[component] = X.LINEAR_LIK[0]
+    sym_P0 = np.array([[P0[0, 0], P0[1, 0]], [P0[1, 0], P0[1, 1]]])
+    true = X.kalman_mp(X.LINEAR_F, X.LINEAR_C, X.LINEAR_Q, H, X.LINEAR_LIK[1], X.LINEAR_LIK[2], m0, sym_P0, ys)
+    assert X.LINEAR_F[0, 1] != 0. and X.LINEAR_F[1, 0] != 0. and X.LINEAR_F[0, 1] != X.LINEAR_F[1, 0] and X.LINEAR_Q[0, 1] != 0.
+    for order in (2, 3):
+        xi, w = X.gauss_hermite_mp(2, order)
+        assert X.trace_distance(X.sigma_point_mp(model, xi, w, m0, P0, ys), true) <= AGREE, f'GH-{order}'
+    assert X.trace_distance(X.ekf_mp(model, m0, P0, ys), true) <= AGREE
+    # and it is not blind: the other component, or the upper triangle of P0, is another filter
+    other = X.ekf_mp(model._replace(component=1 - component), m0, P0, ys)
+    assert X.trace_distance(other, true) > 1e-3
+    assert X.trace_distance(X.ekf_mp(model, m0, P0.T, ys), true) > 1e-3
+
+
+# ---- B.2 the closed form against the restated sigma-point filter at a sufficient order, and not below it
+def _adf_models():
+    one = X.case('adf1/gh4')
+    two = X.case('adf2/gh4')
+    c2 = two.model.coef      # S_01 not constant; mu cubic in either variable and in both together
+    assert np.count_nonzero(c2[3]) > 1 and np.all(c2[:2, 3, 0] != 0.) and np.all(c2[:2, 0, 3] != 0.) and np.all(c2[:2, 1, 2] != 0.)
+    assert one.model.coef[0, 3] != 0. and one.model.coef[1, 2] != 0.
+    return one, two
+
+
+@pytest.mark.parametrize('which', [0, 1])
+def test_closed_form_adf_equals_a_sufficient_rule_and_no_lesser_one(which):
+    case = _adf_models()[which]
+    d = case.model.d
+    m0, P0 = case.initial(0)
+    ys = case.ys[0][:8]
+    closed = X.adf_closed_form(case.model, m0, P0, ys)
+    # degree max(2 deg mu, deg S) = 6 in a standard variable: order n integrates 2 n - 1
+    for order in (4, 6):
+        xi, w = X.gauss_hermite_mp(d, order)
+        assert X.trace_distance(X.sigma_point_mp(case.model, xi, w, m0, P0, ys), closed) <= AGREE, f'order {order}'
+    xi, w = X.gauss_hermite_mp(d, 3)
+    gap = X.trace_distance(X.sigma_point_mp(case.model, xi, w, m0, P0, ys), closed)
+    assert gap > 1e-7, f'order 3 integrates degree 5 only, yet differs from the closed form by {float(gap):.3g}'
+
+
+# ---- B.3 the restatement against the arbiter on every frozen case
+def _spread(name, got, exact):
+    return G.assert_filter_close(got['means'], got['covs'], got['nells'], exact['means'], exact['covs'], exact['nells'], name)
+
+
+def test_restatement_against_the_arbiter(frozen):
+    stored_spread = {'means': 0., 'covs': 0., 'nells': 0.}
+    for case in X.cases():
+        case, exact, ref = X.thaw(frozen, case)
+        runs = [X.restatement_of(case, r) for r in range(case.R)]
+        if case.guarded:
+            for r, run in enumerate(runs):
+                G.assert_well_conditioned(run, f'{case.name} replicate {r}')
+        now = {q: np.stack([getattr(run, q) for run in runs]) for q in ('means', 'covs', 'nells')}
+        npt.assert_array_equal([run.first_nan for run in runs], exact['first_nan'], err_msg=case.name)
+        _spread(f'{case.name} (restatement now)', now, exact)
+        npt.assert_array_equal(ref['first_nan'], exact['first_nan'], err_msg=case.name)
+        worst = _spread(f'{case.name} (restatement stored)', ref, exact)
+        for q, v in worst.items():
+            stored_spread[q] = max(stored_spread[q], v)
+    print('REF_SPREAD measured: ' + ', '.join(f'{q} {v:.3e}' for q, v in stored_spread.items()))
+    # the recorded value is the measured one: not smaller, and not padded
+    for q, v in stored_spread.items():
+        assert v <= X.REF_SPREAD[q] <= 1.05 * v, f'REF_SPREAD[{q!r}] = {X.REF_SPREAD[q]:.4e}, measured {v:.4e}'
+
+
+def test_the_fixture_covers_the_case_list(frozen):
+    names = {k.split(':')[0] for k in frozen}
+    assert names == {c.name for c in X.cases()}
+    for c in X.cases():
+        assert c.ys.shape[1] <= 24 and c.R <= 5
+        if c.guarded and (c.arbiter or c.method) == X.SIGMA_POINT:
+            assert c.n_points <= 64, f'{c.name}: mpmath runs at most 64 points outside the saturation cases'
+
+
+# ---- B.4 the fixture is what the generator writes
+@pytest.mark.parametrize('name', X.FRESHNESS_CASES)
+def test_fixture_is_fresh(frozen, name):
+    fresh = X.freeze(X.case(name))
+    for key, value in fresh.items():
+        got = frozen[key]
+        assert got.dtype == np.asarray(value).dtype and got.shape == np.shape(value), key
+        assert np.array_equal(got, value, equal_nan=True), f'{key} differs from a fresh run of the generator'
+
+
+# ---- the rule on measurements that are not finite, in the arbiter and in the restatement
+@pytest.mark.parametrize('bad', [math.nan, math.inf, -math.inf])
+@pytest.mark.parametrize('name', ['lanes1/n3', 'edges1/deg0/ekf', 'lanes2/n4', 'matrix2/gaussian/c1/ekf/D7'])
+def test_non_finite_measurement_poisons_from_that_step(name, bad):
+    case = X.case(name)
+    ys = case.ys[:, :6].copy()
+    ys[1, 3] = bad
+    case = case._replace(ys=ys)
+    for run in (X.arbiter_of, X.restatement_of):
+        clean, hit = run(case, 0), run(case, 1)
+        assert clean.first_nan == -1 and np.all(np.isfinite(clean.nells))
+        assert hit.first_nan == 3
+        assert np.all(np.isfinite(hit.means[:3])) and np.all(np.isfinite(hit.covs[:3])) and np.all(np.isfinite(hit.nells[:3]))
+        assert np.isnan(hit.means[3:]).all() and np.isnan(hit.covs[3:]).all() and np.isnan(hit.nells[3:]).all()
+
+
+def test_point_masses_at_d2_in_the_arbiter(frozen):
+    # diag(v, 0): a zero second pivot, legal.  diag(0, v) and 0: the first pivot divides by zero, poisoned at step 0
+    _, exact, ref = X.thaw(frozen, X.case('pointmass2/sigma_point'))
+    npt.assert_array_equal(exact['first_nan'], [-1, 0, 0])
+    npt.assert_array_equal(ref['first_nan'], [-1, 0, 0])
+    _, exact, _ = X.thaw(frozen, X.case('pointmass2/ekf'))          # the EKF takes no Cholesky factor
+    npt.assert_array_equal(exact['first_nan'], [-1, -1, -1])
+
+
+def test_saturation_cases_reach_the_tails(frozen):
+    case, exact, _ = X.thaw(frozen, X.case('saturation/bernoulli_logistic/sigma_point'))
+    sd = np.sqrt(exact['covs'][..., 0, 0]).min()
+    assert np.abs(case.xi).max() > 31. and case.model.lik[3] * (sd * 31.) ** 3 > 1000.
+    assert np.all(np.isfinite(exact['nells'])) and np.all(exact['first_nan'] == -1)
+    case, exact, _ = X.thaw(frozen, X.case('saturation/poisson_softplus/sigma_point'))
+    assert case.model.lik[0] * np.sqrt(exact['covs'][..., 0, 0]).min() * 31. > 100. and np.all(np.isfinite(exact['nells']))
+
+
+# ---- the frozen cases can see the defects they are there for (the restatement carries the defect; the arbiter is the stored one)
+def _restatement_misses(frozen, name, defect):
+    case, exact, _ = X.thaw(frozen, X.case(name))
+    case = defect(case)
+    runs = [X.restatement_of(case, r) for r in range(case.R)]
+    now = {q: np.stack([getattr(run, q) for run in runs]) for q in ('means', 'covs', 'nells')}
+    with pytest.raises(AssertionError):
+        _spread(f'{name} with the defect', now, exact)
+
+
+def test_a_dropped_tail_point_shows_only_where_it_has_weight(frozen):
+    def drop(case):
+        w = case.w.copy()
+        w[64] = 0.      # lane 0 of a 64-lane group takes points 0 and 64
+        return case._replace(w=w)
+    _restatement_misses(frozen, 'adf1/gh65-centre-last', drop)
+    _restatement_misses(frozen, 'adf2/gh9-centre-last', drop)
+    case, exact, _ = X.thaw(frozen, X.case('adf1/gh65'))      # the outermost node of 65 weighs 1e-28: no fp64 test sees it go
+    assert case.w[64] < 1e-25
+    runs = [X.restatement_of(drop(case), r) for r in range(case.R)]
+    _spread('adf1/gh65 without its last point', {q: np.stack([getattr(run, q) for run in runs]) for q in ('means', 'covs', 'nells')}, exact)
+
+
+@pytest.mark.parametrize('method', [X.SIGMA_POINT, X.EKF])
+def test_the_upper_triangle_of_p0_shows_if_read(frozen, method):
+    _restatement_misses(frozen, f'matrix2/asymmetric/{method}', lambda case: case._replace(P0=np.swapaxes(case.P0, -1, -2).copy()))
