@@ -260,6 +260,56 @@ int mfs_characteristic_1d(int N, int count, const double* ms, const double* mean
 int mfs_elementary(int which, int n, const double* x, double* out, int device);
 
 /*
+ * ---- diagnostic: the shared device math and the likelihood forms ---------------------------------------------------
+ * Every routine of csrc/device_util.hpp and csrc/likelihood.hpp that the kernel families share, one thread per element,
+ * from a translation unit of its own (csrc/device_math_inst.hip), so that the tests can compare each with exact
+ * arithmetic.  in is [n_in][n], out is [n_out][n] (argument j of element i at in[j * n + i]); integer arguments (kind,
+ * degree, D) travel as doubles.  n_in and n_out must be the routine's own (below), n >= 1.  Host pointers.
+ *
+ *   fn                              inputs                                       outputs
+ *   MFS_DM_EXP / _EXP_SC            y                                            fast_exp<false / true>
+ *   MFS_DM_TANH                     x                                            fast_tanh
+ *   MFS_DM_LOG / _LOG_SC            v                                            fast_log<false / true>
+ *   MFS_DM_RCP_NR / _RCP_SAT / _RSQ_NR   v                                       the Newton-refined 1 / v, 1 / v, 1 / sqrt(v)
+ *   MFS_DM_LOG_FACTORIAL            y                                            log(y!)
+ *   MFS_DM_HORNER                   degree, u, row[MFS_MAX_DEGREE + 1]           sum_j row[j] u^j
+ *   MFS_DM_POLY2                    D, x0, x1, c[HI * HI] (HI = MFS_ND_MAX_EXTENT_HI; the D x D table is c[a * D + b])
+ *                                                                                sum c[a][b] x0^a x1^b
+ *   MFS_DM_POLY2_GRAD               the same                                     value, d / dx0, d / dx1
+ *   MFS_DM_CHOL2                    p00, p01, p11                                l00, l10, l11, ok (1 / 0)
+ *   MFS_DM_LIKELIHOOD               kind, lp[MFS_MAX_LIK], y, x                  likelihood (libm form)
+ *   MFS_DM_LIKELIHOOD_ND            the same                                     likelihood_nd
+ *   MFS_DM_LIK_DENSITY / _SC        kind, eta, var, y                            lik_density<false / true>
+ *   MFS_DM_LIKELIHOOD_JOINT_ND      kind, lp[MFS_MAX_LIK], y, x0, x1             likelihood_joint_nd
+ *   MFS_DM_LIKELIHOOD_FAST / _REGS  kind, lp[MFS_MAX_LIK], y, x                  likelihood_fast with the parameters behind a
+ *                                                                                pointer / in LikRegs; the log(y!) table in LDS
+ *   MFS_DM_LFAC_TABLE               y (an integer in [0, 32])                    the entry of that table
+ */
+#define MFS_DM_EXP 0
+#define MFS_DM_EXP_SC 1
+#define MFS_DM_TANH 2
+#define MFS_DM_LOG 3
+#define MFS_DM_LOG_SC 4
+#define MFS_DM_RCP_NR 5
+#define MFS_DM_RCP_SAT 6
+#define MFS_DM_RSQ_NR 7
+#define MFS_DM_LOG_FACTORIAL 8
+#define MFS_DM_HORNER 9
+#define MFS_DM_POLY2 10
+#define MFS_DM_POLY2_GRAD 11
+#define MFS_DM_CHOL2 12
+#define MFS_DM_LIKELIHOOD 13
+#define MFS_DM_LIKELIHOOD_ND 14
+#define MFS_DM_LIK_DENSITY 15
+#define MFS_DM_LIK_DENSITY_SC 16
+#define MFS_DM_LIKELIHOOD_JOINT_ND 17
+#define MFS_DM_LIKELIHOOD_FAST 18
+#define MFS_DM_LIKELIHOOD_FAST_REGS 19
+#define MFS_DM_LFAC_TABLE 20
+#define MFS_DM_COUNT 21
+int mfs_device_math(int fn, int n, int n_in, const double* in, int n_out, double* out, int device);
+
+/*
  * ---- N-D moment filter (d = 2), host pointers ------------------------------------------------------------------
  * Replaces moment_filter_nd_rms / moment_filter_nd_cms / moment_filter_nd_scms (mfs/multi_dims/filtering.py:283-344,
  * 210-280, 33-207) for B replicates, with either transition family the reference offers.

@@ -152,6 +152,7 @@ _SIGNATURES = [
     ('mfs_plan_nd3_create_joint', _i, [_vpp, C.POINTER(MfsModelNd3), C.POINTER(MfsJointNd3), _i, _i, _i, _i, _i, _vp, _vp, _i,
                                        _i]),
     ('mfs_elementary', _i, [_i, _i, _vp, _vp, _i]),
+    ('mfs_device_math', _i, [_i, _i, _i, _vp, _i, _vp, _i]),
     ('mfs_grid_filter_1d', _i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     ('mfs_grid_filter_1d_cf', _i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp,

@@ -1,5 +1,5 @@
 // capi.hip -- the core of the C ABI of libmfs_hip.so (include/mfs_hip.h): the last-error string, the runtime wrappers, the pool
-// entries, the RCCL loader and the elementary-function diagnostic.  The filter families are units of their own: capi_1d.hip,
+// entries, the RCCL loader and the device-math diagnostics.  The filter families are units of their own: capi_1d.hip,
 // capi_nd.hip, capi_grid.hip, capi_classical.hip.  No compute lives in any of them and no kernel header is included: launchers
 // and argument structs come from registry.hpp, what the units share on the host from host_run.hpp.
 #include <hip/hip_runtime.h>
@@ -226,6 +226,24 @@ int mfs_elementary(int which, int n, const double* x, double* out, int device) {
     if (st.err == hipSuccess) st.err = hipMemcpy(out, d_o, (size_t)n * 8, hipMemcpyDeviceToHost);
     (void)hipDeviceSynchronize();
     return st.finish("mfs_elementary", MFS_OK);
+}
+
+// diagnostic: the shared device math and the likelihood forms, one routine per call
+int mfs_device_math(int fn, int n, int n_in, const double* in, int n_out, double* out, int device) {
+    const mfs::DeviceMathShape shape = mfs::device_math_shape(fn);
+    if (shape.n_in == 0) return fail(MFS_EINVAL, "mfs_device_math: fn = %d outside [0, %d)", fn, MFS_DM_COUNT);
+    if (n <= 0) return fail(MFS_EINVAL, "mfs_device_math: n = %d (>= 1)", n);
+    if (n_in != shape.n_in || n_out != shape.n_out)
+        return fail(MFS_EINVAL, "mfs_device_math: fn = %d takes n_in = %d, n_out = %d, got %d, %d", fn, shape.n_in, shape.n_out,
+                    n_in, n_out);
+    if (!in || !out) return fail(MFS_EINVAL, "mfs_device_math: NULL buffer");
+    HIP_TRY(hipSetDevice(device));
+    mfs::Staging st(device, nullptr, true);
+    const double* d_in = st.in(in, (size_t)n_in * n * 8);
+    double* d_out = st.out(out, (size_t)n_out * n * 8);
+    if (st.err == hipSuccess) st.err = mfs::launch_device_math(fn, n, d_in, d_out, st.s);
+    st.download();
+    return st.finish("mfs_device_math", MFS_OK);
 }
 
 }  // extern "C"

@@ -80,9 +80,11 @@ __device__ __forceinline__ double rcp_sat(const double v) {
 }
 
 __device__ __forceinline__ double rsq_nr(const double v) {
+    // (-0.5 y v, in this order: halving y is exact, halving a v below 2^-1021 drops its last bit -- down to all of them at
+    //  2^-1074, where the result came out 2.25 times too large; for every larger v the product rounds to the same bits either way)
     double y = __builtin_amdgcn_rsq(v);
-    y = fma(y, fma(-0.5 * v * y, y, 0.5), y);
-    y = fma(y, fma(-0.5 * v * y, y, 0.5), y);
+    y = fma(y, fma(-0.5 * y * v, y, 0.5), y);
+    y = fma(y, fma(-0.5 * y * v, y, 0.5), y);
     return y;
 }
 
@@ -170,6 +172,19 @@ __device__ __forceinline__ double log_factorial(const double y) {
     const double series = iz * (1.0 / 12.0 - iz2 * (1.0 / 360.0 - iz2 * (1.0 / 1260.0 - iz2 * (1.0 / 1680.0 - iz2 * (1.0 / 1188.0)))));
     return (z - 0.5) * log(z) - z + 0.91893853320467274178 + series;
 }
+
+// The exponent of the Poisson pmf, y log(rate) - rate - log(y!), from log(rate) as the caller's logarithm gave it.  At y = 0
+// the first term is dropped, as xlogy does upstream: the softplus rate underflows to 0 (link below -36.8) or overflows to
+// +inf (link above 710), and 0 * log(rate) would be NaN where the pmf is 1 and 0.  (The factor is replaced, not the product:
+// the multiply-add the expression contracts to stays the one it was, and with it every finite result.)
+__device__ __forceinline__ double poisson_log_pmf(const double y, const double rate, const double log_rate, const double lfac) {
+    const double lr = (y == 0.0) ? 0.0 : log_rate;
+    return y * lr - rate - lfac;
+}
+
+// The softplus rate of the in-line logarithm, kept non-negative: fast_log(1.0) is -2^-53, not 0 (its two halves cancel to the
+// last bit but one), and the logarithm of that rate is NaN for every count.  A NaN rate stays NaN.
+__device__ __forceinline__ double rate_floor(const double rate) { return (rate < 0.0) ? 0.0 : rate; }
 
 // ---- polynomials and the 2 x 2 Cholesky factor
 __device__ __forceinline__ double horner(const double* __restrict__ row, const int degree, const double u) {

@@ -146,7 +146,10 @@ __device__ __forceinline__ Dual<P> dlikelihood(const int kind, const double* __r
         return (y > 0.5) ? pr : (-pr + 1.0);
     } else if (kind == MFS_LIK_POISSON_SOFTPLUS) {
         const Dual<P> rate = dlog(dexp(par(0) * x) + 1.0);
-        return dexp(y * dlog(rate) - rate - log_factorial(y));
+        // at y = 0 the y log(rate) term is dropped, value and tangents: it is identically zero there, and 0 * log(rate) is NaN once
+        // the rate has underflowed to 0 or overflowed (poisson_log_pmf of device_util.hpp, on duals)
+        const Dual<P> lr = (y == 0.0) ? dconst<P>(0.0) : dlog(rate);
+        return dexp(y * lr - rate - log_factorial(y));
     } else {
         const Dual<P> r = -(par(0) * x + par(1)) + y;
         const Dual<P> var = par(2);

@@ -16,7 +16,7 @@ __device__ __forceinline__ double likelihood(const int kind, const double* __res
         return (y > 0.5) ? p : 1.0 - p;
     } else if (kind == MFS_LIK_POISSON_SOFTPLUS) {
         const double rate = log(1.0 + exp(lp[0] * x));
-        return exp(y * log(rate) - rate - log_factorial(y));
+        return exp(poisson_log_pmf(y, rate, log(rate), log_factorial(y)));
     } else {
         const double r = y - (lp[0] * x + lp[1]);
         return exp(-0.5 * r * r / lp[2]) * rsqrt(6.283185307179586476925 * lp[2]);
@@ -32,8 +32,8 @@ __device__ __forceinline__ double lik_density(const int kind, const double eta, 
         return (y > 0.5) ? p : 1.0 - p;
     }
     if (kind == MFS_LIK_POISSON_SOFTPLUS) {
-        const double rate = fast_log<SC>(1.0 + fast_exp<SC>(eta));
-        return fast_exp<SC>(y * fast_log<SC>(rate) - rate - log_factorial(y));
+        const double rate = rate_floor(fast_log<SC>(1.0 + fast_exp<SC>(eta)));
+        return fast_exp<SC>(poisson_log_pmf(y, rate, fast_log<SC>(rate), log_factorial(y)));
     }
     const double r = y - eta;
     return fast_exp<SC>(-0.5 * r * r * rcp_nr(var)) * rsq_nr(6.283185307179586476925 * var);
@@ -74,9 +74,9 @@ template <class LP>
 __device__ __forceinline__ double likelihood_fast(const int kind, const LP* __restrict__ lp,
                                                   const double* __restrict__ lfac, const double y, const double x) {
     if (kind == MFS_LIK_POISSON_SOFTPLUS) {
-        const double rate = fast_log(1.0 + fast_exp(lik_at(lp, 0) * x));
+        const double rate = rate_floor(fast_log(1.0 + fast_exp(lik_at(lp, 0) * x)));
         const double lf = (y >= 0.0 && y <= (double)kLfacMax && y == floor(y)) ? lfac[(int)y] : log_factorial(y);
-        return fast_exp(y * fast_log(rate) - rate - lf);
+        return fast_exp(poisson_log_pmf(y, rate, fast_log(rate), lf));
     }
     if (kind == MFS_LIK_BERNOULLI_LOGISTIC) {
         const double z = lik_at(lp, 0) + x * (lik_at(lp, 1) + x * (lik_at(lp, 2) + x * lik_at(lp, 3)));

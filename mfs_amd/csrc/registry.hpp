@@ -91,6 +91,22 @@ constexpr int kNdMaxN = 7;
 extern NdEntry g_nd_table[kNdMaxN + 1];   // defined in filternd_inst.hip
 hipError_t launch_elementary(int which, int n, const double* d_x, double* d_out, hipStream_t s);   // filternd_inst.hip
 
+// ---- diagnostic: the shared device math and the likelihood forms (device_math_inst.hip), MFS_DM_* of include/mfs_hip.h
+struct DeviceMathShape { int n_in, n_out; };
+// rows of `in` and `out` a routine takes; {0, 0} for a code that names none
+constexpr DeviceMathShape device_math_shape(const int fn) {
+    return (fn < 0 || fn >= MFS_DM_COUNT) ? DeviceMathShape{0, 0}
+         : (fn <= MFS_DM_LOG_FACTORIAL || fn == MFS_DM_LFAC_TABLE) ? DeviceMathShape{1, 1}
+         : (fn == MFS_DM_HORNER) ? DeviceMathShape{2 + MFS_MAX_DEGREE + 1, 1}
+         : (fn == MFS_DM_POLY2) ? DeviceMathShape{3 + MFS_ND_MAX_EXTENT_HI * MFS_ND_MAX_EXTENT_HI, 1}
+         : (fn == MFS_DM_POLY2_GRAD) ? DeviceMathShape{3 + MFS_ND_MAX_EXTENT_HI * MFS_ND_MAX_EXTENT_HI, 3}
+         : (fn == MFS_DM_CHOL2) ? DeviceMathShape{3, 4}
+         : (fn == MFS_DM_LIK_DENSITY || fn == MFS_DM_LIK_DENSITY_SC) ? DeviceMathShape{4, 1}
+         : (fn == MFS_DM_LIKELIHOOD_JOINT_ND) ? DeviceMathShape{MFS_MAX_LIK + 4, 1}
+         : DeviceMathShape{MFS_MAX_LIK + 3, 1};
+}
+hipError_t launch_device_math(int fn, int n, const double* d_in, double* d_out, hipStream_t s);
+
 // ---- N-D, d = 3: [N]
 using FilterNd3Launch = hipError_t (*)(const FilterNd3Args&, int grid, hipStream_t);
 using FilterNd3JointLaunch = hipError_t (*)(const FilterNd3Args&, const FilterNd3Joint&, int grid, hipStream_t);

@@ -36,6 +36,8 @@ UNITS = {
     'particle_inst.hip': ([], {'particle_kernel.hpp'}),
     'particle_nd_inst.hip': ([], {'particle_nd_kernel.hpp'}),
     'gaussfilter_inst.hip': ([], {'gaussfilter_kernel.hpp'}),
+    # the diagnostic of the shared layer itself: no family
+    'device_math_inst.hip': ([], set()),
 }
 
 
