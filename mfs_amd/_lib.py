@@ -13,6 +13,9 @@ MODE_ODD_TAIL = 0x100   # MFS_MODE_ODD_TAIL: 2N + 1 moments per row (include/mfs
 TRANS = {'operator': 0, 'gaussian': 1}
 UMAP = {'x': 0, 'tanh': 1}
 LIK = {'bernoulli_logistic': 0, 'poisson_softplus': 1, 'gaussian': 2, 'bearing_gaussian': 3}
+# what mfs_plan_1d_kernel_build / mfs_plan_1d_kernel_traits report: MFS_BUILD_* and MFS_TRAITS_*
+BUILD = {'dense': 0, 'fast': 1, 'fast_one_wave': 2, 'fast_one_wave_spec': 3}
+TRAITS = {'runtime': 0, 'central_tanh_bernoulli': 1, 'central_identity_gaussian': 2}
 MAX_N = 32
 GRID_MAX_N = 8192   # MFS_GRID_MAX_N: grid points of the brute-force grid filter
 GRID_MAX_NZ = 8192  # MFS_GRID_MAX_NZ: frequencies of its characteristic functions

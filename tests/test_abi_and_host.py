@@ -194,6 +194,9 @@ def test_header_constants_match_the_python_mirror():
     val = lambda name: int(defs[name], 0)   # noqa: E731
     assert val('MFS_ABI_VERSION') == _lib.ABI_VERSION
     assert val('MFS_MODE_ODD_TAIL') == _lib.MODE_ODD_TAIL
+    assert {k: val('MFS_BUILD_' + k.upper()) for k in _lib.BUILD} == _lib.BUILD
+    assert {k: val('MFS_TRAITS_' + k.upper()) for k in _lib.TRAITS} == _lib.TRAITS
+    assert [sum(k.startswith(p) for k in defs) for p in ('MFS_BUILD_', 'MFS_TRAITS_')] == [4, 3] == [len(_lib.BUILD), len(_lib.TRAITS)]
     assert (val('MFS_ND_TERMS'), val('MFS_ND_ROWS'), val('MFS_ND_TERMS_MAX'), val('MFS_ND_ROWS_MAX')) == \
            (_lib.ND_TERMS, _lib.ND_ROWS, _lib.ND_TERMS_MAX, _lib.ND_ROWS_MAX)
     assert (val('MFS_ND_MAX_EXTENT'), val('MFS_ND_MAX_EXTENT_HI'), val('MFS_ND_MAX_FACTORS')) == \

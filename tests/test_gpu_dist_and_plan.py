@@ -11,34 +11,17 @@ import pytest
 
 from mfs_amd import _lib, synth, dist
 from mfs_amd.one_dim import filtering, moments, ss_models
+from tests.plan_api import CENTRAL_OUTPUTS, run_plan_1d, run_plan_nd
 
 pytestmark = pytest.mark.gpu
 
 
 def _plan_run(N, T, B, chunk, ys, ic, tables, lik, want_moments=True):
-    L = _lib.lib()
-    model, keep = filtering.build_model_struct(tables, lik, B)
-    plan = C.c_void_p()
-    _lib.check(L.mfs_plan_1d_create(C.byref(plan), C.byref(model), 1, N, T, B, 0, chunk, 0))
-    d_m0 = _lib.DeviceBuffer.from_array(ic.cms)
-    d_mean0 = _lib.DeviceBuffer.from_array(np.array([ic.mean]))
-    d_ys = _lib.DeviceBuffer.from_array(ys)
-    d_mom = _lib.DeviceBuffer(B * T * 2 * N * 8) if want_moments else None
-    d_means, d_nell, d_fn = _lib.DeviceBuffer(B * T * 8), _lib.DeviceBuffer(B * 8), _lib.DeviceBuffer(B * 4)
-    stream = C.c_void_p()
-    _lib.check(L.mfs_stream_create(C.byref(stream)))
-    outs = []
-    for _ in range(2):  # second run replays the cached graph when chunked
-        _lib.check(L.mfs_plan_1d_run(plan, d_m0.ptr, 0, d_mean0.ptr, None, d_ys.ptr, d_mom.ptr if d_mom else None,
-                                     d_means.ptr, None, d_nell.ptr, d_fn.ptr, stream))
-        _lib.check(L.mfs_stream_synchronize(stream))
-        outs.append((d_mom.to_array((B, T, 2 * N)) if d_mom else None, d_means.to_array((B, T)),
-                     d_nell.to_array((B,)), d_fn.to_array((B,), np.int32)))
-    geo = [C.c_int() for _ in range(4)]
-    _lib.check(L.mfs_plan_1d_geometry(plan, *[C.byref(g) for g in geo]))
-    _lib.check(L.mfs_plan_1d_destroy(plan))
-    _lib.check(L.mfs_stream_destroy(stream))
-    return outs, [g.value for g in geo]
+    """Two runs of one plan (the second replays the cached graph when chunked), start state shared by the batch:
+    ([Outputs of each run], [lanes per filter, filters per block, grid])."""
+    report, outs = run_plan_1d((tables, lik), N, T, B, chunk=chunk, m0=ic.cms, mean0=ic.mean, ys=ys, runs=2,
+                               outputs=CENTRAL_OUTPUTS[0 if want_moments else 1:])
+    return outs, [report.lanes_per_filter, report.filters_per_block, report.grid]
 
 
 def test_chunked_graph_replay_is_bit_identical_to_single_launch():
@@ -49,20 +32,18 @@ def test_chunked_graph_replay_is_bit_identical_to_single_launch():
     ys, _ = synth.benes_bernoulli_batch(B, T, dt, seed=21)
     (whole, whole2), geo = _plan_run(N, T, B, 0, ys, ic, tables, lik)
     (chunked, chunked2), _ = _plan_run(N, T, B, 25, ys, ic, tables, lik)  # 5 launches captured into one graph
-    for a, b in zip(whole, chunked):
-        npt.assert_array_equal(a, b)
-    for a, b in zip(chunked, chunked2):
-        npt.assert_array_equal(a, b)
-    for a, b in zip(whole, whole2):
-        npt.assert_array_equal(a, b)
+    for first, second in ((whole, chunked), (chunked, chunked2), (whole, whole2)):
+        for name in CENTRAL_OUTPUTS:
+            npt.assert_array_equal(getattr(first, name), getattr(second, name))
     # and the host-pointer API gives the same numbers
     m, means, nell = filtering.moment_filter_cms(c, mu, pmf, ic.cms, ic.mean, ys)
-    npt.assert_array_equal(m, whole[0])
-    npt.assert_array_equal(nell, whole[2])
+    npt.assert_array_equal(m, whole.moments)
+    npt.assert_array_equal(nell, whole.nell)
     assert geo[0] == 8 and geo[1] == 8 and geo[2] == -(-B // geo[1])   # N = 7: eight lanes per filter, eight filters per wave
     # NLL-only runs (no moment stream) agree too
     (nll_only, _), _ = _plan_run(N, T, B, 0, ys, ic, tables, lik, want_moments=False)
-    npt.assert_array_equal(nll_only[2], whole[2])
+    assert nll_only.moments is None
+    npt.assert_array_equal(nll_only.nell, whole.nell)
 
 
 def test_rccl_single_rank_allgather():
@@ -107,37 +88,28 @@ def test_nd_plan_device_pointers_match_host_entry():
     ys, _ = synth.prey_predator_batch(B, T, dt, seed=3)
     cmss, means, nell = fnd.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], pmf, ys, (mi, inds), gs.cms, gs.mean)
 
-    L = _lib.lib()
     tables = fnd._trace_transition((fns[1], 'multi-index'), 'central', (mi, inds))
     mstruct, keep = fnd._model_struct(tables, fnd._trace_likelihood(pmf, 2))
+    geo, runs = run_plan_nd(mstruct, N, T, B, mi, inds, m0=gs.cms, mean0=gs.mean, ys=ys, outputs=(CENTRAL_OUTPUTS,) * 2)
+    assert geo.threads_per_filter == 256 and geo.grid == B and 0 < geo.lds_bytes <= 160 * 1024
+    for out in runs:  # a plan is reusable
+        npt.assert_array_equal(out.moments, cmss)
+        npt.assert_array_equal(out.means, means)
+        npt.assert_array_equal(out.nell, nell)
+        assert np.all(out.first_nan == -1)
+    # scaled mode without scale0 is an argument error, not a crash
+    L = _lib.lib()
     mi32, inds32 = np.ascontiguousarray(mi, dtype=np.int32), np.ascontiguousarray(inds, dtype=np.int32)
-    plan = C.c_void_p()
-    _lib.check(L.mfs_plan_nd_create(C.byref(plan), C.byref(mstruct), _lib.MODE['central'], N, T, B, z, _lib.ptr(mi32),
-                                    _lib.ptr(inds32), 0, 0))
-    geo = [C.c_int() for _ in range(3)]
-    _lib.check(L.mfs_plan_nd_geometry(plan, *[C.byref(g) for g in geo]))
-    assert geo[0].value == 256 and geo[1].value == B and 0 < geo[2].value <= 160 * 1024
     d_m0 = _lib.DeviceBuffer.from_array(np.ascontiguousarray(gs.cms))
     d_mean0 = _lib.DeviceBuffer.from_array(np.ascontiguousarray(gs.mean, dtype=np.float64))
-    d_ys = _lib.DeviceBuffer.from_array(ys)
-    d_mom, d_means = _lib.DeviceBuffer(B * T * z * 8), _lib.DeviceBuffer(B * T * 2 * 8)
-    d_nell, d_fn = _lib.DeviceBuffer(B * 8), _lib.DeviceBuffer(B * 4)
-    for _ in range(2):  # a plan is reusable
-        _lib.check(L.mfs_plan_nd_run(plan, d_m0.ptr, 0, d_mean0.ptr, None, d_ys.ptr, d_mom.ptr, d_means.ptr, None,
-                                     d_nell.ptr, d_fn.ptr, None))
-    _lib.check(L.mfs_device_synchronize())
-    npt.assert_array_equal(d_mom.to_array((B, T, z)), cmss)
-    npt.assert_array_equal(d_means.to_array((B, T, 2)), means)
-    npt.assert_array_equal(d_nell.to_array((B,)), nell)
-    assert np.all(d_fn.to_array((B,), np.int32) == -1)
-    # scaled mode without scale0 is an argument error, not a crash
+    d_ys, d_nell = _lib.DeviceBuffer.from_array(ys), _lib.DeviceBuffer(B * 8)
     plan2 = C.c_void_p()
     _lib.check(L.mfs_plan_nd_create(C.byref(plan2), C.byref(mstruct), _lib.MODE['scaled'], N, T, B, z, _lib.ptr(mi32),
                                     _lib.ptr(inds32), 0, 0))
     rc = L.mfs_plan_nd_run(plan2, d_m0.ptr, 0, d_mean0.ptr, None, d_ys.ptr, None, None, None, d_nell.ptr, None, None)
     assert rc == _lib.MFS_EINVAL if hasattr(_lib, 'MFS_EINVAL') else rc < 0
     _lib.check(L.mfs_plan_nd_destroy(plan2))
-    _lib.check(L.mfs_plan_nd_destroy(plan))
+    del keep
 
 
 def test_pipelined_host_entry_is_bit_identical_and_reuses_the_pool(monkeypatch):

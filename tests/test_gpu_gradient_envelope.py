@@ -16,6 +16,7 @@ import pytest
 
 from mfs_amd import _lib
 from tests import gradient_ref as G
+from tests.plan_api import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -29,8 +30,7 @@ def _bits(a):
 
 
 def _assert_same_bits(got, want, what):
-    for g, w, name in zip(got, want, ('nell', 'grad', 'first_nan')):
-        assert np.array_equal(_bits(g), _bits(w)), f'{what}: {name} differs\n{g}\n{w}'
+    assert_same_bits(got, want, what, names=('nell', 'grad', 'first_nan'))
 
 
 def _check_against_reference(case, outputs=None):

@@ -4,17 +4,17 @@ Lorenz-63 in units of 10 with operator TME-2 tables or a Normal closure, a 3-D l
 factors, a 3-D OU model with a Poisson factor; raw, central and scaled modes; the LDL^T completion; batch independence,
 per-replicate tables, NaN poisoning and the device-pointer plan.  Only filter outputs are compared (the rule's nodes are not
 unique when the K_k have repeated eigenvalues)."""
-import ctypes as C
 import math
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import _lib, stats
+from mfs_amd import stats
 from mfs_amd.multi_dims import filtering, moments
 from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from oracle import models as om, multi_dims as omd, one_dim as o1, tme_sympy
+from tests.plan_api import run_plan_nd
 
 pytestmark = pytest.mark.gpu
 
@@ -352,35 +352,13 @@ def test_plan_is_bit_identical_to_the_host_entry_point():
     ys = np.ascontiguousarray(_lorenz_ys(B, T, seed=11)[..., None])
     cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys[..., 0], (mi, inds), cms0, M0)
     model, keep = filtering._model_struct3(fns[1].tables, filtering._trace_likelihood(_pdf, 3), B)
-    L = _lib.lib()
-    plan = C.c_void_p()
-    mi32 = np.ascontiguousarray(mi, dtype=np.int32)
-    inds32 = np.ascontiguousarray(inds, dtype=np.int32)
-    _lib.check(L.mfs_plan_nd3_create(C.byref(plan), C.byref(model), _lib.MODE['central'], N, T, B, mi.shape[0],
-                                     _lib.ptr(mi32), _lib.ptr(inds32), 0, 0))
-    try:
-        tpf, grid, lds = C.c_int(), C.c_int(), C.c_int()
-        _lib.check(L.mfs_plan_nd3_geometry(plan, C.byref(tpf), C.byref(grid), C.byref(lds)))
-        assert tpf.value == 256 and grid.value == B and 0 < lds.value <= 160 * 1024
-        z = mi.shape[0]
-        d_m0 = _lib.DeviceBuffer.from_array(np.ascontiguousarray(cms0))
-        d_mean0 = _lib.DeviceBuffer.from_array(np.ascontiguousarray(M0))
-        d_ys = _lib.DeviceBuffer.from_array(ys)
-        d_mom = _lib.DeviceBuffer(B * T * z * 8)
-        d_means = _lib.DeviceBuffer(B * T * 3 * 8)
-        d_nell = _lib.DeviceBuffer(B * 8)
-        _lib.check(L.mfs_plan_nd3_run(plan, d_m0.ptr, 0, d_mean0.ptr, None, d_ys.ptr, d_mom.ptr, d_means.ptr, None,
-                                      d_nell.ptr, None, None))
-        _lib.check(L.mfs_device_synchronize())
-        npt.assert_array_equal(d_mom.to_array((B, T, z)), cmss)
-        npt.assert_array_equal(d_means.to_array((B, T, 3)), means)
-        npt.assert_array_equal(d_nell.to_array((B,)), nell)
-        # NLL only: NULL outputs are allowed
-        d_nell2 = _lib.DeviceBuffer(B * 8)
-        _lib.check(L.mfs_plan_nd3_run(plan, d_m0.ptr, 0, d_mean0.ptr, None, d_ys.ptr, None, None, None, d_nell2.ptr, None,
-                                      None))
-        _lib.check(L.mfs_device_synchronize())
-        npt.assert_array_equal(d_nell2.to_array((B,)), nell)
-    finally:
-        L.mfs_plan_nd3_destroy(plan)
+    # the second run is NLL only: NULL outputs are allowed
+    geo, (full, nll_only) = run_plan_nd(model, N, T, B, mi, inds, m0=cms0, mean0=M0, ys=ys,
+                                        outputs=(('moments', 'means', 'nell'), ('nell',)))
+    assert geo.threads_per_filter == 256 and geo.grid == B and 0 < geo.lds_bytes <= 160 * 1024
+    npt.assert_array_equal(full.moments, cmss)
+    npt.assert_array_equal(full.means, means)
+    npt.assert_array_equal(full.nell, nell)
+    assert nll_only[:3] == (None, None, None) and nll_only.first_nan is None
+    npt.assert_array_equal(nll_only.nell, nell)
     del keep

@@ -23,6 +23,7 @@ from mfs_amd.multi_dims import filtering, moments
 from mfs_amd.multi_dims.moments import marginalise_moments
 from mfs_amd.one_dim import filtering as f1, moments as m1
 from oracle import models as om, multi_dims as omd, one_dim as o1, tme_sympy
+from .plan_api import assert_same_bits
 from .test_gpu_nd3 import (C0, DT, M0, _assert_moments, _disp, _disp_sympy, _init, _lorenz, _lorenz_sympy, _lorenz_ys,
                            _moment_err, _opdf, _pdf, _tables)
 
@@ -505,9 +506,7 @@ def test_likelihood_wiring(case):
 
 
 def _assert_same_bits(a, b, keys=('m', 'mean', 'scale', 'nell', 'fn')):
-    for k in keys:
-        if k in a:
-            npt.assert_array_equal(a[k], b[k], err_msg=k)
+    assert_same_bits([a.get(k) for k in keys], [b.get(k) for k in keys], names=keys)
 
 
 def test_per_replicate_likelihood_parameters_are_bit_identical_to_single_runs():

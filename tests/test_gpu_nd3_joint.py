@@ -13,17 +13,17 @@ range-azimuth-elevation at N = 3 runs T = 8.  The Lotka--Volterra cases run T = 
 softplus(x0 + x1 + x2) ~ 3; Bernoulli draws of a degree-2 logit).  Each headline test asserts that the oracle run is finite, so
 a comparison of NaN patterns cannot pass for a comparison of numbers.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import _lib, stats, sym
+from mfs_amd import stats, sym
 from mfs_amd.multi_dims import filtering
 from oracle import models as om
 from .test_gpu_nd3 import BETA, DT, M0, C0, RHO, SIG, _moment_err, _tables
+from .plan_api import run_plan_nd
 from .test_gpu_nd3_envelope import (LV_C0, LV_M0, MODES, _assert_same_bits, compare, device, family, first_bad, initial, lv_path,
                                     oracle, stack_initial)
 
@@ -354,28 +354,12 @@ def test_plan_is_bit_identical_to_the_host_entry_point():
     factors = filtering._trace_likelihood(rae_pdf(), 3)
     model, keep = filtering._model_struct3(fns[1].tables, [], B, ny=3)
     joint, keep_joint = filtering._joint_struct3(factors, B)
-    L = _lib.lib()
-    plan = C.c_void_p()
-    mi32, inds32 = np.ascontiguousarray(mi, dtype=np.int32), np.ascontiguousarray(inds, dtype=np.int32)
-    _lib.check(L.mfs_plan_nd3_create_joint(C.byref(plan), C.byref(model), C.byref(joint), _lib.MODE['central'], N, T, B,
-                                           mi.shape[0], _lib.ptr(mi32), _lib.ptr(inds32), 0, 0))
-    try:
-        tpf, grid, lds = C.c_int(), C.c_int(), C.c_int()
-        _lib.check(L.mfs_plan_nd3_geometry(plan, C.byref(tpf), C.byref(grid), C.byref(lds)))
-        assert tpf.value == 256 and grid.value == B and 0 < lds.value <= 160 * 1024
-        z = mi.shape[0]
-        d_m0 = _lib.DeviceBuffer.from_array(np.ascontiguousarray(st['cms']))
-        d_mean0 = _lib.DeviceBuffer.from_array(np.ascontiguousarray(st['mean']))
-        d_ys = _lib.DeviceBuffer.from_array(ys)
-        d_mom, d_means, d_nell = _lib.DeviceBuffer(B * T * z * 8), _lib.DeviceBuffer(B * T * 3 * 8), _lib.DeviceBuffer(B * 8)
-        _lib.check(L.mfs_plan_nd3_run(plan, d_m0.ptr, 0, d_mean0.ptr, None, d_ys.ptr, d_mom.ptr, d_means.ptr, None,
-                                      d_nell.ptr, None, None))
-        _lib.check(L.mfs_device_synchronize())
-        npt.assert_array_equal(d_mom.to_array((B, T, z)), host['m'])
-        npt.assert_array_equal(d_means.to_array((B, T, 3)), host['mean'])
-        npt.assert_array_equal(d_nell.to_array((B,)), host['nell'])
-    finally:
-        L.mfs_plan_nd3_destroy(plan)
+    geo, (out,) = run_plan_nd(model, N, T, B, mi, inds, joint=joint, m0=st['cms'], mean0=st['mean'], ys=ys,
+                              outputs=(('moments', 'means', 'nell'),))
+    assert geo.threads_per_filter == 256 and geo.grid == B and 0 < geo.lds_bytes <= 160 * 1024
+    npt.assert_array_equal(out.moments, host['m'])
+    npt.assert_array_equal(out.means, host['mean'])
+    npt.assert_array_equal(out.nell, host['nell'])
     del keep, keep_joint
 
 

@@ -4,71 +4,20 @@ eigenvalue loop that freezes only x of a converged lane, and the poison flag tak
 of them changes a floating-point operation that feeds an output, so every check is equality of bits -- moments, means, NLL,
 NaN positions and first_nan -- against the one-wave build (MFS_FAST_PARTNER=0), through the plan API of the C ABI.
 
-Orders N = 14, 15 and the three (model, transition) pairs with a fixed-traits build.  The inputs are the recipes of
-tests/test_gpu_fast_partner.py.  The one-wave reference of a set of inputs is computed once, in one launch, and shared."""
-import ctypes as C
+Orders N = 14, 15 and the three (model, transition) pairs with a fixed-traits build.  The inputs are the recipes that
+tests/test_gpu_fast_partner.py uses (tests/plan_api.py).  The one-wave reference of a set of inputs is computed once, in one
+launch, and shared."""
 import math
 
 import numpy as np
 import pytest
 
-from mfs_amd import _lib
-from mfs_amd.one_dim import filtering
-from tests.test_gpu_fast_straightline import MID_RUN, _bernoulli_ys
-from tests.test_gpu_fast_traits import COMBOS, ONE_WAVE_SPEC, _assert_identical, _model
+from tests.plan_api import (COMBOS, MID_RUN, MID_RUN_B, assert_same_bits, bernoulli_ys, combo_model, one_wave_build,
+                            partner_inputs as _inputs, partner_variant as _partner)
 
 pytestmark = pytest.mark.gpu
 
-FILTERS_PER_WORKGROUP = 16
 CASES = [(combo, N) for combo in sorted(COMBOS) for N in (14, 15)]
-
-
-@pytest.fixture(autouse=True)
-def _default_switches(monkeypatch):
-    for name in ('MFS_PREDICT_RULE', 'MFS_FAST_BUILD', 'MFS_FAST_TRAITS', 'MFS_FAST_PARTNER'):
-        monkeypatch.delenv(name, raising=False)
-
-
-def _run(combo, N, ys, m0, *, chunk=0, moments_out=True):
-    """One central-mode plan run on (B, T) measurements and (B, 2N) start moments:
-    ((moments, means, nell, first_nan), (build, traits, partner), (filters per block, grid))."""
-    ic, tables, lik, _ = _model(combo, N)
-    nb, nt = ys.shape
-    L = _lib.lib()
-    model, keep = filtering.build_model_struct(tables, lik, nb)
-    plan = C.c_void_p()
-    _lib.check(L.mfs_plan_1d_create(C.byref(plan), C.byref(model), 1, N, nt, nb, 0, chunk, 0))
-    build, traits, partner = C.c_int(-1), C.c_int(-1), C.c_int(-1)
-    _lib.check(L.mfs_plan_1d_kernel_build(plan, C.byref(build)))
-    _lib.check(L.mfs_plan_1d_kernel_traits(plan, C.byref(traits)))
-    _lib.check(L.mfs_plan_1d_kernel_partner(plan, C.byref(partner)))
-    fpb, grid = C.c_int(-1), C.c_int(-1)
-    _lib.check(L.mfs_plan_1d_geometry(plan, None, C.byref(fpb), C.byref(grid), None))
-    d_m0 = _lib.DeviceBuffer.from_array(np.ascontiguousarray(m0))
-    d_mean0 = _lib.DeviceBuffer.from_array(np.full(nb, ic.mean))
-    d_ys = _lib.DeviceBuffer.from_array(np.ascontiguousarray(ys))
-    d_mom = _lib.DeviceBuffer(nb * nt * 2 * N * 8) if moments_out else None
-    d_means, d_nell, d_fn = _lib.DeviceBuffer(nb * nt * 8), _lib.DeviceBuffer(nb * 8), _lib.DeviceBuffer(nb * 4)
-    stream = C.c_void_p()
-    _lib.check(L.mfs_stream_create(C.byref(stream)))
-    _lib.check(L.mfs_plan_1d_run(plan, d_m0.ptr, 1, d_mean0.ptr, None, d_ys.ptr, d_mom.ptr if d_mom else None, d_means.ptr,
-                                 None, d_nell.ptr, d_fn.ptr, stream))
-    _lib.check(L.mfs_stream_synchronize(stream))
-    out = (d_mom.to_array((nb, nt, 2 * N)) if d_mom else np.zeros(0), d_means.to_array((nb, nt)), d_nell.to_array((nb,)),
-           d_fn.to_array((nb,), np.int32))
-    _lib.check(L.mfs_plan_1d_destroy(plan))
-    _lib.check(L.mfs_stream_destroy(stream))
-    del keep
-    return out, (build.value, traits.value, partner.value), (fpb.value, grid.value)
-
-
-def _partner(combo, N, ys, m0, **kw):
-    """The default plan: it must be the partner-wave variant, reported as the fixed-traits one-wave build."""
-    out, which, (fpb, grid) = _run(combo, N, ys, m0, **kw)
-    assert which == (ONE_WAVE_SPEC, COMBOS[combo], 1)
-    assert (fpb, grid) == (FILTERS_PER_WORKGROUP, -(-ys.shape[0] // FILTERS_PER_WORKGROUP))
-    return out
-
 
 _REFERENCES = {}
 
@@ -77,35 +26,21 @@ def _one_wave(monkeypatch, key, combo, N, ys, m0):
     """The one-wave build's outputs on these inputs, whole T in one launch, with moments: computed once per `key`, never
     modified (NLL-only and chunked runs of the variant are compared with the parts of it they produce)."""
     if key not in _REFERENCES:
-        monkeypatch.setenv('MFS_FAST_PARTNER', '0')
-        out, which, (fpb, _) = _run(combo, N, ys, m0)
-        monkeypatch.delenv('MFS_FAST_PARTNER')
-        assert which == (ONE_WAVE_SPEC, COMBOS[combo], 0) and fpb == 4
+        out = one_wave_build(monkeypatch, combo, N, ys, m0)
         for x in out:
-            x.setflags(write=False)
+            if x is not None:
+                x.setflags(write=False)
         _REFERENCES[key] = out
     return _REFERENCES[key]
 
 
-def _inputs(combo, N, nb, nt, poison=True):
-    """Bernoulli measurements (a Gaussian law accepts 0 / 1 as well) and the model's start moments; replicate 1 starts from a
-    point mass, so it is poisoned at step 0 -- in the cold rule of the main wave -- next to live replicates."""
-    from mfs_amd import synth
-    from mfs_amd.one_dim import ss_models
-    ys = synth.benes_bernoulli_batch(nb, nt, ss_models.benes_bernoulli(N)[0], seed=4100 + 16 * N + nb)[0]
-    m0 = np.tile(_model(combo, N)[0].cms, (nb, 1))
-    if poison and nb > 1:
-        m0[1, 1:] = 0.
-    return ys, m0
-
-
 def _assert_poison_structure(out, nt):
     """Nothing before first_nan is NaN, everything from first_nan on is: moments and means (the NLL of a poisoned one is NaN)."""
-    moments, means, nell, first_nan = out
+    moments, means, _, nell, first_nan = out
     for b in range(means.shape[0]):
         f = first_nan[b] if first_nan[b] >= 0 else nt
         assert np.isfinite(means[b, :f]).all() and np.isnan(means[b, f:]).all(), (b, f)
-        if moments.size:
+        if moments is not None:
             assert np.isfinite(moments[b, :f]).all() and np.isnan(moments[b, f:]).all(), (b, f)
         assert np.isnan(nell[b]) == (f < nt), (b, f)
 
@@ -118,9 +53,9 @@ def _assert_poison_structure(out, nt):
 def test_window_edges(combo, N, B, monkeypatch):
     for nt in (1, 15, 16, 17, 33, 48):
         ys, m0 = _inputs(combo, N, B, nt)
-        variant = _partner(combo, N, ys, m0)
-        _assert_identical(variant, _one_wave(monkeypatch, ('window', combo, N, B, nt), combo, N, ys, m0))
-        assert variant[3][1] == 0 and (np.delete(variant[3], 1) != 0).all()
+        variant = _partner(monkeypatch, combo, N, ys, m0)
+        assert_same_bits(variant, _one_wave(monkeypatch, ('window', combo, N, B, nt), combo, N, ys, m0))
+        assert variant.first_nan[1] == 0 and (np.delete(variant.first_nan, 1) != 0).all()
         _assert_poison_structure(variant, nt)
 
 
@@ -135,8 +70,8 @@ def test_chunk_edges(combo, N, moments_out, monkeypatch):
     reference = _one_wave(monkeypatch, ('chunk', combo, N), combo, N, ys, m0)
     part = reference if moments_out else reference[1:]
     for chunk in (0, 1, 7, 16, 17):
-        out = _partner(combo, N, ys, m0, chunk=chunk, moments_out=moments_out)
-        _assert_identical(out if moments_out else out[1:], part)
+        out = _partner(monkeypatch, combo, N, ys, m0, chunk=chunk, moments_out=moments_out)
+        assert_same_bits(out if moments_out else out[1:], part)
 
 
 # ---- 3. the late flag: replicates poisoned mid-run next to live ones.  The (N, T, seed) triples are those of
@@ -153,10 +88,10 @@ ORACLE_FIRST_NAN = {14: [166, 157, 206, -1, 213, -1], 15: [-1, -1, 118, 219, -1,
 
 def _mid_run(N, monkeypatch):
     nt, seed = MID_RUN[N]
-    ys = _bernoulli_ys(N, nt, seed)
-    m0 = np.tile(_model('benes_tme3', N)[0].cms, (ys.shape[0], 1))
+    ys = bernoulli_ys(N, nt, seed, MID_RUN_B)
+    m0 = np.tile(combo_model('benes_tme3', N)[0].cms, (ys.shape[0], 1))
     reference = _one_wave(monkeypatch, ('mid', N), 'benes_tme3', N, ys, m0)
-    first_nan = reference[3]
+    first_nan = reference.first_nan
     # the precondition: replicates poisoned mid-run next to replicates that live to T, in the first wave (replicates 0..3)
     assert ((first_nan[:4] > 0) & (first_nan[:4] < nt - 1)).any() and (first_nan[:4] < 0).any(), first_nan
     both = (first_nan >= 0) & (np.array(ORACLE_FIRST_NAN[N]) >= 0)
@@ -167,21 +102,21 @@ def _mid_run(N, monkeypatch):
 @pytest.mark.parametrize('N', [14, 15])
 def test_late_flag_mid_run(N, monkeypatch):
     nt, ys, m0, reference = _mid_run(N, monkeypatch)
-    variant = _partner('benes_tme3', N, ys, m0)
-    np.testing.assert_array_equal(variant[3], reference[3])      # neither a step early nor a step late
+    variant = _partner(monkeypatch, 'benes_tme3', N, ys, m0)
+    np.testing.assert_array_equal(variant.first_nan, reference.first_nan)      # neither a step early nor a step late
     _assert_poison_structure(variant, nt)
-    _assert_identical(variant, reference)
-    _assert_identical(_partner('benes_tme3', N, ys, m0, moments_out=False)[1:], reference[1:])
+    assert_same_bits(variant, reference)
+    assert_same_bits(_partner(monkeypatch, 'benes_tme3', N, ys, m0, moments_out=False)[1:], reference[1:])
 
 
 @pytest.mark.parametrize('N', [14, 15])
 def test_late_flag_at_chunk_edges(N, monkeypatch):
     nt, ys, m0, reference = _mid_run(N, monkeypatch)
-    for p in sorted({int(p) for p in reference[3] if p >= 0}):
+    for p in sorted({int(p) for p in reference.first_nan if p >= 0}):
         for chunk in (p + 1, p):      # p = chunk - 1: the last step of the first launch; p = chunk: the first step of the second
-            out = _partner('benes_tme3', N, ys, m0, chunk=chunk)
+            out = _partner(monkeypatch, 'benes_tme3', N, ys, m0, chunk=chunk)
             _assert_poison_structure(out, nt)
-            _assert_identical(out, reference)
+            assert_same_bits(out, reference)
 
 
 @pytest.mark.parametrize('N', [14, 15])
@@ -189,13 +124,13 @@ def test_late_flag_leaves_live_neighbours_alone(N, monkeypatch):
     """The live replicates of the mid-run batches share their wave with replicates that die: each of them alone in a launch
     gives the bits it gives in the batch, which are the one-wave build's."""
     nt, ys, m0, reference = _mid_run(N, monkeypatch)
-    batch = _partner('benes_tme3', N, ys, m0)
-    live = [b for b in range(ys.shape[0]) if reference[3][b] < 0]
+    batch = _partner(monkeypatch, 'benes_tme3', N, ys, m0)
+    live = [b for b in range(ys.shape[0]) if reference.first_nan[b] < 0]
     for b in live:
-        assert np.isfinite(batch[0][b]).all() and np.isfinite(batch[1][b]).all() and np.isfinite(batch[2][b])
-        alone = _partner('benes_tme3', N, ys[b:b + 1], m0[b:b + 1])
-        _assert_identical(alone, [x[b:b + 1] for x in batch])
-        _assert_identical(alone, [x[b:b + 1] for x in reference])
+        assert np.isfinite(batch.moments[b]).all() and np.isfinite(batch.means[b]).all() and np.isfinite(batch.nell[b])
+        alone = _partner(monkeypatch, 'benes_tme3', N, ys[b:b + 1], m0[b:b + 1])
+        assert_same_bits(alone, batch.rows(slice(b, b + 1)))
+        assert_same_bits(alone, reference.rows(slice(b, b + 1)))
 
 
 # ---- 4. the values of the poison flag: start moments whose Hankel matrix has its first pivot that is not > 0 at position 0,
@@ -236,15 +171,15 @@ def test_poison_flag_values(combo, N, monkeypatch):
     m0, names = _flag_moments(N)
     ys = _inputs(combo, N, len(names), nt, poison=False)[0]
     reference = _one_wave(monkeypatch, ('flags', combo, N), combo, N, ys, m0)
-    variant = _partner(combo, N, ys, m0)
-    np.testing.assert_array_equal(variant[3], reference[3], err_msg=str(names))
-    _assert_identical(variant, reference)
-    first_nan = dict(zip(names, variant[3]))
+    variant = _partner(monkeypatch, combo, N, ys, m0)
+    np.testing.assert_array_equal(variant.first_nan, reference.first_nan, err_msg=str(names))
+    assert_same_bits(variant, reference)
+    first_nan = dict(zip(names, variant.first_nan))
     # m_{2N-1} enters only the last row of the extended matrix: no pivot, a NaN Jacobi entry -- whatever the one-wave build says
     expected_zero = [n for n in names if not n.startswith('live') and n != 'NaN in the last row only']
     assert all(first_nan[n] == 0 for n in expected_zero), first_nan
     assert first_nan['live'] != 0 and first_nan['live again'] != 0, first_nan
-    _assert_identical(_partner(combo, N, ys, m0, chunk=7), reference)
+    assert_same_bits(_partner(monkeypatch, combo, N, ys, m0, chunk=7), reference)
 
 
 # ---- 5. the last step's mean is stored behind the loop
@@ -254,6 +189,6 @@ def test_last_step_mean(combo, N, monkeypatch):
         ys, m0 = _inputs(combo, N, 5, nt)
         reference = _one_wave(monkeypatch, ('window', combo, N, 5, nt), combo, N, ys, m0)
         for chunk in (0, 1):
-            means = _partner(combo, N, ys, m0, chunk=chunk)[1]
-            _assert_identical([means[:, -1]], [reference[1][:, -1]])
+            means = _partner(monkeypatch, combo, N, ys, m0, chunk=chunk).means
+            assert_same_bits([means[:, -1]], [reference.means[:, -1]])
             assert np.isnan(means[1, -1]) and np.isfinite(np.delete(means[:, -1], 1)).all()
