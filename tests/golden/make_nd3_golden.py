@@ -2,12 +2,12 @@
 
 The NumPy oracle (oracle/multi_dims.py with the SymPy TME tables of oracle/tme_sympy.py) takes ~0.15 s per step at N = 3 and
 ~1.2 s at N = 4, too slow to run inside a GPU test at these horizons.  Models: Lorenz-63 in units of 10 with a Gaussian factor
-on x_0 (tests/test_gpu_nd3.py) and the 3-species Lotka--Volterra model with dispersion diag(sigma_k x_k), a Gaussian factor on
-x_0 and a Poisson-softplus factor on x_2 (tests/test_gpu_nd3_envelope.py); their parameters are stored next to the outputs
-and checked by the test.  Operator TME-2 tables; one seeded replicate of each; N = 3 at T = 200 and N = 4 at T = 50 (the
+on x_0 and the 3-species Lotka--Volterra model with dispersion diag(sigma_k x_k), a Gaussian factor on x_0 and a
+Poisson-softplus factor on x_2, both of tests/nd3_models.py; their parameters are stored next to the outputs and checked by
+the test.  Operator TME-2 tables; one seeded replicate of each; N = 3 at T = 200 and N = 4 at T = 50 (the
 first 50 measurements); central and scaled modes.  Run from the repository root:
 
-    python tests/golden/make_nd3_golden.py [--procs P]
+    python tests/golden/make_nd3_golden.py [--procs P] [--out PATH]
 """
 import argparse
 import math
@@ -26,46 +26,13 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from oracle import models as om, multi_dims as omd, tme_sympy  # noqa: E402
+from oracle import multi_dims as omd, tme_sympy  # noqa: E402
+from tests.nd3_models import DT as LORENZ_DT, M0 as LORENZ_M0, C0 as LORENZ_C0, SD as LORENZ_SD  # noqa: E402
+from tests.nd3_models import LV_A, LV_C0, LV_DT, LV_M0, LV_SD, LV_SIG, MODELS, lorenz_drift  # noqa: E402
 
 T_LONG = 200
 N_T = ((3, 200), (4, 50))
 MODES = ('central', 'scaled')
-
-# Lorenz-63 in units of 10 (x = X / 10), dispersion 0.1 I, y = x_0 + N(0, 0.5^2)
-LORENZ_DT, LORENZ_SD = 0.01, 0.5
-LORENZ_M0, LORENZ_C0 = np.array([0.1, 0.1, 2.4]), np.diag([0.01, 0.01, 0.01])
-# Lotka--Volterra: dx_i = x_i (r_i - sum_j A_ij x_j) dt + sigma_i x_i dW_i with r = A 1
-LV_A = np.array([[0.8, 0.3, 0.1], [0.2, 0.6, 0.1], [0.4, 0.2, 0.9]])
-LV_SIG = np.array([0.1, 0.15, 0.2])
-LV_DT, LV_SD = 0.05, 0.2
-LV_M0 = np.array([1.0, 0.9, 1.1])
-LV_C0 = np.array([[0.02, 0.005, 0.], [0.005, 0.03, -0.004], [0., -0.004, 0.025]])
-
-
-def lorenz_drift(x):
-    return [10. * (x[1] - x[0]), x[0] * (28. - 10. * x[2]) - x[1], 10. * x[0] * x[1] - 8. / 3. * x[2]]
-
-
-def lorenz_disp(x):
-    return [[0.1, 0, 0], [0, 0.1, 0], [0, 0, 0.1]]
-
-
-def lv_drift(x):
-    r = LV_A.sum(axis=1)
-    return [x[i] * (float(r[i]) - sum(float(LV_A[i, j]) * x[j] for j in range(3))) for i in range(3)]
-
-
-def lv_disp(x):
-    return [[float(LV_SIG[i]) * x[i] if i == j else 0. for j in range(3)] for i in range(3)]
-
-
-def lorenz_opdf(y, x):
-    return float(om.norm_pdf(y, x[0], LORENZ_SD))
-
-
-def lv_opdf(y, x):
-    return float(om.norm_pdf(y[0], x[0], LV_SD) * om.poisson_pmf(y[1], np.log1p(np.exp(x[2]))))
 
 
 def lorenz_ys(T, seed):
@@ -96,14 +63,13 @@ def lv_ys(T, seed):
     return ys
 
 
-MODELS = {'lorenz': (lorenz_drift, lorenz_disp, LORENZ_DT, LORENZ_M0, LORENZ_C0, lorenz_opdf),
-          'lv': (lv_drift, lv_disp, LV_DT, LV_M0, LV_C0, lv_opdf)}
+FROZEN = ('lorenz', 'lv')     # of tests/nd3_models.MODELS
 _G = {}   # SymPy closures shared with forked workers (lambdified functions do not pickle)
 
 
 def _one(job):
     model, N, mode = job
-    _, _, _, m0, c0, opdf = MODELS[model]
+    m0, c0, opdf = MODELS[model].mean0, MODELS[model].cov0, MODELS[model].opdf
     ocms, omean, omean_var = _G[model]
     T = dict(N_T)[N]
     ys = _G['ys'][model][:T]
@@ -125,15 +91,17 @@ def _one(job):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--procs', type=int, default=max(1, min(8, (os.cpu_count() or 2) - 1)))
+    ap.add_argument('--out', default=os.path.join(HERE, 'filter_nd3.npz'), help='where to write the record')
     a = ap.parse_args()
     t0 = time.time()
     _G['ys'] = {'lorenz': lorenz_ys(T_LONG, seed=1), 'lv': lv_ys(T_LONG, seed=2)}
     mi_max = omd.generate_graded_lexico_multi_indices(3, 2 * max(N for N, _ in N_T) - 1)
-    for model, (drift, disp, dt, *_) in MODELS.items():   # one table for both N: the closures look multi-indices up
-        _, ocms, omean, omean_var = tme_sympy.sde_cond_moments_tme_nd(drift, disp, 3, dt, 2, mi_max)
+    for model in FROZEN:   # one table for both N: the closures look multi-indices up
+        m = MODELS[model]
+        _, ocms, omean, omean_var = tme_sympy.sde_cond_moments_tme_nd(m.drift, m.disp, 3, m.dt, 2, mi_max)
         _G[model] = (ocms, omean, omean_var)
     print(f'tables in {time.time() - t0:.0f} s', flush=True)
-    jobs = [(model, N, mode) for model in MODELS for N, _ in N_T for mode in MODES]
+    jobs = [(model, N, mode) for model in FROZEN for N, _ in N_T for mode in MODES]
     if a.procs <= 1:
         res = [_one(j) for j in jobs]
     else:
@@ -149,9 +117,8 @@ def main():
             out[f'{key}_scales'] = scales
         bad = ~np.isfinite(m).all(axis=1)
         print(f'{key}: nell {nell:.10f}, first non-finite step {int(np.argmax(bad)) if bad.any() else -1}', flush=True)
-    path = os.path.join(HERE, 'filter_nd3.npz')
-    np.savez_compressed(path, **out)
-    print(f'filter_nd3.npz: {os.path.getsize(path) / 1024:.0f} KiB in {time.time() - t0:.0f} s', flush=True)
+    np.savez_compressed(a.out, **out)
+    print(f'{os.path.basename(a.out)}: {os.path.getsize(a.out) / 1024:.0f} KiB in {time.time() - t0:.0f} s', flush=True)
 
 
 if __name__ == '__main__':

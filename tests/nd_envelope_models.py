@@ -1,5 +1,6 @@
-"""Three d = 2 models for the envelope tests of filternd_kernel (tests/test_gpu_nd_envelope.py, tests/test_host_nd.py), each in
-a host form traced by mfs_amd.multi_dims.moments and an oracle form for oracle/tme_sympy.py + oracle/multi_dims.py.
+"""The d = 2 models of the envelope tests of filternd_kernel (tests/test_gpu_nd_envelope.py, tests/test_host_nd.py): drift and
+dispersion as callables on a sequence of the two state variables, which oracle/tme_sympy.py takes as they are and the host
+traces through nd_support.host_drift / host_disp.  What does not depend on the dimension is in tests/nd_support.py.
 
   lv2    two-species competitive Lotka--Volterra, dx_i = x_i (r_i - sum_j A_ij x_j) dt + sigma_i x_i dW_i with r = A 1, dt = 0.05:
          every order of the TME table weighs 10 .. 1000 times the parity bar (TME-1 vs TME-2: 1.5e-4 .. 4.5e-4 in NLL, TME-2 vs
@@ -9,22 +10,22 @@ a host form traced by mfs_amd.multi_dims.moments and an oracle form for oracle/t
   well2  coupled double well (cubic drift): blocks of unequal extent per variable; TME-1 has extent 4, TME-2 extent 7 and TME-3
          extent 10, which the device refuses; its Euler closure has a cubic mean.
 
-A likelihood is a list of factors (kind, component, y-column, parameter): 'gaussian' N(y; x, p^2), 'poisson' with rate
-softplus(p x), 'bernoulli' with probability logistic(p x - 1).  Measurements of a replicate come from its own seeded
+  cv2    the SDE of the bearing-only example; bearing_only_model() is the example itself, discretised exactly.
+
+A likelihood is a factor spec (nd_support.factor_pdfs).  Measurements of a replicate come from its own seeded
 Euler--Maruyama path, 10 sub-steps per dt."""
 import functools
 import math
 from typing import Callable, NamedTuple
 
 import numpy as np
+import scipy.linalg
 import sympy as sp
 
-from mfs_amd import stats, sym
 from mfs_amd.multi_dims import moments
-from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
-from oracle import models as om, multi_dims as omd, tme_sympy
+from oracle import tme_sympy
+from tests.nd_support import all_finite, factor_pdfs, host_disp, host_drift, initial, run_oracle, tables
 
-MODES = ('raw', 'central', 'scaled')
 OPERATOR = ('tme_1', 'tme_2', 'tme_3')
 NORMAL = ('tme_normal_2', 'tme_normal_3', 'euler')
 
@@ -92,33 +93,11 @@ MODELS['cv2'] = Model(0.01, lambda x: [1.0 * x[1], 0.0 * x[0]], lambda x: [[0., 
 MODELS.update({f'lv2_b{b}': lv2(A, s) for b, (A, s) in enumerate(LV_BATCH)})
 
 
-def host_drift(m):
-    return lambda x: np.array(m.drift(x), dtype=object)
-
-
-def host_disp(m):
-    return lambda x: np.array(m.disp(x), dtype=object)
-
-
-@functools.lru_cache(maxsize=None)
-def tables(N):
-    return generate_graded_lexico_multi_indices(2, 2 * N - 1), gram_and_hankel_indices_graded_lexico(N, 2)
-
-
-def initial(mi, mean, cov):
-    """Raw, central and scaled moments of N(mean, cov) on the table, with the mean and the scales."""
-    mean, cov = np.asarray(mean, dtype=float), np.asarray(cov, dtype=float)
-    rms = np.array([omd.raw_moments_mvn_kan(mean, cov, n) for n in mi])
-    cms = np.array([omd.raw_moments_mvn_kan(np.zeros(2), cov, n) for n in mi])
-    scale = np.sqrt(np.diag(cov))
-    return {'rms': rms, 'cms': cms, 'scms': cms / np.prod(scale ** mi, axis=-1), 'mean': mean, 'scale': scale}
-
-
 @functools.lru_cache(maxsize=None)
 def host_family(model, fam, N):
     """-> (the five device closures, their signature) of a transition family of MODELS[model]."""
     m = MODELS[model]
-    mi, _ = tables(N)
+    mi, _ = tables(2, N)
     if fam in OPERATOR:
         return moments.sde_cond_moments_tme(host_drift(m), host_disp(m), m.dt, int(fam[-1])), 'multi-index'
     if fam == 'euler':
@@ -131,7 +110,7 @@ def sympy_family(model, fam, N):
     """The oracle's closures (rms, cms, scms, mean, mean_var) of the same family by SymPy differentiation (oracle/tme_sympy.py);
     the mean-and-variance closure of a Normal family from tme_sympy.mean_and_cov_expr itself."""
     m = MODELS[model]
-    mi, _ = tables(N)
+    mi, _ = tables(2, N)
     if fam in OPERATOR and N < 4 and model in ('lv2', 'lin2', 'well2'):
         return sympy_family(model, fam, 4)      # 'multi-index' closures look a moment up by its multi-index: one table serves
     if fam in OPERATOR:
@@ -161,26 +140,6 @@ def oracle_family(model, fam, N):
     """The closures the oracle filter runs: SymPy tables for N <= 4; for N = 5..7 the host's NumPy closures, which
     tests/test_host_nd.py pins to SymPy at the multi-indices of N = 3, 4 (SymPy costs 10 .. 40 s per table at those orders)."""
     return sympy_family(model, fam, N) if N <= 4 else host_family(model, fam, N)[0]
-
-
-# ---- likelihoods ----
-def _factor(kind, y, xk, p, dev):
-    if kind == 'gaussian':
-        return stats.norm_pdf(y, xk, p) if dev else om.norm_pdf(y, xk, p)
-    if kind == 'poisson':
-        return stats.poisson_pmf(y, sym.log(1. + sym.exp(xk * p))) if dev else om.poisson_pmf(y, np.log1p(np.exp(xk * p)))
-    return (stats.bernoulli_pmf(y, 1. / (1. + sym.exp(-(xk * p) + 1.))) if dev else
-            om.bernoulli_pmf(y, 1. / (1. + np.exp(-(xk * p) + 1.))))
-
-
-def factor_pdfs(spec):
-    """-> (device pdf, oracle pdf): the product of the factors of `spec` in that order; y is indexed by column."""
-    def pdf(y, x):
-        return math.prod(_factor(kind, y[c], x[j], p, True) for kind, j, c, p in spec)
-
-    def opdf(y, x):
-        return float(math.prod(_factor(kind, y[c], x[j], p, False) for kind, j, c, p in spec))
-    return pdf, opdf
 
 
 def path(m, T, seed):
@@ -221,21 +180,28 @@ def measurements(model, B, T, seed, spec=None):
     return ys
 
 
-# ---- the oracle filter ----
-def run_oracle(mode, ofns, sig, opdf, ys, N, st, stable=False):
-    """oracle/multi_dims.py on one replicate (T, ny) -> dict(m, mean, scale, nell); raw mode reports its means as the
-    first-order raw moments."""
-    mi, inds = tables(N)
-    mp = (mi, inds)
-    if mode == 'raw':
-        m, nell = omd.moment_filter_nd_rms((ofns[0], sig), opdf, ys, mp, st['rms'], stable)
-        return {'m': m, 'nell': nell}
-    if mode == 'central':
-        m, mean, nell = omd.moment_filter_nd_cms((ofns[1], sig), ofns[3], opdf, ys, mp, st['cms'], st['mean'], stable)
-        return {'m': m, 'mean': mean, 'nell': nell}
-    m, mean, scale, nell = omd.moment_filter_nd_scms((ofns[2], sig), ofns[4], opdf, ys, mp, st['scms'], st['mean'], st['scale'],
-                                                     stable)
-    return {'m': m, 'mean': mean, 'scale': scale, 'nell': nell}
+def bearing_only_model():
+    """The reference's examples/2d_bearing_only.ipynb, cells 3-7: constant-velocity LTI model discretised exactly, Gaussian-sum
+    start, y_k = atan2(x_1, x_0) + sqrt(0.1) noise."""
+    dt, T, xi = 0.01, 100, 0.1
+    A = np.array([[0., 1.], [0., 0.]])
+    Bm = np.array([[0., 0.], [0., 1.]])
+    # discretise_lti_sde (mfs/utils.py, Van Loan / Axelsson & Gustafsson 2015): F = expm(A dt), Q = int_0^dt e^{As} B B^T e^{A^T s} ds
+    blk = scipy.linalg.expm(np.block([[A, Bm @ Bm.T], [np.zeros((2, 2)), -A.T]]) * dt)
+    F = blk[:2, :2]
+    Q = blk[:2, 2:] @ F.T
+    means0 = np.array([[1., 0.], [1., 1.]])
+    covs0 = np.array([np.eye(2), np.eye(2)]) * 0.01
+    weights0 = np.array([0.7, 0.3])
+    rng = np.random.default_rng(999)
+    comp = rng.choice(2, p=weights0)
+    x = means0[comp] + 0.1 * rng.standard_normal(2)
+    cq = np.linalg.cholesky(Q)
+    ys = np.empty(T)
+    for k in range(T):
+        x = F @ x + cq @ rng.standard_normal(2)
+        ys[k] = np.arctan2(x[1], x[0]) + math.sqrt(xi) * rng.standard_normal()
+    return dt, T, xi, F, Q, means0, covs0, weights0, ys
 
 
 def raw_means(rms):
@@ -243,19 +209,16 @@ def raw_means(rms):
     return np.stack([rms[..., 2], rms[..., 1]], axis=-1)
 
 
-def all_finite(r):
-    return bool(np.isfinite(r['nell']) and all(np.all(np.isfinite(r[k])) for k in ('m', 'mean', 'scale') if k in r))
-
-
 @functools.lru_cache(maxsize=None)
 def oracle_case(model, fam, N, mode, T, seed, b=0, spec=None, stable=False):
     """The oracle's run of replicate b of measurements(model, b + 1, T, seed, spec), from the model's initial law, cached."""
     m = MODELS[model]
-    mi, _ = tables(N)
+    mi, inds = tables(2, N)
     spec = m.spec if spec is None else spec
     ys = measurements(model, b + 1, T, seed, spec)[b]
     sig = 'multi-index' if fam in OPERATOR else 'index'
-    return run_oracle(mode, oracle_family(model, fam, N), sig, factor_pdfs(spec)[1], ys, N, initial(mi, m.mean0, m.cov0), stable)
+    return run_oracle(mode, oracle_family(model, fam, N), sig, factor_pdfs(spec)[1], ys, mi, inds,
+                      initial(mi, m.mean0, m.cov0), stable)
 
 
 def admissible(model, fam, N, mode, T, seed, b=0, spec=None):

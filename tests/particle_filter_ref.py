@@ -8,16 +8,35 @@ callable.  Besides the outputs the restatement returns the run's resampling marg
 (i + u_i) / n to its two neighbouring entries of the cumulative weights.  Resampling is discrete, so two implementations agree
 only while that margin exceeds the rounding of their prefix sums; the parity tests assert it.
 """
+import functools
 import math
 
 import numpy as np
 
+from mfs_amd import stats
+from mfs_amd.classical_filters_smoothers import gaussian_transition
 from mfs_amd.utils import GaussianSum1D
+from tests import brute_force_ref as R
 
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 W0, W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
 MASK = np.uint64(0xFFFFFFFF)
 S32 = np.uint64(32)
+
+
+# ---- the linear model of the shape sweeps: the OU model of tests/brute_force_ref.py through TME-2, a Gaussian measurement
+SWEEP_DT = 0.2
+
+
+def gauss_pdf(y, x):
+    return stats.norm_pdf(y, x, math.sqrt(R.OU_R))
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_model():
+    """-> (the transition, the initial law)."""
+    return (gaussian_transition(R.ou_drift, R.ou_dispersion, SWEEP_DT, 'tme-2'),
+            GaussianSum1D.new([0.], [R.OU_SIGMA ** 2], [1.]))
 
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1):

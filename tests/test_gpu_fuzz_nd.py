@@ -1,16 +1,15 @@
 """A seeded randomised sweep of the N-D entry points (prey--predator, d = 2) against the NumPy oracle: order N, transition
 family (operator tables of TME order 1-3, Normal closures of order 2-3, Euler), representation (raw / central / scaled),
 length and data seed drawn at random.  Every case: NLL and means to 1e-6, moments to 1e-6 with the floor of
-tests/test_gpu_parity_nd.py.  (The same sweep run off-line over 40 cases with the final kernels: no failure.)"""
+tests/nd_support.py.  (The same sweep run off-line over 40 cases with the final kernels: no failure.)"""
 import numpy as np
 import numpy.testing as npt
 import pytest
 
 from mfs_amd import synth
 from mfs_amd.multi_dims import filtering, moments, ss_models
-from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from oracle import multi_dims as omd, tme_sympy
-from .test_gpu_parity_nd import _assert_moments
+from tests.nd_support import assert_moments, tables
 
 pytestmark = pytest.mark.gpu
 
@@ -38,8 +37,7 @@ def test_random_nd_cases_match_oracle(seed):
         if mode == 'raw' and N > 3:
             mode = 'central'
         T, dseed = int(rng.integers(8, 25)), int(rng.integers(1, 10 ** 6))
-        mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-        inds = gram_and_hankel_indices_graded_lexico(N, 2)
+        mi, inds = tables(2, N)
         dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
         _, _, ogs, odrift, odisp, _, opmf = omd.prey_predator(mi)
         fns, sig, orms, ocms, omean = _tables(N, fam, mi, drift, disp, dt, odrift, odisp)
@@ -50,7 +48,7 @@ def test_random_nd_cases_match_oracle(seed):
             ref = omd.moment_filter_nd_cms((ocms, sig), omean, opmf, ys[1], (mi, inds), ogs.cms, ogs.mean)
             npt.assert_allclose(got[2][1], ref[2], rtol=1e-6, err_msg=tag)
             npt.assert_allclose(got[1][1], ref[1], rtol=1e-6, err_msg=tag)
-            _assert_moments(got[0][1], ref[0], mi, rtol=1e-6)
+            assert_moments(got[0][1], ref[0], mi, rtol=1e-6)
         elif mode == 'raw':
             got = filtering.moment_filter_nd_rms((fns[0], sig), pmf, ys, (mi, inds), gs.rms)
             ref = omd.moment_filter_nd_rms((orms, sig), opmf, ys[1], (mi, inds), ogs.rms)

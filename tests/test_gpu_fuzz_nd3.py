@@ -3,15 +3,15 @@ N in {2, 3, 4}, transition family (operator TME-1 / TME-2 tables, TME-normal-2 /
 (raw / central / scaled), stable off / on, model (Lorenz-63, 3-species Lotka--Volterra, 3-D OU), length and data seed drawn
 at random; T is capped by N (12 / 6 / 3 at N = 2 / 3 / 4) to bound the oracle's CPU time.  Every case: replicate 1 of a
 batch of 2 against oracle/multi_dims.py at 1e-6 with the natural-magnitude floor, and the NaN criterion of
-tests/test_gpu_fuzz_1d.py (compare() of tests/test_gpu_nd3_envelope.py).  Raw moments about the origin of Lorenz-63 at
+tests/test_gpu_fuzz_1d.py (compare() of tests/nd_support.py).  Raw moments about the origin of Lorenz-63 at
 N = 4 (a law of sd 0.1 centred at (0.1, 0.1, 2.4)) have a Gram matrix singular to working precision from the start; that
 combination runs in central mode, as tests/test_gpu_nd3.py does.  (The same sweep run off-line over 180 cases, seeds 1-30,
 with the final kernels and criterion: no failure.)"""
 import numpy as np
 import pytest
 
-from .test_gpu_nd3 import _tables
-from .test_gpu_nd3_envelope import MODELS, MODES, compare, device, family, initial, oracle
+from tests.nd3_models import MODELS, family
+from tests.nd_support import MODES, compare, initial, run_device, run_oracle, tables
 
 pytestmark = pytest.mark.gpu
 
@@ -37,13 +37,13 @@ def draw_cases(seed, n=6):
 
 
 def run_case(N, fam, mode, stable, model, T, dseed):
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     m = MODELS[model]
     fns, sig, ofns = family(model, fam, N)
     st = initial(mi, m.mean0, m.cov0)
     ys = m.ys(2, T, dseed)
-    got = device(mode, fns, sig, m.pdf, ys, mi, inds, st, stable)
-    ref = oracle(mode, ofns, sig, m.opdf, ys[1], mi, inds, st, stable)
+    got = run_device(mode, fns, sig, m.pdf, ys, mi, inds, st, stable)
+    ref = run_oracle(mode, ofns, sig, m.opdf, ys[1], mi, inds, st, stable, completed=True)
     compare(got, 1, ref, mi, inds, f'N={N} {fam} {mode} stable={stable} {model} T={T} seed={dseed}')
 
 

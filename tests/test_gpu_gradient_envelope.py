@@ -20,7 +20,6 @@ from tests.plan_api import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
-REFERENCE_CASES = G.EVERY_INSTANTIATION + G.MATRIX + G.BATCHING + G.GEOMETRY + G.LONG
 MFS_EINVAL, MFS_EUNSUPPORTED = -1, -2
 
 

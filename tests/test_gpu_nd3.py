@@ -10,108 +10,42 @@ import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import stats
+from mfs_amd import stats, sym
 from mfs_amd.multi_dims import filtering, moments
-from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from oracle import models as om, multi_dims as omd, one_dim as o1, tme_sympy
+from tests.nd3_models import C0, DT, M0, MODELS, SD, lorenz_disp, lorenz_drift, lorenz_opdf, lorenz_pdf, lorenz_ys
+from tests.nd_support import assert_moments, host_disp, host_drift, initial, tables
 from tests.plan_api import run_plan_nd
 
 pytestmark = pytest.mark.gpu
 
-DT = 0.01
-SIG, RHO, BETA = 10., 28., 8. / 3.
-M0 = np.array([0.1, 0.1, 2.4])
-C0 = np.diag([0.01, 0.01, 0.01])
-SD = 0.5
-
-
-def _moment_err(got, ref, mi):
-    """(T, z) relative error per moment with the natural magnitude prod_k sigma_k^{n_k} as the floor of the denominator:
-    first-order central moments and odd moments of near-symmetric laws are rounding noise around zero."""
-    got, ref, mi = np.asarray(got), np.asarray(ref), np.asarray(mi)
-    d = mi.shape[1]
-    second = [int(np.where((mi == 2 * np.eye(d, dtype=int)[k]).all(axis=1))[0][0]) for k in range(d)]
-    m2 = np.stack([np.abs(ref[:, second[k]]) for k in range(d)], axis=-1)          # (T, d): E[(x_k - c_k)^2] or E[x_k^2]
-    natural = np.prod(np.sqrt(m2)[:, None, :] ** mi[None, :, :], axis=-1)          # (T, z)
-    scale = np.maximum(np.abs(ref), natural * 1e-2 + 1e-300)
-    return np.abs(got - ref) / scale
-
-
-def _assert_moments(got, ref, mi, rtol):
-    """_moment_err <= rtol wherever the reference is finite, and the same NaN pattern."""
-    assert np.array_equal(np.isnan(np.asarray(got)), np.isnan(np.asarray(ref)))
-    err = _moment_err(got, ref, mi)
-    assert np.nanmax(err) <= rtol, f'max scaled error {np.nanmax(err):.3e} > {rtol}'
-
-
-def _lorenz(x):
-    return np.array([SIG * (x[1] - x[0]), x[0] * (RHO - 10. * x[2]) - x[1], 10. * x[0] * x[1] - BETA * x[2]], dtype=object)
-
-
-def _lorenz_sympy(x):
-    return [SIG * (x[1] - x[0]), x[0] * (RHO - 10. * x[2]) - x[1], 10. * x[0] * x[1] - BETA * x[2]]
-
-
-def _disp(x):
-    return np.diag([0.1, 0.1, 0.1]).astype(object)
-
-
-def _disp_sympy(x):
-    return [[0.1, 0, 0], [0, 0.1, 0], [0, 0, 0.1]]
-
-
-def _pdf(y, x):
-    return stats.norm_pdf(y, x[0], SD)
-
-
-def _opdf(y, x):
-    return float(om.norm_pdf(y, x[0], SD))
-
-
-def _tables(N):
-    return generate_graded_lexico_multi_indices(3, 2 * N - 1), gram_and_hankel_indices_graded_lexico(N, 3)
+_lorenz, _disp = host_drift(MODELS['lorenz']), host_disp(MODELS['lorenz'])      # the forms the host traces
 
 
 def _init(mi, mean=M0, cov=C0):
-    cms = np.array([omd.raw_moments_mvn_kan(np.zeros(3), cov, n) for n in mi])
-    rms = np.array([omd.raw_moments_mvn_kan(mean, cov, n) for n in mi])
-    return cms, rms
-
-
-def _lorenz_ys(B, T, seed, sd=SD):
-    rng = np.random.default_rng(seed)
-    x = M0 + 0.1 * rng.standard_normal((B, 3))
-    sub = 10
-    h = DT / sub
-    ys = np.empty((B, T))
-    for t in range(T):
-        for _ in range(sub):
-            a = np.stack([SIG * (x[:, 1] - x[:, 0]), x[:, 0] * (RHO - 10. * x[:, 2]) - x[:, 1],
-                          10. * x[:, 0] * x[:, 1] - BETA * x[:, 2]], axis=-1)
-            x = x + a * h + 0.1 * math.sqrt(h) * rng.standard_normal((B, 3))
-        ys[:, t] = x[:, 0] + sd * rng.standard_normal(B)
-    return ys
+    st = initial(mi, mean, cov)
+    return st['cms'], st['rms']
 
 
 @pytest.mark.parametrize('N,T', [(2, 30), (3, 10), (4, 3)])
 def test_lorenz_operator_central_and_raw(N, T):
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     cms0, rms0 = _init(mi)
     fns = moments.sde_cond_moments_tme(_lorenz, _disp, DT, 2, d=3)
-    ofns = tme_sympy.sde_cond_moments_tme_nd(_lorenz_sympy, _disp_sympy, 3, DT, 2, mi)
+    ofns = tme_sympy.sde_cond_moments_tme_nd(lorenz_drift, lorenz_disp, 3, DT, 2, mi)
     B = 2
-    ys = _lorenz_ys(B, T, seed=N)
-    cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), cms0, M0)
+    ys = lorenz_ys(B, T, seed=N)
+    cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), cms0, M0)
     assert cmss.shape == (B, T, mi.shape[0]) and means.shape == (B, T, 3) and nell.shape == (B,)
-    rc = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], _opdf, ys[0], (mi, inds), cms0, M0)
+    rc = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], lorenz_opdf, ys[0], (mi, inds), cms0, M0)
     npt.assert_allclose(nell[0], rc[2], rtol=1e-6)
     npt.assert_allclose(means[0], rc[1], rtol=1e-6)
-    _assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
+    assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
     if N <= 3:
-        rmss, nell_r = filtering.moment_filter_nd_rms((fns[0], 'multi-index'), _pdf, ys, (mi, inds), rms0)
-        rr = omd.moment_filter_nd_rms((ofns[0], 'multi-index'), _opdf, ys[0], (mi, inds), rms0)
+        rmss, nell_r = filtering.moment_filter_nd_rms((fns[0], 'multi-index'), lorenz_pdf, ys, (mi, inds), rms0)
+        rr = omd.moment_filter_nd_rms((ofns[0], 'multi-index'), lorenz_opdf, ys[0], (mi, inds), rms0)
         npt.assert_allclose(nell_r[0], rr[1], rtol=1e-6)
-        _assert_moments(rmss[0], rr[0], mi, rtol=1e-6)
+        assert_moments(rmss[0], rr[0], mi, rtol=1e-6)
         # raw and central filters agree on the device (reference tests/test_filtering.py:229-242)
         npt.assert_allclose(means[:, :, 0], rmss[:, :, 3], rtol=1e-6)
         npt.assert_allclose(nell, nell_r, rtol=1e-6)
@@ -119,27 +53,27 @@ def test_lorenz_operator_central_and_raw(N, T):
 
 @pytest.mark.parametrize('N,T', [(2, 20), (3, 6)])
 def test_lorenz_operator_scaled(N, T):
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     cms0, _ = _init(mi)
     scale0 = np.sqrt(np.diag(C0))
     scms0 = cms0 / np.prod(scale0 ** mi, axis=-1)
     fns = moments.sde_cond_moments_tme(_lorenz, _disp, DT, 2, d=3)
-    _, ocms, _, omean_var = tme_sympy.sde_cond_moments_tme_nd(_lorenz_sympy, _disp_sympy, 3, DT, 2, mi)
+    _, ocms, _, omean_var = tme_sympy.sde_cond_moments_tme_nd(lorenz_drift, lorenz_disp, 3, DT, 2, mi)
 
     def oscms(x, idx, mean, scale):
         return ocms(x, idx, mean) / np.prod(np.asarray(scale) ** np.asarray(idx), axis=-1)
 
-    ys = _lorenz_ys(2, T, seed=20 + N)
-    scmss, means, scales, nell = filtering.moment_filter_nd_scms((fns[2], 'multi-index'), fns[4], _pdf, ys, (mi, inds),
+    ys = lorenz_ys(2, T, seed=20 + N)
+    scmss, means, scales, nell = filtering.moment_filter_nd_scms((fns[2], 'multi-index'), fns[4], lorenz_pdf, ys, (mi, inds),
                                                                  scms0, M0, scale0)
     assert scales.shape == (2, T, 3)
-    rs = omd.moment_filter_nd_scms((oscms, 'multi-index'), omean_var, _opdf, ys[0], (mi, inds), scms0, M0, scale0)
+    rs = omd.moment_filter_nd_scms((oscms, 'multi-index'), omean_var, lorenz_opdf, ys[0], (mi, inds), scms0, M0, scale0)
     npt.assert_allclose(nell[0], rs[3], rtol=1e-6)
     npt.assert_allclose(means[0], rs[1], rtol=1e-6)
     npt.assert_allclose(scales[0], rs[2], rtol=1e-6)
-    _assert_moments(scmss[0], rs[0], mi, rtol=1e-6)
+    assert_moments(scmss[0], rs[0], mi, rtol=1e-6)
     # scaled and central filters agree (reference tests/test_filtering.py:168-242)
-    _, cmeans, cnell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), cms0, M0)
+    _, cmeans, cnell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), cms0, M0)
     npt.assert_allclose(means, cmeans, rtol=1e-6)
     npt.assert_allclose(nell, cnell, rtol=1e-6)
 
@@ -149,26 +83,26 @@ def test_lorenz_operator_scaled(N, T):
 def test_lorenz_normal_closures(N, T, order, kan):
     """'index' Normal closures against the oracle filter, with the oracle's per-node Kan closure (N = 2) or with the host's
     vectorised d = 3 closure, which tests/test_host_nd3.py pins to Kan."""
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     cms0, rms0 = _init(mi)
     if order == 'euler':
         fns = moments.sde_cond_moments_euler_maruyama(_lorenz, _disp, DT, mi)
     else:
         fns = moments.sde_cond_moments_tme_normal(_lorenz, _disp, DT, order, mi)
-    orms, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(_lorenz_sympy, _disp_sympy, 3, DT, order, mi)
+    orms, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(lorenz_drift, lorenz_disp, 3, DT, order, mi)
     if not kan:
         orms, ocms = fns[0], fns[1]
-    ys = _lorenz_ys(2, T, seed=30 + N)
-    cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'index'), fns[3], _pdf, ys, (mi, inds), cms0, M0)
-    rc = omd.moment_filter_nd_cms((ocms, 'index'), omean, _opdf, ys[0], (mi, inds), cms0, M0)
+    ys = lorenz_ys(2, T, seed=30 + N)
+    cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'index'), fns[3], lorenz_pdf, ys, (mi, inds), cms0, M0)
+    rc = omd.moment_filter_nd_cms((ocms, 'index'), omean, lorenz_opdf, ys[0], (mi, inds), cms0, M0)
     npt.assert_allclose(nell[0], rc[2], rtol=1e-6)
     npt.assert_allclose(means[0], rc[1], rtol=1e-6)
-    _assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
+    assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
     if N == 2:
-        rmss, nell_r = filtering.moment_filter_nd_rms((fns[0], 'index'), _pdf, ys, (mi, inds), rms0)
-        rr = omd.moment_filter_nd_rms((orms, 'index'), _opdf, ys[0], (mi, inds), rms0)
+        rmss, nell_r = filtering.moment_filter_nd_rms((fns[0], 'index'), lorenz_pdf, ys, (mi, inds), rms0)
+        rr = omd.moment_filter_nd_rms((orms, 'index'), lorenz_opdf, ys[0], (mi, inds), rms0)
         npt.assert_allclose(nell_r[0], rr[1], rtol=1e-6)
-        _assert_moments(rmss[0], rr[0], mi, rtol=1e-6)
+        assert_moments(rmss[0], rr[0], mi, rtol=1e-6)
 
 
 def _linear_model():
@@ -182,7 +116,7 @@ def _linear_model():
 def test_linear_gaussian_three_factors(mode):
     """A 3-D linear-Gaussian model observed in every component (ny = 3), the reference's math.prod(norm.pdf(y, x, sd))."""
     N, T = 3, 12
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     F, Q = _linear_model()
     fns = moments.cond_moments_linear_gaussian(F, Q, mi)
     mean0 = np.array([0.5, -0.3, 0.2])
@@ -202,7 +136,7 @@ def test_linear_gaussian_three_factors(mode):
         rc = omd.moment_filter_nd_cms((fns[1], 'index'), fns[3], opdf, ys[0], (mi, inds), cms0, mean0)
         npt.assert_allclose(nell[0], rc[2], rtol=1e-6)
         npt.assert_allclose(means[0], rc[1], rtol=1e-6)
-        _assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
+        assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
     else:
         scale0 = np.sqrt(np.diag(cov0))
         scms0 = cms0 / np.prod(scale0 ** mi, axis=-1)
@@ -212,14 +146,14 @@ def test_linear_gaussian_three_factors(mode):
         npt.assert_allclose(nell[0], rs[3], rtol=1e-6)
         npt.assert_allclose(means[0], rs[1], rtol=1e-6)
         npt.assert_allclose(scales[0], rs[2], rtol=1e-6)
-        _assert_moments(scmss[0], rs[0], mi, rtol=1e-6)
+        assert_moments(scmss[0], rs[0], mi, rtol=1e-6)
 
 
 @pytest.mark.parametrize('mode', ['raw', 'central'])
 def test_ou_operator_poisson_factor(mode):
     """3-D OU with operator TME-2 tables and a Poisson-softplus factor on x_1."""
     N, T = 2, 15
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     A = np.array([[-1., 0.3, 0.], [0., -0.8, 0.4], [0.2, 0., -0.6]])
 
     def drift(x):
@@ -252,18 +186,17 @@ def test_ou_operator_poisson_factor(mode):
         rmss, nell = filtering.moment_filter_nd_rms((fns[0], 'multi-index'), pdf, ys, (mi, inds), rms0)
         rr = omd.moment_filter_nd_rms((ofns[0], 'multi-index'), opdf, ys[0], (mi, inds), rms0)
         npt.assert_allclose(nell[0], rr[1], rtol=1e-6)
-        _assert_moments(rmss[0], rr[0], mi, rtol=1e-6)
+        assert_moments(rmss[0], rr[0], mi, rtol=1e-6)
     else:
         cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], pdf, ys, (mi, inds), cms0,
                                                            mean0)
         rc = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], opdf, ys[0], (mi, inds), cms0, mean0)
         npt.assert_allclose(nell[0], rc[2], rtol=1e-6)
         npt.assert_allclose(means[0], rc[1], rtol=1e-6)
-        _assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
+        assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
 
 
 def sym_softplus(x):
-    from mfs_amd import sym
     return sym.log(1. + sym.exp(x))
 
 
@@ -271,26 +204,26 @@ def test_stable_filter_and_an_indefinite_start():
     """stable=True (the LDL^T completion, mfs/utils.py:495-538): on a well-posed start the completed factor is the Cholesky
     factor; from initial moments whose Gram matrix is indefinite the first rule takes the completion, as the oracle's does."""
     N, T = 3, 8
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     cms0, _ = _init(mi)
     fns = moments.sde_cond_moments_tme(_lorenz, _disp, DT, 2, d=3)
-    ofns = tme_sympy.sde_cond_moments_tme_nd(_lorenz_sympy, _disp_sympy, 3, DT, 2, mi)
-    ys = _lorenz_ys(2, T, seed=41)
-    cs, ms, ns = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), cms0, M0, stable=True)
-    cp, mp, np_ = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), cms0, M0)
+    ofns = tme_sympy.sde_cond_moments_tme_nd(lorenz_drift, lorenz_disp, 3, DT, 2, mi)
+    ys = lorenz_ys(2, T, seed=41)
+    cs, ms, ns = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), cms0, M0, stable=True)
+    cp, mp, np_ = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), cms0, M0)
     npt.assert_allclose(ns, np_, rtol=1e-9)
     npt.assert_allclose(ms, mp, rtol=1e-9)
-    r = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], _opdf, ys[0], (mi, inds), cms0, M0, stable=True)
+    r = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], lorenz_opdf, ys[0], (mi, inds), cms0, M0, stable=True)
     npt.assert_allclose(ns[0], r[2], rtol=1e-6)
-    _assert_moments(cs[0], r[0], mi, rtol=1e-6)
+    assert_moments(cs[0], r[0], mi, rtol=1e-6)
     # E[x0^4] < E[x0^2]^2: no law has these moments, the LDL^T of the Gram matrix has a negative pivot
     bad = cms0.copy()
     bad[int(np.where((mi == [4, 0, 0]).all(axis=1))[0][0])] *= 0.2
     _, dpiv = o1.ldl(bad[inds[0]])
     assert dpiv.min() < 0.
-    cb, mb, nb, fnb = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), bad, M0,
+    cb, mb, nb, fnb = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), bad, M0,
                                                      stable=True, return_first_nan=True)
-    rb = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], _opdf, ys[0], (mi, inds), bad, M0, stable=True)
+    rb = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], lorenz_opdf, ys[0], (mi, inds), bad, M0, stable=True)
     # the completed rule carries a node far out with a negligible weight; the following Gram matrices are singular to
     # rounding, and when a later pivot lands at -1e-17, +1e-17 or exactly 0 is rounding luck on either side (as at d = 1, 2).
     # The first step, which takes the completion, is compared: its K_k have norms ~ 1 / eps^2, and both eigensolvers are
@@ -298,34 +231,34 @@ def test_stable_filter_and_an_indefinite_start():
     assert np.all(np.isfinite(rb[0][0])) and np.all(np.isfinite(cb[0, 0]))
     npt.assert_allclose(mb[0, 0], rb[1][0], rtol=2e-3)
     # without the completion the same start poisons at once, as the reference's Cholesky does
-    _, _, nell_c, fn_c = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), bad, M0,
+    _, _, nell_c, fn_c = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), bad, M0,
                                                         return_first_nan=True)
     assert np.all(fn_c == 0) and np.all(np.isnan(nell_c))
 
 
 def test_batch_position_poisoning_and_per_replicate_tables():
     N, T, B = 3, 12, 4
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     cms0, _ = _init(mi)
     fns = moments.sde_cond_moments_tme(_lorenz, _disp, DT, 2, d=3)
-    ys = _lorenz_ys(B, T, seed=7)
-    mB, meansB, nellB, fnB = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), cms0, M0,
+    ys = lorenz_ys(B, T, seed=7)
+    mB, meansB, nellB, fnB = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), cms0, M0,
                                                             return_first_nan=True)
     assert np.all(fnB == -1)
     # a replicate's bits do not depend on where it sits in the batch
     for b in (0, 2):
-        m1, means1, nell1 = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys[b], (mi, inds), cms0, M0)
+        m1, means1, nell1 = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys[b], (mi, inds), cms0, M0)
         npt.assert_array_equal(m1, mB[b])
         npt.assert_array_equal(means1, meansB[b])
         assert nell1 == nellB[b]
     rev = ys[::-1].copy()
-    mR, _, nellR = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, rev, (mi, inds), cms0, M0)
+    mR, _, nellR = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, rev, (mi, inds), cms0, M0)
     npt.assert_array_equal(mR[::-1], mB)
     npt.assert_array_equal(nellR[::-1], nellB)
     # NaN poisoning is per replicate: the others keep their bits
     cms_b = np.tile(cms0, (B, 1))
     cms_b[1, int(np.where((mi == [2, 0, 0]).all(axis=1))[0][0])] = -1.
-    m, means, nell, fn = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys, (mi, inds), cms_b,
+    m, means, nell, fn = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys, (mi, inds), cms_b,
                                                         np.tile(M0, (B, 1)), return_first_nan=True)
     assert fn[1] == 0 and np.isnan(nell[1]) and np.all(np.isnan(m[1])) and np.all(np.isnan(means[1]))
     for b in (0, 2, 3):
@@ -336,9 +269,9 @@ def test_batch_position_poisoning_and_per_replicate_tables():
     per = [moments.sde_cond_moments_tme(_lorenz, (lambda s: (lambda x: np.diag([s, s, s]).astype(object)))(s), DT, 2, d=3)
            for s in sigmas]
     bfns = moments.batch_closures(per)
-    mP, _, nellP = filtering.moment_filter_nd_cms((bfns[1], 'multi-index'), bfns[3], _pdf, ys, (mi, inds), cms0, M0)
+    mP, _, nellP = filtering.moment_filter_nd_cms((bfns[1], 'multi-index'), bfns[3], lorenz_pdf, ys, (mi, inds), cms0, M0)
     for b in (0, 3):
-        m1, _, nell1 = filtering.moment_filter_nd_cms((per[b][1], 'multi-index'), per[b][3], _pdf, ys[b], (mi, inds), cms0, M0)
+        m1, _, nell1 = filtering.moment_filter_nd_cms((per[b][1], 'multi-index'), per[b][3], lorenz_pdf, ys[b], (mi, inds), cms0, M0)
         npt.assert_allclose(mP[b], m1, rtol=1e-12, atol=1e-15)
         npt.assert_allclose(nellP[b], nell1, rtol=1e-12)
     assert abs(nellP[0] - nellP[3]) > 1e-6
@@ -346,12 +279,12 @@ def test_batch_position_poisoning_and_per_replicate_tables():
 
 def test_plan_is_bit_identical_to_the_host_entry_point():
     N, T, B = 2, 20, 3
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     cms0, _ = _init(mi)
     fns = moments.sde_cond_moments_tme(_lorenz, _disp, DT, 2, d=3)
-    ys = np.ascontiguousarray(_lorenz_ys(B, T, seed=11)[..., None])
-    cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], _pdf, ys[..., 0], (mi, inds), cms0, M0)
-    model, keep = filtering._model_struct3(fns[1].tables, filtering._trace_likelihood(_pdf, 3), B)
+    ys = np.ascontiguousarray(lorenz_ys(B, T, seed=11)[..., None])
+    cmss, means, nell = filtering.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], lorenz_pdf, ys[..., 0], (mi, inds), cms0, M0)
+    model, keep = filtering._model_struct3(fns[1].tables, filtering._trace_likelihood(lorenz_pdf, 3), B)
     # the second run is NLL only: NULL outputs are allowed
     geo, (full, nll_only) = run_plan_nd(model, N, T, B, mi, inds, m0=cms0, mean0=M0, ys=ys,
                                         outputs=(('moments', 'means', 'nell'), ('nell',)))

@@ -9,10 +9,8 @@ Oracles: oracle/multi_dims.py with the SymPy TME tables of oracle/tme_sympy.py f
 closures the host's vectorised Stein closure, which tests/test_host_nd3.py pins to the oracle's per-node Kan moments (one
 case here runs the Kan closure itself).  The bar is that of tests/test_gpu_nd3.py: 1e-6 relative on NLL, means, scales and
 moments, with the natural-magnitude floor.  Where a test uses another bound, it says where the bound comes from."""
-import functools
 import math
 import os
-from typing import Callable, NamedTuple
 
 import numpy as np
 import numpy.testing as npt
@@ -23,236 +21,14 @@ from mfs_amd.multi_dims import filtering, moments
 from mfs_amd.multi_dims.moments import marginalise_moments
 from mfs_amd.one_dim import filtering as f1, moments as m1
 from oracle import models as om, multi_dims as omd, one_dim as o1, tme_sympy
-from .plan_api import assert_same_bits
-from .test_gpu_nd3 import (C0, DT, M0, _assert_moments, _disp, _disp_sympy, _init, _lorenz, _lorenz_sympy, _lorenz_ys,
-                           _moment_err, _opdf, _pdf, _tables)
+from tests.nd3_models import (C0, DT, LV_A, LV_C0, LV_DT, LV_M0, LV_SD, LV_SIG, M0, MODELS, family, lorenz_disp, lorenz_drift,
+                              lv_model, lv_path, lv_pdf, lv_ys)
+from tests.nd_support import (KIND_NAMES, MODES, MOMENTS_OF, RTOL, assert_state, compare, factor_pdfs, first_bad, host_disp,
+                              host_drift, initial, moment_err, run_device, run_oracle, same_bits, stack_initial, tables)
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-6
-MODES = ('raw', 'central', 'scaled')
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'filter_nd3.npz')
-
-# ---- 3-species Lotka--Volterra (competition, equilibrium (1, 1, 1)): dx_i = x_i (r_i - sum_j A_ij x_j) dt + sigma_i x_i dW_i
-LV_A = np.array([[0.8, 0.3, 0.1], [0.2, 0.6, 0.1], [0.4, 0.2, 0.9]])
-LV_SIG = np.array([0.1, 0.15, 0.2])
-LV_DT = 0.05
-LV_M0 = np.array([1.0, 0.9, 1.1])
-LV_C0 = np.array([[0.02, 0.005, 0.], [0.005, 0.03, -0.004], [0., -0.004, 0.025]])
-LV_SD = 0.2
-
-
-def lv_drift(A, x):
-    """r = A 1, so that (1, 1, 1) is the equilibrium; x is a list / object array of the three state variables."""
-    r = A.sum(axis=1)
-    return [x[i] * (float(r[i]) - sum(float(A[i, j]) * x[j] for j in range(3))) for i in range(3)]
-
-
-def lv_disp(sig, x):
-    return [[float(sig[i]) * x[i] if i == j else 0. for j in range(3)] for i in range(3)]
-
-
-def lv_path(B, T, seed, A=LV_A, sig=LV_SIG):
-    """Euler--Maruyama states on 10 sub-steps per dt, (B, T, 3), and the generator for the measurement noise."""
-    rng = np.random.default_rng(seed)
-    r = A.sum(axis=1)
-    x = LV_M0 + 0.1 * rng.standard_normal((B, 3))
-    h = LV_DT / 10
-    xs = np.empty((B, T, 3))
-    for t in range(T):
-        for _ in range(10):
-            x = np.abs(x + x * (r - x @ A.T) * h + sig * x * math.sqrt(h) * rng.standard_normal((B, 3)))
-        xs[:, t] = x
-    return xs, rng
-
-
-def _lv_pdf(y, x):
-    return stats.norm_pdf(y[0], x[0], LV_SD) * stats.poisson_pmf(y[1], sym.log(1. + sym.exp(x[2])))
-
-
-def _lv_opdf(y, x):
-    return float(om.norm_pdf(y[0], x[0], LV_SD) * om.poisson_pmf(y[1], np.log1p(np.exp(x[2]))))
-
-
-def lv_ys(B, T, seed, A=LV_A, sig=LV_SIG):
-    """(B, T, 2): x_0 + N(0, LV_SD^2) and Poisson(softplus(x_2)) counts."""
-    xs, rng = lv_path(B, T, seed, A, sig)
-    return np.stack([xs[..., 0] + LV_SD * rng.standard_normal((B, T)),
-                     rng.poisson(np.log1p(np.exp(xs[..., 2]))).astype(np.float64)], axis=-1)
-
-
-# ---- 3-D OU with a Poisson factor on x_1 (tests/test_gpu_nd3.py) ----
-OU_A = np.array([[-1., 0.3, 0.], [0., -0.8, 0.4], [0.2, 0., -0.6]])
-
-
-def _ou_drift(x):
-    return [sum(float(OU_A[i, j]) * x[j] for j in range(3)) for i in range(3)]
-
-
-def _ou_disp(x):
-    return [[0.3, 0., 0.], [0., 0.3, 0.], [0., 0., 0.3]]
-
-
-class Model(NamedTuple):
-    dt: float
-    drift: Callable      # host tracing: object array of polynomial variables
-    disp: Callable
-    odrift: Callable     # oracle: list of SymPy symbols
-    odisp: Callable
-    mean0: np.ndarray
-    cov0: np.ndarray
-    pdf: Callable
-    opdf: Callable
-    ys: Callable         # (B, T, seed) -> measurements
-
-
-def lv_model(A=LV_A, sig=LV_SIG):
-    return Model(LV_DT, lambda x: np.array(lv_drift(A, x), dtype=object), lambda x: np.array(lv_disp(sig, x), dtype=object),
-                 lambda x: lv_drift(A, x), lambda x: lv_disp(sig, x), LV_M0, LV_C0, _lv_pdf, _lv_opdf,
-                 lambda B, T, seed: lv_ys(B, T, seed, A, sig))
-
-
-MODELS = {
-    'lorenz': Model(DT, _lorenz, _disp, _lorenz_sympy, _disp_sympy, M0, C0, _pdf, _opdf,
-                    lambda B, T, seed: _lorenz_ys(B, T, seed)),
-    'lv': lv_model(),
-    'ou': Model(0.1, lambda x: np.array(_ou_drift(x), dtype=object), lambda x: np.array(_ou_disp(x), dtype=object),
-                _ou_drift, _ou_disp, np.array([1., 1.5, 0.5]), np.diag([0.1, 0.1, 0.1]),
-                lambda y, x: stats.poisson_pmf(y, sym.log(1. + sym.exp(x[1]))),
-                lambda y, x: float(om.poisson_pmf(y, np.log1p(np.exp(x[1])))),
-                lambda B, T, seed: np.random.default_rng(seed).poisson(1.5, size=(B, T)).astype(np.float64)),
-}
-
-
-@functools.lru_cache(maxsize=None)
-def family(model, fam, N):
-    """-> (device closures, signature, oracle closures (rms, cms, scms, mean, mean_var)) of a transition family."""
-    m = MODELS[model]
-    mi, _ = _tables(N)
-    if fam in ('tme_1', 'tme_2'):
-        order = int(fam[-1])
-        fns = moments.sde_cond_moments_tme(m.drift, m.disp, m.dt, order, d=3)
-        orms, ocms, omean, omean_var = tme_sympy.sde_cond_moments_tme_nd(m.odrift, m.odisp, 3, m.dt, order, mi)
-
-        def oscms(x, idx, mean, scale):
-            return ocms(x, idx, mean) / np.prod(np.asarray(scale) ** np.asarray(idx), axis=-1)
-        return fns, 'multi-index', (orms, ocms, oscms, omean, omean_var)
-    if fam == 'euler':
-        fns = moments.sde_cond_moments_euler_maruyama(m.drift, m.disp, m.dt, mi)
-    else:
-        fns = moments.sde_cond_moments_tme_normal(m.drift, m.disp, m.dt, int(fam[-1]), mi)
-    return fns, 'index', fns
-
-
-def initial(mi, mean, cov):
-    """Raw, central and scaled moments of N(mean, cov) on the table, with the mean and the scales."""
-    cms, rms = _init(mi, mean, cov)
-    scale = np.sqrt(np.diag(cov))
-    return {'rms': rms, 'cms': cms, 'scms': cms / np.prod(scale ** mi, axis=-1), 'mean': np.asarray(mean, dtype=float),
-            'scale': scale}
-
-
-def stack_initial(states):
-    return {k: np.stack([s[k] for s in states]) for k in states[0]}
-
-
-def device(mode, fns, sig, pdf, ys, mi, inds, st, stable=False):
-    """The device filter of one mode on batched measurements -> dict(m, mean, scale, nell, fn)."""
-    mp = (mi, inds)
-    if mode == 'raw':
-        m, nell, fn = filtering.moment_filter_nd_rms((fns[0], sig), pdf, ys, mp, st['rms'], stable, return_first_nan=True)
-        return {'m': m, 'nell': nell, 'fn': fn}
-    if mode == 'central':
-        m, mean, nell, fn = filtering.moment_filter_nd_cms((fns[1], sig), fns[3], pdf, ys, mp, st['cms'], st['mean'], stable,
-                                                           return_first_nan=True)
-        return {'m': m, 'mean': mean, 'nell': nell, 'fn': fn}
-    m, mean, scale, nell, fn = filtering.moment_filter_nd_scms((fns[2], sig), fns[4], pdf, ys, mp, st['scms'], st['mean'],
-                                                               st['scale'], stable, return_first_nan=True)
-    return {'m': m, 'mean': mean, 'scale': scale, 'nell': nell, 'fn': fn}
-
-
-def oracle(mode, ofns, sig, opdf, ys, mi, inds, st, stable=False):
-    """oracle/multi_dims.py on one replicate -> dict(m, mean, scale, nell, completed); `completed` is the first step one of
-    whose two rules took the LDL^T completion (a pivot not > 0, stable=True only), -1 if none."""
-    mp = (mi, inds)
-    calls, first = [0], [-1]
-    ldl0 = o1.ldl
-
-    def spy(mat):
-        l, d = ldl0(mat)
-        if first[0] < 0 and not np.all(d > 0):
-            first[0] = calls[0]
-        calls[0] += 1
-        return l, d
-    o1.ldl = spy
-    try:
-        if mode == 'raw':
-            m, nell = omd.moment_filter_nd_rms((ofns[0], sig), opdf, ys, mp, st['rms'], stable)
-            out = {'m': m, 'nell': nell}
-        elif mode == 'central':
-            m, mean, nell = omd.moment_filter_nd_cms((ofns[1], sig), ofns[3], opdf, ys, mp, st['cms'], st['mean'], stable)
-            out = {'m': m, 'mean': mean, 'nell': nell}
-        else:
-            m, mean, scale, nell = omd.moment_filter_nd_scms((ofns[2], sig), ofns[4], opdf, ys, mp, st['scms'], st['mean'],
-                                                             st['scale'], stable)
-            out = {'m': m, 'mean': mean, 'scale': scale, 'nell': nell}
-    finally:
-        o1.ldl = ldl0
-    out['completed'] = first[0] // 2 if first[0] >= 0 else -1
-    return out
-
-
-def first_bad(r):
-    bad = ~np.isfinite(r['m']).all(axis=1)
-    for k in ('mean', 'scale'):
-        if k in r:
-            bad |= ~np.isfinite(r[k]).all(axis=1)
-    return int(np.argmax(bad)) if bad.any() else -1
-
-
-def _second(mi):
-    return [int(np.where((mi == 2 * np.eye(3, dtype=int)[k]).all(axis=1))[0][0]) for k in range(3)]
-
-
-def assert_state(got, b, ref, mi, upto, rtol, tag=''):
-    """Moments, means and scales of replicate b of `got` against `ref` on steps < upto: relative, with the natural
-    magnitude as the floor (1e-2 sd for a mean)."""
-    if upto <= 0:
-        return
-    _assert_moments(got['m'][b, :upto], ref['m'][:upto], mi, rtol)
-    sd = ref['scale'][:upto] if 'scale' in ref else np.sqrt(np.abs(ref['m'][:upto][:, _second(mi)]))
-    for k in ('mean', 'scale'):
-        if k in ref:
-            err = np.abs(got[k][b, :upto] - ref[k][:upto]) / np.maximum(np.abs(ref[k][:upto]), 1e-2 * sd)
-            assert err.max() <= rtol, f'{tag}: {k} error {err.max():.3e} > {rtol}'
-
-
-def compare(got, b, ref, mi, inds, tag=''):
-    """Replicate b of a device run against the oracle's run of it: 1e-6 on every step before either side poisons, and the
-    NaN criterion of tests/test_gpu_fuzz_1d.py -- a poisoning the other side does not share (or shares at another step)
-    is accepted only where the later side's Gram matrix around that step is numerically singular (cond >= 1e13).  With
-    stable=True, the comparison ends at the first step whose rule takes the LDL^T completion: its K_k have norms
-    ~ 1 / eps^2 and both eigensolvers are accurate relative to those norms only (the criterion of
-    tests/test_gpu_nd3.py::test_stable_filter_and_an_indefinite_start).  Returns the number of steps compared."""
-    T = ref['m'].shape[0]
-    f_dev, f_ora = int(got['fn'][b]), first_bad(ref)
-    upto = min(f if f >= 0 else T for f in (f_dev, f_ora))
-    completed = ref.get('completed', -1)
-    if 0 <= completed < upto:
-        assert_state(got, b, ref, mi, completed, RTOL, tag)
-        return completed
-    assert_state(got, b, ref, mi, upto, RTOL, tag)
-    if f_dev < 0 and f_ora < 0:
-        assert abs(got['nell'][b] - ref['nell']) <= RTOL * abs(ref['nell']), f'{tag}: nell {got["nell"][b]} vs {ref["nell"]}'
-    elif f_dev >= 0:
-        assert np.isnan(got['nell'][b]) and np.all(np.isnan(got['m'][b, f_dev:])), tag
-    if f_dev != f_ora:
-        later = got['m'][b] if (f_ora >= 0 and (f_dev < 0 or f_dev > f_ora)) else ref['m']
-        conds = [np.linalg.cond(later[t][inds[0]]) for t in range(max(upto - 2, 0), min(upto + 1, T))
-                 if np.all(np.isfinite(later[t]))]
-        assert conds and max(conds) >= 1e13, \
-            f'{tag}: poisons at step {f_dev} (device) / {f_ora} (oracle), cond {max(conds, default=0.):.1e}'
-    return upto
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -266,7 +42,7 @@ RULE_COV = _L @ _L.T                    # correlated, anisotropic (sd 0.5, 0.25,
 def _oracle_rule_err(mode, st, mi, inds, stable):
     """The oracle's own reproduction error on the same input: one oracle.multi_dims.moment_quadrature_nd rule integrating
     the monomials of the table in the mode's coordinates (max _moment_err)."""
-    key = {'raw': 'rms', 'central': 'cms', 'scaled': 'scms'}[mode]
+    key = MOMENTS_OF[mode]
     if mode == 'raw':
         w, x = omd.moment_quadrature_nd(st['rms'], inds, ldl=stable)
         u = x
@@ -277,7 +53,7 @@ def _oracle_rule_err(mode, st, mi, inds, stable):
         w, x = omd.moment_quadrature_nd(st['scms'], inds, st['mean'], st['scale'], ldl=stable)
         u = (x - st['mean']) / st['scale']
     rep = np.einsum('i,ij->j', w, np.prod(u[:, None, :] ** mi[None, :, :], axis=-1))
-    return float(_moment_err(rep[None], st[key][None], mi).max())
+    return float(moment_err(rep[None], st[key][None], mi).max())
 
 
 @pytest.mark.parametrize('stable', [False, True])
@@ -295,15 +71,15 @@ def test_rule_reproduces_its_input_moments(N, mode, stable):
     Bound: the oracle's own error for one rule on the same input (_oracle_rule_err), times the 2 T rules of the run (their
     errors add at most linearly), times 10 for the device's eigensolver (cyclic Jacobi) against LAPACK's."""
     T, B = 20, 2
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     st = initial(mi, RULE_MEAN, RULE_COV)
     q = 0.05 if mode == 'scaled' else 0.
     fns = moments.cond_moments_linear_gaussian(np.eye(3), q * RULE_COV, mi)
     ys = np.random.default_rng(N).normal(size=(B, T))
-    got = device(mode, fns, 'index', lambda y, x: stats.norm_pdf(y, 0. * x[2] + 0.3, 1.), ys, mi, inds, st, stable)
+    got = run_device(mode, fns, 'index', lambda y, x: stats.norm_pdf(y, 0. * x[2] + 0.3, 1.), ys, mi, inds, st, stable)
     e1 = _oracle_rule_err(mode, st, mi, inds, stable)
     bound = 10 * 2 * T * max(e1, np.finfo(float).eps)
-    key = {'raw': 'rms', 'central': 'cms', 'scaled': 'scms'}[mode]
+    key = MOMENTS_OF[mode]
     want = {'m': np.broadcast_to(st[key], (T, mi.shape[0]))}
     if mode != 'raw':
         want['mean'] = np.broadcast_to(st['mean'], (T, 3))
@@ -312,7 +88,7 @@ def test_rule_reproduces_its_input_moments(N, mode, stable):
     nell = np.sum(0.5 * (ys - 0.3) ** 2 + 0.5 * math.log(2 * math.pi), axis=1)
     assert np.all(got['fn'] == -1)
     print(f'N={N} {mode} stable={stable}: oracle one-rule error {e1:.2e}, device after {2 * T} rules '
-          f'{max(_moment_err(got["m"][b], want["m"], mi).max() for b in range(B)):.2e}, bound {bound:.2e}')
+          f'{max(moment_err(got["m"][b], want["m"], mi).max() for b in range(B)):.2e}, bound {bound:.2e}')
     for b in range(B):
         assert_state(got, b, want, mi, T, bound, f'N={N} {mode} stable={stable}')
         assert abs(got['nell'][b] - nell[b]) <= bound * abs(nell[b])
@@ -329,7 +105,7 @@ def test_independent_components_reduce_to_three_1d_filters():
     N, T, dt = 3, 15, 0.1
     a, bdisp, sd = np.array([-1.0, -0.6, -1.5]), np.array([0.3, 0.5, 0.4]), np.array([0.5, 0.8, 0.6])
     m0, v0 = np.array([0.2, -0.4, 0.6]), np.array([0.2, 0.1, 0.3])
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     st = initial(mi, m0, np.diag(v0))
     ys = np.array([0.3, -0.2, 0.5]) + np.random.default_rng(17).normal(size=(T, 3)) * 0.7
 
@@ -347,7 +123,7 @@ def test_independent_components_reduce_to_three_1d_filters():
 
     fns = moments.sde_cond_moments_tme(lambda x: np.array(drift(x), dtype=object), lambda x: np.array(disp(x), dtype=object),
                                        dt, 2, d=3)
-    got = device('central', fns, 'multi-index', pdf, ys[None], mi, inds, st)
+    got = run_device('central', fns, 'multi-index', pdf, ys[None], mi, inds, st)
     _, ocms, omean, _ = tme_sympy.sde_cond_moments_tme_nd(drift, disp, 3, dt, 2, mi)
     ref = omd.moment_filter_nd_cms((ocms, 'multi-index'), omean, opdf, ys, (mi, inds), st['cms'], m0)
     assert compare(got, 0, {'m': ref[0], 'mean': ref[1], 'nell': ref[2]}, mi, inds, 'independent d = 3') == T
@@ -360,8 +136,8 @@ def test_independent_components_reduce_to_three_1d_filters():
                                            ys[:, k])
         of = tme_sympy.sde_cond_moments_tme_1d(lambda x, k=k: float(a[k]) * x, lambda x, k=k: float(bdisp[k]), dt, 2, 2 * N)
         oc1, ome1, on1 = o1.moment_filter_cms(of[1], of[3], lambda y, x, k=k: om.norm_pdf(y, x, sd[k]), cms0, m0[k], ys[:, k])
-        gap_ora = _moment_err(marginalise_moments(ref[0], 3, N, k), oc1, mi1).max()
-        gap_dev = _moment_err(marginalise_moments(got['m'][0], 3, N, k), c1, mi1).max()
+        gap_ora = moment_err(marginalise_moments(ref[0], 3, N, k), oc1, mi1).max()
+        gap_dev = moment_err(marginalise_moments(got['m'][0], 3, N, k), c1, mi1).max()
         assert gap_dev <= gap_ora + 2 * RTOL, f'component {k}: moments {gap_dev:.3e} vs the oracle gap {gap_ora:.3e}'
         floor = 1e-2 * np.sqrt(oc1[:, 2])
         gap_ora = (np.abs(ref[1][:, k] - ome1) / np.maximum(np.abs(ome1), floor)).max()
@@ -389,7 +165,7 @@ def test_lotka_volterra_tables_fill_every_extent_byte(fam, min_extent):
     """What the Lotka--Volterra tests run through the kernel: coefficient blocks of extent >= 5 (TME-2) / 4 (TME-normal-3)
     that are not constant in any of the three variables, so that every byte of ext = ea | eb << 8 | ec << 16 matters."""
     fns, _, _ = family('lv', fam, 3)
-    model, keep = filtering._model_struct3(fns[0].tables, filtering._trace_likelihood(_lv_pdf, 3))
+    model, keep = filtering._model_struct3(fns[0].tables, filtering._trace_likelihood(lv_pdf, 3))
     assert model.extent >= min_extent
     ext = np.array(_extents(keep[0]))
     assert ext.max() >= min_extent
@@ -412,13 +188,13 @@ def test_lotka_volterra_against_the_oracle(N, fam, mode, stable, T):
     """The 3-species Lotka--Volterra model (state-dependent dispersion), a Gaussian factor on x_0 and a Poisson-softplus
     factor on x_2; replicate 1 of a batch of 2 against the oracle.  Raw mode at N = 4 may meet a numerically singular Gram
     matrix: compare() then applies the one-sided poisoning criterion instead of skipping."""
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     m = MODELS['lv']
     fns, sig, ofns = family('lv', fam, N)
     st = initial(mi, m.mean0, m.cov0)
     ys = m.ys(2, T, 100 + N)
-    got = device(mode, fns, sig, m.pdf, ys, mi, inds, st, stable)
-    ref = oracle(mode, ofns, sig, m.opdf, ys[1], mi, inds, st, stable)
+    got = run_device(mode, fns, sig, m.pdf, ys, mi, inds, st, stable)
+    ref = run_oracle(mode, ofns, sig, m.opdf, ys[1], mi, inds, st, stable, completed=True)
     upto = compare(got, 1, ref, mi, inds, f'lv N={N} {fam} {mode} stable={stable}')
     assert upto == T or (mode == 'raw' and N == 4)
 
@@ -427,36 +203,17 @@ def test_lotka_volterra_against_the_oracle(N, fam, mode, stable, T):
 def test_lorenz_tme_normal_3(N, T, mode, kan):
     """Lorenz-63 with the TME-normal-3 closure; at N = 2 against the oracle's own per-node Kan closure
     (oracle/tme_sympy.py sde_cond_moments_normal_nd)."""
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     m = MODELS['lorenz']
     fns, sig, ofns = family('lorenz', 'tme_normal_3', N)
     if kan:
-        orms, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(_lorenz_sympy, _disp_sympy, 3, DT, 3, mi)
+        orms, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(lorenz_drift, lorenz_disp, 3, DT, 3, mi)
         ofns = (orms, ocms, None, omean, None)
     st = initial(mi, m.mean0, m.cov0)
     ys = m.ys(2, T, 50 + N)
-    got = device(mode, fns, sig, m.pdf, ys, mi, inds, st)
-    ref = oracle(mode, ofns, sig, m.opdf, ys[1], mi, inds, st)
+    got = run_device(mode, fns, sig, m.pdf, ys, mi, inds, st)
+    ref = run_oracle(mode, ofns, sig, m.opdf, ys[1], mi, inds, st, completed=True)
     assert compare(got, 1, ref, mi, inds, f'lorenz N={N} tme_normal_3 {mode}') == T
-
-
-def factor_pdfs(spec):
-    """spec: [(kind, component, ycol, p)] -> (device pdf, oracle pdf): the product of the factors in that order.  Gaussian:
-    N(y; x, p^2); Poisson: rate softplus(p x); Bernoulli: logistic(p x - 1)."""
-    def one(kind, y, xk, p, dev):
-        if kind == 'gaussian':
-            return stats.norm_pdf(y, xk, p) if dev else om.norm_pdf(y, xk, p)
-        if kind == 'poisson':
-            return stats.poisson_pmf(y, sym.log(1. + sym.exp(xk * p))) if dev else om.poisson_pmf(y, np.log1p(np.exp(xk * p)))
-        return (stats.bernoulli_pmf(y, 1. / (1. + sym.exp(-(xk * p) + 1.))) if dev else
-                om.bernoulli_pmf(y, 1. / (1. + np.exp(-(xk * p) + 1.))))
-
-    def pdf(y, x):
-        return math.prod(one(kind, y[c], x[j], p, True) for kind, j, c, p in spec)
-
-    def opdf(y, x):
-        return float(math.prod(one(kind, y[c], x[j], p, False) for kind, j, c, p in spec))
-    return pdf, opdf
 
 
 def factor_ys(spec, B, T, seed):
@@ -483,7 +240,6 @@ WIRING = {
     # two factors on x_1 (columns 2 and 0) and a third, on x_0, between them
     'two_on_x1': [('gaussian', 1, 2, 0.3), ('bernoulli', 0, 1, 2.0), ('gaussian', 1, 0, 0.5)],
 }
-_KIND = {'gaussian': 'gaussian', 'poisson': 'poisson_softplus', 'bernoulli': 'bernoulli_logistic'}
 
 
 @pytest.mark.parametrize('case', list(WIRING))
@@ -492,27 +248,23 @@ def test_likelihood_wiring(case):
     factors, the components and the columns: Lotka--Volterra, TME-2, N = 3, central, against the oracle."""
     spec = WIRING[case]
     N, T = 3, 6
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     m = MODELS['lv']
     fns, sig, ofns = family('lv', 'tme_2', N)
     pdf, opdf = factor_pdfs(spec)
     assert [(f.kind, f.component, f.ycol) for f in filtering._trace_likelihood(pdf, 3)] == \
-        [(_KIND[kind], j, c) for kind, j, c, _ in spec]
+        [(KIND_NAMES[kind], j, c) for kind, j, c, _ in spec]
     st = initial(mi, m.mean0, m.cov0)
     ys = factor_ys(spec, 2, T, 7)
-    got = device('central', fns, sig, pdf, ys, mi, inds, st)
-    ref = oracle('central', ofns, sig, opdf, ys[0], mi, inds, st)
+    got = run_device('central', fns, sig, pdf, ys, mi, inds, st)
+    ref = run_oracle('central', ofns, sig, opdf, ys[0], mi, inds, st, completed=True)
     assert compare(got, 0, ref, mi, inds, case) == T
-
-
-def _assert_same_bits(a, b, keys=('m', 'mean', 'scale', 'nell', 'fn')):
-    assert_same_bits([a.get(k) for k in keys], [b.get(k) for k in keys], names=keys)
 
 
 def test_per_replicate_likelihood_parameters_are_bit_identical_to_single_runs():
     """lik_batched: a Gaussian factor with a per-replicate sd and a Bernoulli factor with a per-replicate offset."""
     N, T, B = 2, 10, 3
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     m = MODELS['lv']
     fns, sig, _ = family('lv', 'tme_2', N)
     sds, offs = np.array([0.15, 0.3, 0.6]), np.array([0.5, 1.0, 2.0])
@@ -525,51 +277,51 @@ def test_per_replicate_likelihood_parameters_are_bit_identical_to_single_runs():
     st = initial(mi, m.mean0, m.cov0)
     ys = factor_ys([('gaussian', 0, 0, 0.3), ('bernoulli', 1, 1, 2.0)], B, T, 5)
     for mode in ('central', 'scaled'):
-        got = device(mode, fns, sig, pdf_of(sds, offs), ys, mi, inds, st)
+        got = run_device(mode, fns, sig, pdf_of(sds, offs), ys, mi, inds, st)
         assert np.all(got['fn'] == -1) and len(set(got['nell'].tolist())) == B
         for b in range(B):
-            one = device(mode, fns, sig, pdf_of(float(sds[b]), float(offs[b])), ys[b:b + 1], mi, inds, st)
-            _assert_same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
+            one = run_device(mode, fns, sig, pdf_of(float(sds[b]), float(offs[b])), ys[b:b + 1], mi, inds, st)
+            same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
 
 
 def test_per_replicate_tables_and_initial_states_are_bit_identical_to_single_runs():
     """Per-replicate transition tables (batch_closures over the dispersion sigma) and per-replicate m0 / mean0 / scale0:
     each replicate has the bits of its own single-replicate run."""
     N, T, B = 2, 10, 3
-    mi, inds = _tables(N)
-    per = [moments.sde_cond_moments_tme(mdl.drift, mdl.disp, LV_DT, 2, d=3)
+    mi, inds = tables(3, N)
+    per = [moments.sde_cond_moments_tme(host_drift(mdl), host_disp(mdl), LV_DT, 2, d=3)
            for mdl in (lv_model(sig=LV_SIG * f) for f in (0.5, 1.0, 2.0))]
     bfns = moments.batch_closures(per)
     ys = lv_ys(B, T, 9)
     st = initial(mi, LV_M0, LV_C0)
     for mode in MODES:
-        got = device(mode, bfns, 'multi-index', _lv_pdf, ys, mi, inds, st)
+        got = run_device(mode, bfns, 'multi-index', lv_pdf, ys, mi, inds, st)
         assert np.all(got['fn'] == -1) and len(set(got['nell'].tolist())) == B
         for b in range(B):
-            one = device(mode, per[b], 'multi-index', _lv_pdf, ys[b:b + 1], mi, inds, st)
-            _assert_same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
+            one = run_device(mode, per[b], 'multi-index', lv_pdf, ys[b:b + 1], mi, inds, st)
+            same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
     fns, sig, _ = family('lv', 'tme_2', N)
     shifts = np.array([[0., 0., 0.], [0.1, -0.05, 0.02], [-0.1, 0.1, 0.]])
     states = [initial(mi, LV_M0 + shifts[b], LV_C0 * f) for b, f in enumerate((1., 1.5, 0.7))]
     for mode in MODES:
-        got = device(mode, fns, sig, _lv_pdf, ys, mi, inds, stack_initial(states))
+        got = run_device(mode, fns, sig, lv_pdf, ys, mi, inds, stack_initial(states))
         assert np.all(got['fn'] == -1) and len(set(got['nell'].tolist())) == B
         for b in range(B):
-            one = device(mode, fns, sig, _lv_pdf, ys[b:b + 1], mi, inds, states[b])
-            _assert_same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
+            one = run_device(mode, fns, sig, lv_pdf, ys[b:b + 1], mi, inds, states[b])
+            same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
 
 
 @pytest.mark.parametrize('mode', MODES)
 def test_nan_measurement_poisons_its_replicate_from_that_step(mode):
     N, T, B, t_nan = 2, 12, 3, 7
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     fns, sig, _ = family('lv', 'tme_2', N)
     st = initial(mi, LV_M0, LV_C0)
     ys = lv_ys(B, T, 21)
-    clean = device(mode, fns, sig, _lv_pdf, ys, mi, inds, st)
+    clean = run_device(mode, fns, sig, lv_pdf, ys, mi, inds, st)
     assert np.all(clean['fn'] == -1)
     ys[1, t_nan, 0] = np.nan
-    got = device(mode, fns, sig, _lv_pdf, ys, mi, inds, st)
+    got = run_device(mode, fns, sig, lv_pdf, ys, mi, inds, st)
     assert list(got['fn']) == [-1, t_nan, -1]
     assert np.isnan(got['nell'][1])
     for k in ('m', 'mean', 'scale'):
@@ -584,15 +336,15 @@ def test_nan_measurement_poisons_its_replicate_from_that_step(mode):
 def test_empty_batch_and_zero_steps(mode):
     """B = 0 gives empty outputs, T = 0 the initial state's shapes, a zero NLL and no poisoning."""
     N = 2
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     z = mi.shape[0]
     fns, sig, _ = family('lv', 'tme_2', N)
     st = initial(mi, LV_M0, LV_C0)
     ys = lv_ys(3, 5, 1)
-    r = device(mode, fns, sig, _lv_pdf, ys[:0], mi, inds, st)
+    r = run_device(mode, fns, sig, lv_pdf, ys[:0], mi, inds, st)
     assert r['m'].shape == (0, 5, z) and r['nell'].shape == (0,) and r['fn'].shape == (0,)
     assert all(r[k].shape == (0, 5, 3) for k in ('mean', 'scale') if k in r)
-    r = device(mode, fns, sig, _lv_pdf, ys[:, :0], mi, inds, st)
+    r = run_device(mode, fns, sig, lv_pdf, ys[:, :0], mi, inds, st)
     assert r['m'].shape == (3, 0, z)
     assert all(r[k].shape == (3, 0, 3) for k in ('mean', 'scale') if k in r)
     npt.assert_array_equal(r['nell'], np.zeros(3))
@@ -614,9 +366,9 @@ def test_long_horizon_golden_fixture():
     assert float(g['lv_dt']) == LV_DT and float(g['lv_sd']) == LV_SD and float(g['lorenz_dt']) == DT
     for model in ('lorenz', 'lv'):
         m = MODELS[model]
-        fns = moments.sde_cond_moments_tme(m.drift, m.disp, m.dt, 2, d=3)
+        fns = moments.sde_cond_moments_tme(host_drift(m), host_disp(m), m.dt, 2, d=3)
         for N, T in ((3, 200), (4, 50)):
-            mi, inds = _tables(N)
+            mi, inds = tables(3, N)
             st = initial(mi, m.mean0, m.cov0)
             ys = g[f'{model}_ys'][None, :T]
             for mode in ('central', 'scaled'):
@@ -625,7 +377,7 @@ def test_long_horizon_golden_fixture():
                 if mode == 'scaled':
                     ref['scale'] = g[f'{key}_scales']
                 assert ref['m'].shape == (T, mi.shape[0])
-                got = device(mode, fns, 'multi-index', m.pdf, ys, mi, inds, st)
+                got = run_device(mode, fns, 'multi-index', m.pdf, ys, mi, inds, st)
                 f_ora = first_bad(ref)
                 assert int(got['fn'][0]) == f_ora, f'{key}: first NaN {got["fn"][0]} vs {f_ora}'
                 assert_state(got, 0, ref, mi, T if f_ora < 0 else f_ora, RTOL, key)
@@ -655,7 +407,7 @@ def test_reversing_the_components_reverses_the_outputs(fam, mode):
     amplify over the 2 T rules of a run, 2 T cond(G0) eps (raw moments about the origin: cond(G0) = 2e5)."""
     N, T, B = 3, 10, 2
     p = REV
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     spec = [('gaussian', 0, 0, 0.2), ('poisson', 2, 1, 1.0), ('bernoulli', 1, 2, 2.0)]
     spec_p = [(kind, int(np.where(p == j)[0][0]), c, q) for kind, j, c, q in spec]
     ys = factor_ys(spec, B, T, 13)
@@ -664,10 +416,10 @@ def test_reversing_the_components_reverses_the_outputs(fam, mode):
                                (LV_A[p][:, p], LV_SIG[p], LV_M0[p], LV_C0[p][:, p], spec_p)):
         mdl = lv_model(A, sig)
         if fam == 'tme_2':
-            fns, sig_ = moments.sde_cond_moments_tme(mdl.drift, mdl.disp, LV_DT, 2, d=3), 'multi-index'
+            fns, sig_ = moments.sde_cond_moments_tme(host_drift(mdl), host_disp(mdl), LV_DT, 2, d=3), 'multi-index'
         else:
-            fns, sig_ = moments.sde_cond_moments_tme_normal(mdl.drift, mdl.disp, LV_DT, 2, mi), 'index'
-        out.append(device(mode, fns, sig_, factor_pdfs(sp)[0], ys, mi, inds, initial(mi, m0, c0)))
+            fns, sig_ = moments.sde_cond_moments_tme_normal(host_drift(mdl), host_disp(mdl), LV_DT, 2, mi), 'index'
+        out.append(run_device(mode, fns, sig_, factor_pdfs(sp)[0], ys, mi, inds, initial(mi, m0, c0)))
     # moment j of x' is the moment n of x with n[p] = n'_j
     idx = []
     for row in mi:
@@ -677,9 +429,9 @@ def test_reversing_the_components_reverses_the_outputs(fam, mode):
     ref, got = out
     assert np.all(ref['fn'] == -1) and np.all(got['fn'] == -1)
     st = initial(mi, LV_M0, LV_C0)
-    g0 = st[{'raw': 'rms', 'central': 'cms', 'scaled': 'scms'}[mode]][inds[0]]
+    g0 = st[MOMENTS_OF[mode]][inds[0]]
     bound = max(1e-10, 2 * T * np.linalg.cond(g0) * np.finfo(float).eps)
-    err = max(_moment_err(got['m'][b], ref['m'][b][:, idx], mi).max() for b in range(B))
+    err = max(moment_err(got['m'][b], ref['m'][b][:, idx], mi).max() for b in range(B))
     print(f'{fam} {mode}: moments of the reversed run off by {err:.1e}, bound {bound:.1e}')
     for b in range(B):
         want = {'m': ref['m'][b][:, idx]}

@@ -2,8 +2,9 @@
 atan2(p, sqrt(q)) of trivariate polynomials, against the oracle's N-D filters, whose measurement density is any Python
 callable of (y, x).
 
-Bar: that of tests/test_gpu_nd3.py and tests/test_gpu_nd3_envelope.py (`compare`: 1e-6 relative on NLL, means, scales and
-moments with the natural-magnitude floor; under stable=True the comparison stops at the first LDL^T completion).
+Bar: that of tests/test_gpu_nd3.py and tests/test_gpu_nd3_envelope.py (`compare` of tests/nd_support.py: 1e-6 relative on
+NLL, means, scales and moments with the natural-magnitude floor; under stable=True the comparison stops at the first LDL^T
+completion).
 
 Inputs were chosen so that the ORACLE ALONE stays finite: every (case, N, family, mode, stable) combination of
 `PARITY` was run through oracle/multi_dims.py alone on the CPU, with the data of this file; none of the 50 poisons.  The
@@ -13,39 +14,21 @@ range-azimuth-elevation at N = 3 runs T = 8.  The Lotka--Volterra cases run T = 
 softplus(x0 + x1 + x2) ~ 3; Bernoulli draws of a degree-2 logit).  Each headline test asserts that the oracle run is finite, so
 a comparison of NaN patterns cannot pass for a comparison of numbers.
 """
-import math
-
 import numpy as np
 import numpy.testing as npt
 import pytest
 
 from mfs_amd import stats, sym
-from mfs_amd.multi_dims import filtering
+from mfs_amd.multi_dims import filtering, moments, ss_models
 from oracle import models as om
-from .test_gpu_nd3 import BETA, DT, M0, C0, RHO, SIG, _moment_err, _tables
-from .plan_api import run_plan_nd
-from .test_gpu_nd3_envelope import (LV_C0, LV_M0, MODES, _assert_same_bits, compare, device, family, first_bad, initial, lv_path,
-                                    oracle, stack_initial)
+from tests.nd3_models import C0, LV_C0, LV_M0, M0, family, lorenz_path, lv_path
+from tests.nd_support import MODES, compare, first_bad, initial, moment_err, run_device, run_oracle, same_bits, tables
+from tests.plan_api import run_plan_nd
 
 pytestmark = pytest.mark.gpu
 
 SENSOR = np.array([-5., -5., -2.])
 PROD_SD, RANGE_SD, ANGLE_SD = 0.5, 0.5, 0.1
-
-
-def lorenz_path(B, T, seed):
-    """Euler--Maruyama Lorenz-63 states (units of 10) on 10 sub-steps per DT, (B, T, 3), and the generator."""
-    rng = np.random.default_rng(seed)
-    x = M0 + 0.1 * rng.standard_normal((B, 3))
-    h = DT / 10
-    xs = np.empty((B, T, 3))
-    for t in range(T):
-        for _ in range(10):
-            a = np.stack([SIG * (x[:, 1] - x[:, 0]), x[:, 0] * (RHO - 10. * x[:, 2]) - x[:, 1],
-                          10. * x[:, 0] * x[:, 1] - BETA * x[:, 2]], axis=-1)
-            x = x + a * h + 0.1 * math.sqrt(h) * rng.standard_normal((B, 3))
-        xs[:, t] = x
-    return xs, rng
 
 
 # ---- the measurement models: device callable (traced), oracle callable (numbers), data ----
@@ -145,7 +128,7 @@ def mixed_ys(B, T, seed):
                      xs[..., 2] + MIX_SD * rng.standard_normal((B, T))], axis=-1)
 
 
-# case -> (dynamics of test_gpu_nd3_envelope.MODELS, device pdf, oracle pdf, data, mean0, cov0, {N: T})
+# case -> (dynamics of nd3_models.MODELS, device pdf, oracle pdf, data, mean0, cov0, {N: T})
 CASES = {
     'product': ('lorenz', product_pdf(), product_opdf(), product_ys, M0, C0, {2: 16, 3: 10, 4: 3}),
     'rae': ('lorenz', rae_pdf(), rae_opdf(), rae_ys, M0, C0, {2: 16, 3: 8, 4: 3}),
@@ -163,7 +146,7 @@ PARITY = [(case,) + run for case in CASES for run in RUNS]
 
 def setup(case, N, fam):
     model, pdf, opdf, ys_of, mean0, cov0, horizon = CASES[case]
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     fns, sig, ofns = family(model, NORMAL[model] if fam == 'normal' else fam, N)
     return pdf, opdf, ys_of, horizon[N], mi, inds, fns, sig, ofns, initial(mi, mean0, cov0)
 
@@ -172,8 +155,8 @@ def setup(case, N, fam):
 def test_joint_factors_match_the_oracle(case, N, fam, mode, stable):
     pdf, opdf, ys_of, T, mi, inds, fns, sig, ofns, st = setup(case, N, fam)
     ys = ys_of(2, T, 100 + N)
-    got = device(mode, fns, sig, pdf, ys, mi, inds, st, stable)
-    ref = oracle(mode, ofns, sig, opdf, ys[0], mi, inds, st, stable)
+    got = run_device(mode, fns, sig, pdf, ys, mi, inds, st, stable)
+    ref = run_oracle(mode, ofns, sig, opdf, ys[0], mi, inds, st, stable, completed=True)
     tag = f'{case} N={N} {fam} {mode} stable={stable}'
     assert first_bad(ref) < 0 and np.isfinite(ref['nell']), f'{tag}: the oracle alone poisons; not a test input'
     assert got['fn'][0] == -1, f'{tag}: the device poisons at step {got["fn"][0]}, the oracle does not'
@@ -222,9 +205,9 @@ def _oracle_of(kind, k):
 
 
 def _gap(a, b, mi):
-    """Largest relative gap between two single-replicate runs over NLL, means, scales and moments (moments as `_moment_err`)."""
+    """Largest relative gap between two single-replicate runs over NLL, means, scales and moments (moments as `moment_err`)."""
     g = float(abs(a['nell'] - b['nell']) / abs(b['nell']))
-    g = max(g, float(np.nanmax(_moment_err(a['m'], b['m'], mi))))
+    g = max(g, float(np.nanmax(moment_err(a['m'], b['m'], mi))))
     for k in ('mean', 'scale'):
         if k in a and k in b:
             g = max(g, float(np.max(np.abs(a[k] - b[k]) / np.maximum(np.abs(b[k]), 1e-300))))
@@ -242,7 +225,7 @@ def test_joint_poly_of_one_component_agrees_with_the_single_component_factor(kin
     the factor by 1 * 1, and both evaluate the argument by the same fused Horner steps -- while each run is 2e-13 .. 9e-12 from
     the oracle (the test prints the three figures of each case)."""
     N, T = 3, 8
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     fns, sig, ofns = family('lv', 'tme_2', N)
     st = initial(mi, LV_M0, LV_C0)
     xs, rng = lv_path(2, T, 7 + k)
@@ -255,9 +238,9 @@ def test_joint_poly_of_one_component_agrees_with_the_single_component_factor(kin
     traced = filtering._trace_likelihood(_joint_of(kind, k), 3)
     assert isinstance(traced[0], sym.JointLikelihoodSpec) and traced[0].link == 'poly'
     assert not isinstance(filtering._trace_likelihood(_single_of(kind, k), 3)[0], sym.JointLikelihoodSpec)
-    joint = device(mode, fns, sig, _joint_of(kind, k), ys, mi, inds, st)
-    single = device(mode, fns, sig, _single_of(kind, k), ys, mi, inds, st)
-    ref = oracle(mode, ofns, sig, _oracle_of(kind, k), ys[0], mi, inds, st)
+    joint = run_device(mode, fns, sig, _joint_of(kind, k), ys, mi, inds, st)
+    single = run_device(mode, fns, sig, _single_of(kind, k), ys, mi, inds, st)
+    ref = run_oracle(mode, ofns, sig, _oracle_of(kind, k), ys[0], mi, inds, st, completed=True)
     assert first_bad(ref) < 0
     assert compare(joint, 0, ref, mi, inds, 'joint') == T and compare(single, 0, ref, mi, inds, 'single') == T
     j0, s0 = _rows(joint, 0), _rows(single, 0)
@@ -272,26 +255,26 @@ def test_joint_poly_of_one_component_agrees_with_the_single_component_factor(kin
 @pytest.mark.parametrize('mode', MODES)
 def test_batch_position_and_poisoned_neighbours_do_not_change_a_replicate(mode):
     N, T, B = 2, 12, 4
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     fns, sig, _ = family('lorenz', 'tme_2', N)
     st = initial(mi, M0, C0)
     ys = rae_ys(B, T, 5)
-    clean = device(mode, fns, sig, rae_pdf(), ys, mi, inds, st)
+    clean = run_device(mode, fns, sig, rae_pdf(), ys, mi, inds, st)
     assert np.all(clean['fn'] == -1) and len(set(clean['nell'].tolist())) == B
     perm = np.array([2, 0, 3, 1])
-    moved = device(mode, fns, sig, rae_pdf(), ys[perm], mi, inds, st)
-    _assert_same_bits(moved, _rows(clean, perm))
+    moved = run_device(mode, fns, sig, rae_pdf(), ys[perm], mi, inds, st)
+    same_bits(moved, _rows(clean, perm))
     # a NaN measurement in a joint factor's column (the elevation) poisons that replicate from that step, and no other
     t_nan = 5
     bad = ys.copy()
     bad[1, t_nan, 2] = np.nan
-    got = device(mode, fns, sig, rae_pdf(), bad, mi, inds, st)
+    got = run_device(mode, fns, sig, rae_pdf(), bad, mi, inds, st)
     assert list(got['fn']) == [-1, t_nan, -1, -1] and np.isnan(got['nell'][1])
     for k in ('m', 'mean', 'scale'):
         if k in got:
             assert np.all(np.isnan(got[k][1, t_nan:])), k
             npt.assert_array_equal(got[k][1, :t_nan], clean[k][1, :t_nan], err_msg=k)
-    _assert_same_bits(_rows(got, [0, 2, 3]), _rows(clean, [0, 2, 3]))
+    same_bits(_rows(got, [0, 2, 3]), _rows(clean, [0, 2, 3]))
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -299,7 +282,7 @@ def test_per_replicate_sensors_and_noise_equal_separate_runs(mode):
     """mfs_joint_nd3.batched: sensor positions (coefficient blocks) and noise levels (par) per replicate, stacked with
     stats.batch_likelihoods, together with a per-replicate single-component factor."""
     N, T, B = 2, 10, 3
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     fns, sig, _ = family('lorenz', 'tme_2', N)
     st = initial(mi, M0, C0)
     sensors = np.array([[-5., -5., -2.], [-4., -6., -3.], [6., -5., -1.5]])
@@ -311,34 +294,34 @@ def test_per_replicate_sensors_and_noise_equal_separate_runs(mode):
     batched = stats.batch_likelihoods([member(b) for b in range(B)])
     joint, _ = filtering._joint_struct3(filtering._trace_likelihood(batched, 3), B)
     assert joint.batched == 1 and joint.n_joint == 3
-    got = device(mode, fns, sig, batched, ys, mi, inds, st)
+    got = run_device(mode, fns, sig, batched, ys, mi, inds, st)
     assert np.all(got['fn'] == -1) and len(set(got['nell'].tolist())) == B
     for b in range(B):
-        one = device(mode, fns, sig, member(b), ys[b:b + 1], mi, inds, st)
-        _assert_same_bits(_rows(got, slice(b, b + 1)), one)
+        one = run_device(mode, fns, sig, member(b), ys[b:b + 1], mi, inds, st)
+        same_bits(_rows(got, slice(b, b + 1)), one)
     # a mixed model: per-replicate single-component parameters and joint parameters in one batch
     mix = stats.batch_likelihoods([lambda y, x, b=b: stats.norm_pdf(y[1], x[2], 0.4 + 0.1 * b)
                                    * stats.norm_pdf(y[0], x[0] * x[1] + 0.1 * b, 0.5 + 0.2 * b) for b in range(B)])
     ysm = mixed_ys(B, T, 8)
-    gm = device(mode, fns, sig, mix, ysm, mi, inds, st)
+    gm = run_device(mode, fns, sig, mix, ysm, mi, inds, st)
     assert np.all(gm['fn'] == -1)
     for b in range(B):
-        one = device(mode, fns, sig, lambda y, x, b=b: stats.norm_pdf(y[1], x[2], 0.4 + 0.1 * b)
+        one = run_device(mode, fns, sig, lambda y, x, b=b: stats.norm_pdf(y[1], x[2], 0.4 + 0.1 * b)
                      * stats.norm_pdf(y[0], x[0] * x[1] + 0.1 * b, 0.5 + 0.2 * b), ysm[b:b + 1], mi, inds, st)
-        _assert_same_bits(_rows(gm, slice(b, b + 1)), one)
+        same_bits(_rows(gm, slice(b, b + 1)), one)
 
 
 @pytest.mark.parametrize('mode', MODES)
 def test_empty_batch_and_zero_steps(mode):
     N = 2
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     z = mi.shape[0]
     fns, sig, _ = family('lorenz', 'tme_2', N)
     st = initial(mi, M0, C0)
     ys = rae_ys(3, 5, 1)
-    r = device(mode, fns, sig, rae_pdf(), ys[:0], mi, inds, st)
+    r = run_device(mode, fns, sig, rae_pdf(), ys[:0], mi, inds, st)
     assert r['m'].shape == (0, 5, z) and r['nell'].shape == (0,) and r['fn'].shape == (0,)
-    r = device(mode, fns, sig, rae_pdf(), ys[:, :0], mi, inds, st)
+    r = run_device(mode, fns, sig, rae_pdf(), ys[:, :0], mi, inds, st)
     assert r['m'].shape == (3, 0, z)
     npt.assert_array_equal(r['nell'], np.zeros(3))
     npt.assert_array_equal(r['fn'], -np.ones(3))
@@ -346,11 +329,11 @@ def test_empty_batch_and_zero_steps(mode):
 
 def test_plan_is_bit_identical_to_the_host_entry_point():
     N, T, B = 3, 6, 3
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     fns, sig, _ = family('lorenz', 'tme_2', N)
     st = initial(mi, M0, C0)
     ys = np.ascontiguousarray(rae_ys(B, T, 11))
-    host = device('central', fns, sig, rae_pdf(), ys, mi, inds, st)
+    host = run_device('central', fns, sig, rae_pdf(), ys, mi, inds, st)
     factors = filtering._trace_likelihood(rae_pdf(), 3)
     model, keep = filtering._model_struct3(fns[1].tables, [], B, ny=3)
     joint, keep_joint = filtering._joint_struct3(factors, B)
@@ -366,20 +349,19 @@ def test_plan_is_bit_identical_to_the_host_entry_point():
 def test_negative_sqrt_argument_poisons_only_its_replicate():
     """sqrt of a negative value is NaN at the node and poisons the replicate through p(y), as a non-finite posterior does."""
     N, T, B = 2, 4, 2
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     fns, sig, _ = family('lorenz', 'tme_2', N)
     st = initial(mi, M0, C0)
     members = [lambda y, x: stats.norm_pdf(y, sym.sqrt(x[0] * x[0] + x[1] * x[1] + 1.), 0.5),
                lambda y, x: stats.norm_pdf(y, sym.sqrt(x[0] * x[0] + x[1] * x[1] - 100.), 0.5)]
     ys = np.ones((B, T))
-    got = device('central', fns, sig, stats.batch_likelihoods(members), ys, mi, inds, st)
+    got = run_device('central', fns, sig, stats.batch_likelihoods(members), ys, mi, inds, st)
     assert list(got['fn']) == [-1, 0] and np.isfinite(got['nell'][0]) and np.isnan(got['nell'][1])
 
 
 def test_tracking_model_factory_runs():
-    from mfs_amd.multi_dims import moments, ss_models
     N = 2
-    mi, inds = _tables(N)
+    mi, inds = tables(3, N)
     dt, T, ts, gs, drift, dispersion, emission, pdf, simulate = ss_models.lorenz_tracking(mi)
     _, _, ys = simulate(np.random.default_rng(3))
     fns = moments.sde_cond_moments_tme(drift, dispersion, dt, 2, d=3)

@@ -7,7 +7,7 @@ initial laws; chunked launches; NaN measurements; the exchange of the two state 
 Models: tests/nd_envelope_models.py -- lv2 (every order of its TME table weighs 10 .. 1000 times the bar), lin2 (raw mode up to
 N = 7), well2 (unequal extents per variable, the extent limits, a cubic Euler mean).  Oracle: oracle/multi_dims.py with the SymPy
 tables of oracle/tme_sympy.py for N <= 4 and with the host's NumPy closures for N = 5..7, which tests/test_host_nd.py pins to
-SymPy.  The bar is that of tests/test_gpu_parity_nd.py: 1e-6 relative on NLL, means and scales, `_assert_moments` at 1e-6, equal
+SymPy.  The bar is that of tests/test_gpu_parity_nd.py: 1e-6 relative on NLL, means and scales, nd_support.assert_moments at 1e-6, equal
 first-NaN steps.  Every case first asserts on the oracle alone that it is admissible (nd_envelope_models.admissible): no case
 is skipped.  Where a test uses another bound, it says where the bound comes from.
 
@@ -51,16 +51,13 @@ import pytest
 
 from mfs_amd import _lib, stats, sym
 from mfs_amd.multi_dims import filtering, moments
-from oracle import multi_dims as omd, one_dim as o1
-from . import nd_envelope_models as em
-from .test_gpu_nd3_envelope import _assert_same_bits, device, first_bad, stack_initial
-from .test_gpu_nd_reference import _bearing_only_model
-from .test_gpu_parity_nd import _assert_moments
+from oracle import models as om, multi_dims as omd, one_dim as o1
+from tests import nd_envelope_models as em, nd_support as ns
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-6
-MODES = em.MODES
+MODES = ns.MODES
 
 
 def steps(N):
@@ -79,10 +76,10 @@ SEEDS = {('well2', 'tme_1', 6, 'central'): 1, ('well2', 'tme_1', 6, 'scaled'): 1
 
 def run_device(model, fam, N, mode, ys, spec=None, st=None, stable=False, pdf=None):
     m = em.MODELS[model]
-    mi, inds = em.tables(N)
+    mi, inds = ns.tables(2, N)
     fns, sig = em.host_family(model, fam, N)
-    pdf = em.factor_pdfs(m.spec if spec is None else spec)[0] if pdf is None else pdf
-    return device(mode, fns, sig, pdf, ys, mi, inds, em.initial(mi, m.mean0, m.cov0) if st is None else st, stable)
+    pdf = ns.factor_pdfs(m.spec if spec is None else spec)[0] if pdf is None else pdf
+    return ns.run_device(mode, fns, sig, pdf, ys, mi, inds, ns.initial(mi, m.mean0, m.cov0) if st is None else st, stable)
 
 
 def rel(got, ref):
@@ -91,34 +88,32 @@ def rel(got, ref):
 
 def assert_parity(got, b, ref, N, tag, rtol=RTOL):
     """Replicate b of a device run against an oracle run that is finite throughout: equal first-NaN steps (none), NLL, means and
-    scales to rtol relative, the moments by _assert_moments.  Prints the figures before it asserts."""
-    mi, _ = em.tables(N)
-    assert em.all_finite(ref), f'{tag}: the oracle is not finite'
+    scales to rtol relative, the moments by assert_moments.  Prints the figures before it asserts."""
+    mi, _ = ns.tables(2, N)
+    assert ns.all_finite(ref), f'{tag}: the oracle is not finite'
     errs = {'nell': rel(got['nell'][b], ref['nell'])}
     for k in ('mean', 'scale'):
         if k in ref:
             errs[k] = rel(got[k][b], ref[k])
     fin = np.isfinite(got['m'][b]).all()
     if fin:
-        second = [int(np.where((mi == 2 * np.eye(2, dtype=int)[k]).all(axis=1))[0][0]) for k in range(2)]
-        nat = np.prod(np.sqrt(np.abs(ref['m'][:, second]))[:, None, :] ** mi[None], axis=-1)
-        errs['m'] = float(np.max(np.abs(got['m'][b] - ref['m']) / np.maximum(np.abs(ref['m']), nat * 1e-2 + 1e-300)))
+        errs['m'] = float(np.max(ns.moment_err(got['m'][b], ref['m'], mi)))
     print(f'PARITY {tag}: ' + ' '.join(f'{k}={v:.2e}' for k, v in errs.items()))
-    assert int(got['fn'][b]) == first_bad(ref) == -1, f'{tag}: first NaN at {got["fn"][b]} (device) / {first_bad(ref)} (oracle)'
+    assert int(got['fn'][b]) == ns.first_bad(ref) == -1, f'{tag}: first NaN at {got["fn"][b]} (device) / {ns.first_bad(ref)} (oracle)'
     npt.assert_allclose(got['nell'][b], ref['nell'], rtol=rtol, err_msg=tag)
     for k in ('mean', 'scale'):
         if k in ref:
             npt.assert_allclose(got[k][b], ref[k], rtol=rtol, err_msg=f'{tag}: {k}')
-    _assert_moments(got['m'][b], ref['m'], mi, rtol)
+    ns.assert_moments(got['m'][b], ref['m'], mi, rtol)
 
 
 def admit(mode, ref, central):
     """The admission condition (nd_envelope_models.admissible) for an oracle run made outside oracle_case: finite, and a raw run
     within 1e-8 of the central one, which `central()` computes, in NLL and means."""
-    assert em.all_finite(ref), 'the oracle is not finite'
+    assert ns.all_finite(ref), 'the oracle is not finite'
     if mode == 'raw':
         cen = central()
-        assert em.all_finite(cen)
+        assert ns.all_finite(cen)
         assert rel(ref['nell'], cen['nell']) <= 1e-8 and rel(em.raw_means(ref['m']), cen['mean']) <= 1e-8
 
 
@@ -196,7 +191,7 @@ def test_the_cases_cover_every_kernel_in_every_mode():
     seen = {}
     for model, fam, N, mode in CASES:
         fns, sig = em.host_family(model, fam, N)
-        seen.setdefault(kernel_of(fns, sig, em.factor_pdfs(em.MODELS[model].spec)[0], N), set()).add(mode)
+        seen.setdefault(kernel_of(fns, sig, ns.factor_pdfs(em.MODELS[model].spec)[0], N), set()).add(mode)
     kernels = [(N, tk) for N in ALL_N for tk in (0, 1, 2)]
     assert sorted(seen) == kernels
     for k in kernels:
@@ -220,7 +215,7 @@ def test_well2_extents_beyond_the_tables_are_refused_and_the_library_goes_on():
     """well2's TME-2 table has extent 7 (the 16-row layout holds 6) and its TME-3 table extent 10 (the 29-row layout holds 7):
     both are refused on the host, naming the extent; TME-1 (extent 4, unequal per variable) then gives the bits it gave before."""
     N, T = 3, 10
-    mi, inds = em.tables(N)
+    mi, inds = ns.tables(2, N)
     m = em.MODELS['well2']
     ys = em.measurements('well2', 2, T, 5)
     before = run_device('well2', 'tme_1', N, 'central', ys)
@@ -234,14 +229,13 @@ def test_well2_extents_beyond_the_tables_are_refused_and_the_library_goes_on():
     dense, D = fns[1].tables.dense_table()
     ext = [tuple(int(v.max()) + 1 for v in np.nonzero(blk)) for blk in dense if np.any(blk)]
     assert D == 4 and any(ea != eb for ea, eb in ext)
-    _assert_same_bits(run_device('well2', 'tme_1', N, 'central', ys), before)
+    ns.same_bits(run_device('well2', 'tme_1', N, 'central', ys), before)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # c. likelihood kinds and placement
 # ---------------------------------------------------------------------------------------------------------------------
 _P = {'gaussian': (0.2, 0.3), 'poisson': (1.0, 1.5), 'bernoulli': (2.0, 3.0)}
-_KIND = {'gaussian': 'gaussian', 'poisson': 'poisson_softplus', 'bernoulli': 'bernoulli_logistic'}
 
 
 def placement(kind, where):
@@ -256,8 +250,8 @@ def placement(kind, where):
 def test_likelihood_kinds_and_placement(kind, where, N):
     """Each factor reads its own component and y column (fac_component / fac_ycol): lv2, TME-2, central."""
     spec = placement(kind, where)
-    traced = filtering._trace_likelihood(em.factor_pdfs(spec)[0], 2)
-    assert [(f.kind, f.component, f.ycol) for f in traced] == [(_KIND[k], j, c) for k, j, c, _ in spec]
+    traced = filtering._trace_likelihood(ns.factor_pdfs(spec)[0], 2)
+    assert [(f.kind, f.component, f.ycol) for f in traced] == [(ns.KIND_NAMES[k], j, c) for k, j, c, _ in spec]
     # (seed 105 at N = 5: the oracle itself poisons with the 0.2-sd Gaussian factor on x_1; seed 1 is admitted for all twelve)
     check_case('lv2', 'tme_2', N, 'central', spec, seed=103 if N == 3 else 1)
 
@@ -273,14 +267,14 @@ def test_exchanging_the_components_exchanges_the_outputs(mode, fam, N):
     1e-6 of one truth (the tensor rule chains the two components symmetrically, so both orders give the same rule in exact
     arithmetic)."""
     T, seed = steps(N), 100 + N
-    mi, _ = em.tables(N)
+    mi, inds = ns.tables(2, N)
     ok, what = em.admissible('lv2', fam, N, mode, T, seed)
     assert ok, what
     ys = em.measurements('lv2', 2, T, seed)
     rev = em.MODELS['lv2_rev']
     sig = 'multi-index' if fam in em.OPERATOR else 'index'
-    ref = em.run_oracle(mode, em.oracle_family('lv2_rev', fam, N), sig, em.factor_pdfs(rev.spec)[1], ys[0, :, ::-1], N,
-                        em.initial(mi, rev.mean0, rev.cov0))
+    ref = ns.run_oracle(mode, em.oracle_family('lv2_rev', fam, N), sig, ns.factor_pdfs(rev.spec)[1], ys[0, :, ::-1], mi, inds,
+                        ns.initial(mi, rev.mean0, rev.cov0))
     got = run_device('lv2_rev', fam, N, mode, np.ascontiguousarray(ys[:, :, ::-1]))
     assert_parity(got, 0, ref, N, f'lv2 exchanged {fam} N={N} {mode}')
     orig = run_device('lv2', fam, N, mode, ys)
@@ -290,7 +284,7 @@ def test_exchanging_the_components_exchanges_the_outputs(mode, fam, N):
         for k in ('mean', 'scale'):
             if k in got:
                 npt.assert_allclose(got[k][b], orig[k][b][:, ::-1], rtol=2 * RTOL)
-        _assert_moments(got['m'][b], orig['m'][b][:, idx], mi, 2 * RTOL)
+        ns.assert_moments(got['m'][b], orig['m'][b][:, idx], mi, 2 * RTOL)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -306,7 +300,7 @@ def test_stable_equals_plain_on_a_well_posed_input_and_matches_the_stable_oracle
     tests/test_gpu_stable.py) and meets the bar against oracle(..., stable=True).  Raw mode stops at N = 4: lv2's raw Gram
     matrices do not pass the admission condition above it."""
     T, seed = steps(N), 100 + N
-    mi, _ = em.tables(N)
+    mi, _ = ns.tables(2, N)
     ys = em.measurements('lv2', 2, T, seed)
     got = check_case('lv2', 'tme_2', N, mode, stable=True)
     plain = run_device('lv2', 'tme_2', N, mode, ys)
@@ -316,7 +310,7 @@ def test_stable_equals_plain_on_a_well_posed_input_and_matches_the_stable_oracle
         if k in got:
             npt.assert_allclose(got[k], plain[k], rtol=1e-9)
     for b in range(2):
-        _assert_moments(got['m'][b], plain['m'][b], mi, 1e-9)
+        ns.assert_moments(got['m'][b], plain['m'][b], mi, 1e-9)
 
 
 def test_stable_completes_an_indefinite_start_in_scaled_mode():
@@ -330,9 +324,9 @@ def test_stable_completes_an_indefinite_start_in_scaled_mode():
     single entries moved; N = 2, 3; lv2, lin2, well2; tried on the CPU) are not: the oracle's own completed scaled run loses
     the replicate within two steps or goes on from a scale of 1e-10 that is a rounding residue."""
     N, T = 3, 20
-    mi, inds = em.tables(N)
+    mi, inds = ns.tables(2, N)
     m = em.MODELS['lv2']
-    st = em.initial(mi, m.mean0, m.cov0)
+    st = ns.initial(mi, m.mean0, m.cov0)
     st['scms'] = st['scms'].copy()
     st['scms'][mi.sum(axis=1) == 4] *= 0.5 - 1e-10
     _, dpiv = o1.ldl(st['scms'][inds[0]])
@@ -342,9 +336,9 @@ def test_stable_completes_an_indefinite_start_in_scaled_mode():
     assert np.all(plain['fn'] == 0) and np.all(np.isnan(plain['nell']))
     got = run_device('lv2', 'tme_2', N, 'scaled', ys, st=st, stable=True)
     for b in range(2):
-        ref = em.run_oracle('scaled', em.oracle_family('lv2', 'tme_2', N), 'multi-index', em.factor_pdfs(m.spec)[1], ys[b], N, st,
+        ref = ns.run_oracle('scaled', em.oracle_family('lv2', 'tme_2', N), 'multi-index', ns.factor_pdfs(m.spec)[1], ys[b], mi, inds, st,
                             stable=True)
-        assert em.all_finite(ref) and ref['scale'].min() > 0.03, 'chosen on the CPU: the completed oracle run stays finite and sane'
+        assert ns.all_finite(ref) and ref['scale'].min() > 0.03, 'chosen on the CPU: the completed oracle run stays finite and sane'
         print(f'PARITY lv2 indefinite start b={b}: first NaN {got["fn"][b]} ' +
               ' '.join(f'{k}={rel(got[k][b], ref[k]):.2e}' for k in ('nell', 'mean', 'scale')))
         assert got['fn'][b] == -1
@@ -364,12 +358,12 @@ def _pairwise_different(v):
 def test_per_replicate_tables_against_their_own_oracle_runs(mode):
     """batch_closures over three (A, sigma) points of lv2: replicate b runs tables b."""
     N, T, B = 3, 15, 3
-    mi, inds = em.tables(N)
+    mi, inds = ns.tables(2, N)
     m = em.MODELS['lv2']
     per = [em.host_family(f'lv2_b{b}', 'tme_2', N)[0] for b in range(B)]
     ys = np.stack([em.measurements(f'lv2_b{b}', b + 1, T, 31)[b] for b in range(B)])
-    st = em.initial(mi, m.mean0, m.cov0)
-    got = device(mode, moments.batch_closures(per), 'multi-index', em.factor_pdfs(m.spec)[0], ys, mi, inds, st)
+    st = ns.initial(mi, m.mean0, m.cov0)
+    got = ns.run_device(mode, moments.batch_closures(per), 'multi-index', ns.factor_pdfs(m.spec)[0], ys, mi, inds, st)
     assert _pairwise_different(got['nell'])
     for b in range(B):
         ok, what = em.admissible(f'lv2_b{b}', 'tme_2', N, mode, T, 31, b)
@@ -382,7 +376,7 @@ def test_per_replicate_likelihood_parameters_and_initial_laws_against_their_own_
     """A Gaussian factor with a per-replicate sd and a Bernoulli factor with a per-replicate offset (lik_batched), then
     per-replicate m0 / mean0 / scale0: each replicate against the oracle's run of its own parameters."""
     N, T, B = 3, 15, 3
-    mi, inds = em.tables(N)
+    mi, inds = ns.tables(2, N)
     m = em.MODELS['lv2']
     fns, sig = em.host_family('lv2', 'tme_2', N)
     ofns = em.oracle_family('lv2', 'tme_2', N)
@@ -392,27 +386,27 @@ def test_per_replicate_likelihood_parameters_and_initial_laws_against_their_own_
         return lambda y, x: stats.norm_pdf(y[0], x[0], sd) * stats.bernoulli_pmf(y[1], 1. / (1. + sym.exp(-(x[1] * 2.) + c)))
 
     def opdf_of(sd, c):
-        return lambda y, x: float(em.om.norm_pdf(y[0], x[0], sd) * em.om.bernoulli_pmf(y[1], 1. / (1. + np.exp(-(x[1] * 2.) + c))))
+        return lambda y, x: float(om.norm_pdf(y[0], x[0], sd) * om.bernoulli_pmf(y[1], 1. / (1. + np.exp(-(x[1] * 2.) + c))))
 
     model, _ = filtering._model_struct(fns[0].tables, filtering._trace_likelihood(pdf_of(sds, offs), 2), B)
     assert model.lik_batched == 1
     ys = em.measurements('lv2', B, T, 41, (('gaussian', 0, 0, 0.2), ('bernoulli', 1, 1, 2.0)))
-    st = em.initial(mi, m.mean0, m.cov0)
-    got = device(mode, fns, sig, pdf_of(sds, offs), ys, mi, inds, st)
+    st = ns.initial(mi, m.mean0, m.cov0)
+    got = ns.run_device(mode, fns, sig, pdf_of(sds, offs), ys, mi, inds, st)
     assert _pairwise_different(got['nell'])
     for b in range(B):
-        ref = em.run_oracle(mode, ofns, sig, opdf_of(float(sds[b]), float(offs[b])), ys[b], N, st)
-        admit(mode, ref, lambda: em.run_oracle('central', ofns, sig, opdf_of(float(sds[b]), float(offs[b])), ys[b], N, st))
+        ref = ns.run_oracle(mode, ofns, sig, opdf_of(float(sds[b]), float(offs[b])), ys[b], mi, inds, st)
+        admit(mode, ref, lambda: ns.run_oracle('central', ofns, sig, opdf_of(float(sds[b]), float(offs[b])), ys[b], mi, inds, st))
         assert_parity(got, b, ref, N, f'lv2 likelihood parameters {b} {mode}')
     shifts = np.array([[0., 0.], [0.1, -0.05], [-0.1, 0.1]])
-    states = [em.initial(mi, m.mean0 + shifts[b], m.cov0 * f) for b, f in enumerate((1., 1.5, 0.7))]
-    pdf, opdf = em.factor_pdfs(m.spec)
+    states = [ns.initial(mi, m.mean0 + shifts[b], m.cov0 * f) for b, f in enumerate((1., 1.5, 0.7))]
+    pdf, opdf = ns.factor_pdfs(m.spec)
     ys = em.measurements('lv2', B, T, 43)
-    got = device(mode, fns, sig, pdf, ys, mi, inds, stack_initial(states))
+    got = ns.run_device(mode, fns, sig, pdf, ys, mi, inds, ns.stack_initial(states))
     assert _pairwise_different(got['nell'])
     for b in range(B):
-        ref = em.run_oracle(mode, ofns, sig, opdf, ys[b], N, states[b])
-        admit(mode, ref, lambda: em.run_oracle('central', ofns, sig, opdf, ys[b], N, states[b]))
+        ref = ns.run_oracle(mode, ofns, sig, opdf, ys[b], mi, inds, states[b])
+        admit(mode, ref, lambda: ns.run_oracle('central', ofns, sig, opdf, ys[b], mi, inds, states[b]))
         assert_parity(got, b, ref, N, f'lv2 initial law {b} {mode}')
 
 
@@ -426,10 +420,10 @@ def test_a_replicate_alone_has_the_bits_it_has_in_a_batch_and_calls_repeat(mode,
     T, B = 12, 3
     ys = em.measurements('lv2', B, T, 51)
     got = run_device('lv2', 'tme_2', N, mode, ys)
-    _assert_same_bits(run_device('lv2', 'tme_2', N, mode, ys), got)
+    ns.same_bits(run_device('lv2', 'tme_2', N, mode, ys), got)
     for b in range(B):
         one = run_device('lv2', 'tme_2', N, mode, ys[b:b + 1])
-        _assert_same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
+        ns.same_bits({k: v[b:b + 1] for k, v in got.items()}, one)
 
 
 @pytest.mark.parametrize('fam', ['tme_3', 'tme_normal_2'])
@@ -442,15 +436,15 @@ def test_chunked_launches_give_the_bits_of_one_launch(fam, monkeypatch):
     assert np.all(one['fn'] == -1)
     for chunks in (3, T):
         monkeypatch.setenv('MFS_HOST_CHUNKS', str(chunks))
-        _assert_same_bits(run_device('lv2', fam, N, 'scaled', ys), one)
+        ns.same_bits(run_device('lv2', fam, N, 'scaled', ys), one)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # h. the bearing likelihood
 # ---------------------------------------------------------------------------------------------------------------------
 def _bearing(N, T):
-    dt, _, xi, F, Q, means0, covs0, weights0, ys = _bearing_only_model(N)
-    mi, inds = em.tables(N)
+    dt, _, xi, F, Q, means0, covs0, weights0, ys = em.bearing_only_model()
+    mi, inds = ns.tables(2, N)
     gs = omd.GaussianSumND.new(means0, covs0, weights0, mi)
     sd = math.sqrt(xi)
     pdf = lambda y, x: stats.norm_pdf(y, sym.arctan2(x[1], x[0]), sd)                                     # noqa: E731
@@ -469,12 +463,12 @@ def test_bearing_likelihood_on_the_joint_kernels_and_the_normal_closure(N):
     fns, sig = em.host_family('cv2', 'tme_2', N)
     if N in BEARING_OPERATOR_N:
         assert kernel_of(fns, sig, pdf, N) == (N, 3)
-        ref = em.run_oracle('central', em.oracle_family('cv2', 'tme_2', N), sig, opdf, ys[1], N, st)
-        got = device('central', fns, sig, pdf, ys, mi, inds, st)
+        ref = ns.run_oracle('central', em.oracle_family('cv2', 'tme_2', N), sig, opdf, ys[1], mi, inds, st)
+        got = ns.run_device('central', fns, sig, pdf, ys, mi, inds, st)
         assert_parity(got, 1, ref, N, f'bearing tme_2 N={N} central')
     else:
         with pytest.raises(_lib.MfsError, match=r'error -2: a likelihood of both state components'):
-            device('central', fns, sig, pdf, ys, mi, inds, st)
+            ns.run_device('central', fns, sig, pdf, ys, mi, inds, st)
     lg = moments.cond_moments_linear_gaussian(F, Q, mi)
     if N <= 4:      # the notebook's closures: Kan moments of N(F x - mean, Q) per node
         ocms = lambda x, index, mean: np.array([[omd.raw_moments_mvn_kan(F @ xi_ - mean, Q, mi[i]) for i in index]   # noqa: E731
@@ -482,8 +476,8 @@ def test_bearing_likelihood_on_the_joint_kernels_and_the_normal_closure(N):
         ofns = (None, ocms, None, lambda x: x @ F.T, None)
     else:
         ofns = lg
-    ref = em.run_oracle('central', ofns, 'index', opdf, ys[1], N, st)
-    got = device('central', lg, 'index', pdf, ys, mi, inds, st)
+    ref = ns.run_oracle('central', ofns, 'index', opdf, ys[1], mi, inds, st)
+    got = ns.run_device('central', lg, 'index', pdf, ys, mi, inds, st)
     assert_parity(got, 1, ref, N, f'bearing linear_gaussian N={N} central')
 
 

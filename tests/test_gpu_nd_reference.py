@@ -6,17 +6,21 @@ reference uses TME-3 with the 'multi-index' closure the device's operator path t
 under test does not depend on the order.  Every device result is also compared with the oracle.
 """
 import math
+import os
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import stats, synth
-from mfs_amd.multi_dims import filtering, moments
+from mfs_amd import stats, sym, synth
+from mfs_amd.multi_dims import filtering, moments, ss_models
 from mfs_amd.multi_dims.moments import raw_moments_mvn_kan, central_moments_mvn_kan, marginalise_moments
 from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from mfs_amd.one_dim import filtering as f1, moments as m1
-from oracle import multi_dims as omd, one_dim as o, tme_sympy, models as om
+from mfs_amd.utils import GaussianSumND
+from oracle import models as om, multi_dims as omd, parity, tme_sympy
+from tests.nd_envelope_models import bearing_only_model
+from tests.nd_support import tables
 
 pytestmark = pytest.mark.gpu
 
@@ -105,8 +109,7 @@ def test_independent_2d_reduces_to_two_1d_filters_and_d1_is_the_1d_filter():
     rms0_1d = np.array([float(m1.raw_moment_of_normal(m0, var0, p)) for p in range(2 * N)])
     rmss_1d, nell_1d = f1.moment_filter_rms(f1d[0], measurement_cond_pdf, rms0_1d, ys)
     d = 2
-    mi = generate_graded_lexico_multi_indices(d, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, d)
+    mi, inds = tables(d, N)
     fnd = moments.sde_cond_moments_tme(drift, dispersion_2d, dt, order)
     rms0 = np.array([raw_moments_mvn_kan(m0 * np.ones(d), var0 * np.eye(d), m) for m in mi])
     rmss_2d, nell_2d = filtering.moment_filter_nd_rms((fnd[0], 'multi-index'), measurement_cond_pdf_2d, ys_2d, (mi, inds),
@@ -150,11 +153,8 @@ def test_independent_2d_reduces_to_two_1d_filters_and_d1_is_the_1d_filter():
 def test_per_replicate_parameters_on_the_nd_path():
     """theta per replicate (BASELINE config 4's grid carried to d = 2): batched transition tables and batched likelihood
     parameters give, replicate by replicate, the bits of the single-theta runs."""
-    from mfs_amd import sym
-    from mfs_amd.multi_dims import ss_models
     N, Tn = 3, 40
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
+    mi, inds = tables(2, N)
     pdt, _, _, gs, pdrift, pdisp, _, ppmf, _ = ss_models.prey_predator(mi)
     sig = np.array([0.05, 0.1, 0.2])
     off = np.array([1.0, 0.5, 1.5])
@@ -192,8 +192,7 @@ def test_narrow_likelihood_takes_the_checked_fallback(monkeypatch):
     T2 = 25
     ys_2d = 0.1 + 0.05 * np.random.randn(T2, 2)
     d, N, order, m0, var0 = 2, 3, 2, 0.1, 0.2
-    mi = generate_graded_lexico_multi_indices(d, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, d)
+    mi, inds = tables(d, N)
     fnd = moments.sde_cond_moments_tme(drift, dispersion_2d, dt, order)
     cms0 = np.array([central_moments_mvn_kan(var0 * np.eye(d), m) for m in mi])
     mean0 = m0 * np.ones(d)
@@ -230,8 +229,7 @@ def test_two_measurements_of_one_component():
     T2 = 30
     ys_2d = 0.2 + np.random.randn(T2, 2)
     d, N, order, m0, var0 = 2, 3, 2, 0.1, 0.2
-    mi = generate_graded_lexico_multi_indices(d, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, d)
+    mi, inds = tables(d, N)
     fnd = moments.sde_cond_moments_tme(drift, dispersion_2d, dt, order)
     cms0 = np.array([central_moments_mvn_kan(var0 * np.eye(d), m) for m in mi])
     mean0 = m0 * np.ones(d)
@@ -255,8 +253,7 @@ def test_nan_measurement_poisons_the_nd_replicate_from_that_step():
     and the replicate is NaN from that step on (first_nan says which); the other replicate of the batch is untouched."""
     ys, ys_2d = _measurements()
     d, N, order, m0, var0 = 2, 3, 2, 0.1, 0.2
-    mi = generate_graded_lexico_multi_indices(d, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, d)
+    mi, inds = tables(d, N)
     fnd = moments.sde_cond_moments_tme(drift, dispersion_2d, dt, order)
     cms0 = np.array([central_moments_mvn_kan(var0 * np.eye(d), m) for m in mi])
     mean0 = m0 * np.ones(d)
@@ -269,44 +266,15 @@ def test_nan_measurement_poisons_the_nd_replicate_from_that_step():
     npt.assert_array_equal(m[0, :13], m[1, :13])
 
 
-def _bearing_only_model(N):
-    """/root/reference/examples/2d_bearing_only.ipynb cells 3-7: constant-velocity LTI model discretised exactly, Gaussian-sum
-    start, y_k = atan2(x_1, x_0) + sqrt(0.1) noise."""
-    import scipy.linalg
-    dt, T, xi = 0.01, 100, 0.1
-    A = np.array([[0., 1.], [0., 0.]])
-    Bm = np.array([[0., 0.], [0., 1.]])
-    # discretise_lti_sde (mfs/utils.py, Van Loan / Axelsson & Gustafsson 2015): F = expm(A dt), Q = int_0^dt e^{As} B B^T e^{A^T s} ds
-    blk = scipy.linalg.expm(np.block([[A, Bm @ Bm.T], [np.zeros((2, 2)), -A.T]]) * dt)
-    F = blk[:2, :2]
-    Q = blk[:2, 2:] @ F.T
-    means0 = np.array([[1., 0.], [1., 1.]])
-    covs0 = np.array([np.eye(2), np.eye(2)]) * 0.01
-    weights0 = np.array([0.7, 0.3])
-    rng = np.random.default_rng(999)
-    comp = rng.choice(2, p=weights0)
-    x = means0[comp] + 0.1 * rng.standard_normal(2)
-    cq = np.linalg.cholesky(Q)
-    ys = np.empty(T)
-    for k in range(T):
-        x = F @ x + cq @ rng.standard_normal(2)
-        ys[k] = np.arctan2(x[1], x[0]) + math.sqrt(xi) * rng.standard_normal()
-    return dt, T, xi, F, Q, means0, covs0, weights0, ys
-
-
 def test_bearing_only_example_runs_with_a_likelihood_of_both_components():
     """examples/2d_bearing_only.ipynb cell 7: `norm.pdf(y, arctan2(x[1], x[0]), sqrt(xi))` is not a product of one-component
     factors.  The reference evaluates any callable at the tensor-product nodes (mfs/multi_dims/filtering.py:263-275); the device
     does the same on its eigen-node route (both K_k diagonalised; MFS_ND_UPDATE=grid integrates over the Chebyshev grid of the
     Normal-closure prediction instead).  N = 4, T = 100 as in the notebook, against
     oracle.multi_dims.moment_filter_nd_cms with the notebook's closures (Kan moments of N(F x - mean, Q)); 1e-6 on NLL and means."""
-    import os
-    from mfs_amd import sym, stats
-    from mfs_amd.utils import GaussianSumND
     N = 4
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
-    dt, T, xi, F, Q, means0, covs0, weights0, ys = _bearing_only_model(N)
+    mi, inds = tables(2, N)
+    dt, T, xi, F, Q, means0, covs0, weights0, ys = bearing_only_model()
     gs = GaussianSumND.new(means0, covs0, weights0, mi)
     ogs = omd.GaussianSumND.new(means0, covs0, weights0, mi)
     fns = moments.cond_moments_linear_gaussian(F, Q, mi)
@@ -326,7 +294,6 @@ def test_bearing_only_example_runs_with_a_likelihood_of_both_components():
     assert np.isfinite(rc[2])
     npt.assert_allclose(nell, rc[2], rtol=1e-6)
     npt.assert_allclose(means, rc[1], rtol=1e-6, atol=1e-9)
-    from oracle import parity
     assert parity.rel_err(cmss, rc[0], parity.natural_magnitude_nd(rc[0], mi)).max() <= 1e-6
     # A/B: the Chebyshev grid of the prediction instead of the eigen-nodes (exact for polynomial integrands only: NLL and means
     # hold 1e-6, the odd high moments lose digits to the interpolation of the likelihood)
@@ -339,8 +306,7 @@ def test_bearing_only_example_runs_with_a_likelihood_of_both_components():
     npt.assert_allclose(me2, rc[1], rtol=1e-6, atol=1e-9)
     assert parity.rel_err(cm2, rc[0], parity.natural_magnitude_nd(rc[0], mi)).max() <= 1e-3
     # a joint factor with the TME-order-3 operator tables is refused (their tile has no room for the node tables)
-    from mfs_amd.multi_dims import ss_models as snd
-    dt2, _, _, gs2, drift, disp, _, _, _ = snd.prey_predator(mi)
+    dt2, _, _, gs2, drift, disp, _, _, _ = ss_models.prey_predator(mi)
     tme = moments.sde_cond_moments_tme(drift, disp, dt2, 3)
     with pytest.raises(Exception):
         filtering.moment_filter_nd_cms((tme[1], 'multi-index'), tme[3], pdf, ys, (mi, inds), gs2.cms, gs2.mean)
@@ -349,13 +315,9 @@ def test_bearing_only_example_runs_with_a_likelihood_of_both_components():
 def test_bearing_likelihood_with_an_operator_table_transition():
     """The same likelihood of both components with `sde_cond_moments_tme` (operator tables, 'multi-index' signature): the
     prey--predator dynamics observed through a noisy bearing.  N = 3, T = 40 against the oracle at 1e-6."""
-    from mfs_amd import sym, stats
-    from mfs_amd.multi_dims import ss_models as snd
-    from oracle import parity
     N, T = 3, 40
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
-    dt, _, _, gs, drift, disp, _, _, _ = snd.prey_predator(mi)
+    mi, inds = tables(2, N)
+    dt, _, _, gs, drift, disp, _, _, _ = ss_models.prey_predator(mi)
     _, _, ogs, odrift, odisp, _, _ = omd.prey_predator(mi)
     fns = moments.sde_cond_moments_tme(drift, disp, dt, 2)
     _, ocms, omean, _ = tme_sympy.sde_cond_moments_tme_nd(odrift, odisp, 2, dt, 2, mi)
@@ -379,9 +341,7 @@ def test_results_do_not_depend_on_the_batch_a_replicate_sits_in(family):
     come out bit for bit the same whether it is filtered alone, with a few others, or in a batch that fills every CU three
     times over."""
     N, Tn = 5, 25
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
-    from mfs_amd.multi_dims import ss_models
+    mi, inds = tables(2, N)
     pdt, _, _, gs, pdrift, pdisp, _, ppmf, _ = ss_models.prey_predator(mi)
     fns, sig = ((moments.sde_cond_moments_tme(pdrift, pdisp, pdt, 2), 'multi-index') if family == 'tme_2' else
                 (moments.sde_cond_moments_tme_normal(pdrift, pdisp, pdt, 2, mi), 'index'))

@@ -8,30 +8,14 @@ import pytest
 
 from mfs_amd import synth, sym
 from mfs_amd.multi_dims import filtering, moments, ss_models
-from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from oracle import multi_dims as omd, tme_sympy
+from tests.nd_support import assert_moments, tables
 
 pytestmark = pytest.mark.gpu
 
 
-def _assert_moments(got, ref, mi, rtol):
-    """Relative error per moment with the natural magnitude prod_k sigma_k^{n_k} as the floor of the denominator:
-    first-order central moments and odd moments of near-symmetric laws are rounding noise around zero."""
-    got, ref, mi = np.asarray(got), np.asarray(ref), np.asarray(mi)
-    assert np.array_equal(np.isnan(got), np.isnan(ref))
-    d = mi.shape[1]
-    second = [int(np.where((mi == 2 * np.eye(d, dtype=int)[k]).all(axis=1))[0][0]) for k in range(d)]
-    m2 = np.stack([np.abs(ref[:, second[k]]) for k in range(d)], axis=-1)          # (T, d): E[(x_k - c_k)^2] or E[x_k^2]
-    natural = np.prod(np.sqrt(m2)[:, None, :] ** mi[None, :, :], axis=-1)          # (T, z)
-    scale = np.maximum(np.abs(ref), natural * 1e-2 + 1e-300)
-    err = np.abs(got - ref) / scale
-    assert np.nanmax(err) <= rtol, f'max scaled error {np.nanmax(err):.3e} > {rtol}'
-
-
 def _setup(N, tme_order=2):
-    d = 2
-    mi = generate_graded_lexico_multi_indices(d, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, d)
+    mi, inds = tables(2, N)
     dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
     fns = moments.sde_cond_moments_tme(drift, disp, dt, tme_order)
     _, _, ogs, odrift, odisp, _, opmf = omd.prey_predator(mi)
@@ -52,7 +36,7 @@ def test_prey_predator_central_and_raw(N, T, tme_order):
         rc = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], opmf, ys[b], (mi, inds), ogs.cms, ogs.mean)
         npt.assert_allclose(nell[b], rc[2], rtol=1e-6)
         npt.assert_allclose(means[b], rc[1], rtol=1e-6)
-        _assert_moments(cmss[b], rc[0], mi, rtol=1e-6)
+        assert_moments(cmss[b], rc[0], mi, rtol=1e-6)
         if N <= 4:
             rr = omd.moment_filter_nd_rms((ofns[0], 'multi-index'), opmf, ys[b], (mi, inds), ogs.rms)
             npt.assert_allclose(nell_r[b], rr[1], rtol=1e-6)
@@ -96,8 +80,7 @@ def test_nd_shapes_errors_and_single_trajectory():
 def test_prey_predator_normal_closures(N, T, order):
     """'index'-signature Normal closures (mfs/multi_dims/moments.py:257-411; used by dardel/prey_predator/mf.py with
     --trans=tme_normal_2 / euler; reference tests/test_filtering.py:182-222) against the oracle's Kan-formula path."""
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
+    mi, inds = tables(2, N)
     dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
     _, _, ogs, odrift, odisp, _, opmf = omd.prey_predator(mi)
     if order == 'euler':
@@ -111,7 +94,7 @@ def test_prey_predator_normal_closures(N, T, order):
     rc = omd.moment_filter_nd_cms((ocms, 'index'), omean, opmf, ys[0], (mi, inds), ogs.cms, ogs.mean)
     npt.assert_allclose(nell[0], rc[2], rtol=1e-6)
     npt.assert_allclose(means[0], rc[1], rtol=1e-6)
-    _assert_moments(cmss[0], rc[0], mi, rtol=1e-6)   # (N = 6 with TME-normal-3 needs the 34 x 34 Chebyshev grid: the largest the tables hold)
+    assert_moments(cmss[0], rc[0], mi, rtol=1e-6)   # (N = 6 with TME-normal-3 needs the 34 x 34 Chebyshev grid: the largest the tables hold)
     if N <= 3:
         rmss, nell_r = filtering.moment_filter_nd_rms((fns[0], 'index'), pmf, ys, (mi, inds), gs.rms)
         rr = omd.moment_filter_nd_rms((orms, 'index'), opmf, ys[0], (mi, inds), ogs.rms)
@@ -126,8 +109,7 @@ def test_prey_predator_normal_closures(N, T, order):
 def test_prey_predator_scaled_mode(N, T, family):
     """moment_filter_nd_scms (mfs/multi_dims/filtering.py:33-207) against the oracle, and the reference's own
     three-mode equivalence (tests/test_filtering.py:168-242: means of the scaled and central filters agree)."""
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
+    mi, inds = tables(2, N)
     dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
     _, _, ogs, odrift, odisp, _, opmf = omd.prey_predator(mi)
     if family == 'tme_2':
@@ -161,7 +143,7 @@ def test_prey_predator_scaled_mode(N, T, family):
     npt.assert_allclose(nell[0], rs[3], rtol=1e-6)
     npt.assert_allclose(means[0], rs[1], rtol=1e-6)
     npt.assert_allclose(scales[0], rs[2], rtol=1e-6)
-    _assert_moments(scmss[0], rs[0], mi, rtol=1e-6)
+    assert_moments(scmss[0], rs[0], mi, rtol=1e-6)
     with pytest.raises(sym.NotDeviceDescribable):   # the mean-only closure is not the mean-and-variance closure
         filtering.moment_filter_nd_scms((fns[2], sig), fns[3], pmf, ys, (mi, inds), scms0, gs.mean, scale0)
 
@@ -188,12 +170,12 @@ def test_update_by_eigen_decomposition_matches_chebyshev_route(N, T, family, mon
     npt.assert_allclose(eig[2], cheb[2], rtol=1e-9)
     npt.assert_allclose(eig[1], cheb[1], rtol=1e-9)
     for b in range(B):
-        _assert_moments(eig[0][b], cheb[0][b], mi, rtol=1e-6)
+        assert_moments(eig[0][b], cheb[0][b], mi, rtol=1e-6)
     if family == 'tme_2':
         rc = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], opmf, ys[0], (mi, inds), ogs.cms, ogs.mean)
         npt.assert_allclose(eig[2][0], rc[2], rtol=1e-6)
         npt.assert_allclose(eig[1][0], rc[1], rtol=1e-6)
-        _assert_moments(eig[0][0], rc[0], mi, rtol=1e-6)
+        assert_moments(eig[0][0], rc[0], mi, rtol=1e-6)
 
 
 def test_tme_order_3_scaled_mode_and_wide_table():
@@ -203,8 +185,8 @@ def test_tme_order_3_scaled_mode_and_wide_table():
     N, T, B = 3, 30, 2
     mi, inds, dt, gs, fns, pmf, ogs, ofns, opmf = _setup(N, 3)
     ys, _ = synth.prey_predator_batch(B, T, dt, seed=33)
-    tables = filtering._trace_transition((fns[1], 'multi-index'), 'central')
-    assert int(tables.kappas.sum(axis=1).max()) == 6 and tables.dense_table()[1] == 7
+    traced = filtering._trace_transition((fns[1], 'multi-index'), 'central')
+    assert int(traced.kappas.sum(axis=1).max()) == 6 and traced.dense_table()[1] == 7
     scale0 = np.sqrt(np.array([gs.cms[5], gs.cms[3]]))
     scms0 = gs.cms / np.prod(scale0 ** mi, axis=-1)
     scmss, means_s, scales, nell_s = filtering.moment_filter_nd_scms((fns[2], 'multi-index'), fns[4], pmf, ys, (mi, inds),
@@ -214,7 +196,7 @@ def test_tme_order_3_scaled_mode_and_wide_table():
     rc = omd.moment_filter_nd_cms((ofns[1], 'multi-index'), ofns[2], opmf, ys[0], (mi, inds), ogs.cms, ogs.mean)
     npt.assert_allclose(nell_c[0], rc[2], rtol=1e-6)
     npt.assert_allclose(means_c[0], rc[1], rtol=1e-6)
-    _assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
+    assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
     npt.assert_allclose(nell_s, nell_c, rtol=1e-6)
     npt.assert_allclose(means_s, means_c, rtol=1e-6)
     npt.assert_allclose(scales ** 2, np.stack([cmss[:, :, 5], cmss[:, :, 3]], axis=-1), rtol=1e-6)
@@ -226,8 +208,7 @@ def test_maximum_order_N7(family):
     own code paths: two elimination streams in the front end (3 s > 64 lanes), strided Jacobi rounds without the index table,
     gather indices from global memory.  Against the oracle, a few steps."""
     N, T, B = 7, 6, 2
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
+    mi, inds = tables(2, N)
     assert mi.shape[0] == 105 and inds.shape[1] == 28
     dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
     _, _, ogs, odrift, odisp, _, opmf = omd.prey_predator(mi)
@@ -244,7 +225,7 @@ def test_maximum_order_N7(family):
     rc = omd.moment_filter_nd_cms((ocms, sig), omean, opmf, ys[0], (mi, inds), ogs.cms, ogs.mean)
     npt.assert_allclose(nell[0], rc[2], rtol=1e-6)
     npt.assert_allclose(means[0], rc[1], rtol=1e-6)
-    _assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
+    assert_moments(cmss[0], rc[0], mi, rtol=1e-6)
 
 
 def test_nd_empty_batch_and_zero_steps():
@@ -263,8 +244,7 @@ def test_normal_closure_poisoning_is_per_replicate():
     """An indefinite start (negative variance) NaN-poisons that replicate at step 0 on the Normal-closure path too (its
     prediction runs on the Chebyshev grid: the rule's matrices are NaN, so are the grid weights), the neighbour is untouched."""
     N = 4
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
+    mi, inds = tables(2, N)
     dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
     fns = moments.sde_cond_moments_tme_normal(drift, disp, dt, 2, mi)
     ys, _ = synth.prey_predator_batch(2, 20, dt, seed=1)

@@ -13,13 +13,12 @@ replaced, never skipped).
 """
 import ctypes as C
 import functools
-import math
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import _lib, stats
+from mfs_amd import _lib
 from mfs_amd.classical_filters_smoothers import bootstrap_filter, gaussian_transition, stratified, systematic
 from mfs_amd.one_dim import ss_models
 from mfs_amd.one_dim.filtering import build_model_struct, _trace_likelihood
@@ -30,10 +29,6 @@ from tests import particle_filter_ref as P
 pytestmark = pytest.mark.gpu
 
 RESAMPLERS = {'stratified': stratified, 'systematic': systematic}
-
-
-def _gauss_pdf(y, x):
-    return stats.norm_pdf(y, x, math.sqrt(R.OU_R))
 
 
 def _assert_result_close(res, ref, n, what):
@@ -69,16 +64,10 @@ def test_stream_matches_the_restatement(tag, t):
 
 # ---- parity sweep: one particle, the wave (63, 64, 65), one block and its edge (1024, 1500), one cf segment and its edge
 # (4096, 5000).  Replicate b of a case has its own seed and measurements whatever B is, so its restatement is computed once.
-SWEEP_DT, SWEEP_T = 0.2, 12
+SWEEP_DT, SWEEP_T = P.SWEEP_DT, 12
 # n -> first seed where the default (1) leaves a target within 1.3 x the margin bound: seeds 1.. give 1.28 x the bound at
 # n = 5000 and 1.01 x at n = 20 000; these give 24 x and 3.2 x
 SWEEP_SEED0 = {5000: 21, 20000: 101}
-
-
-@functools.lru_cache(maxsize=None)
-def _sweep_model():
-    return (gaussian_transition(R.ou_drift, R.ou_dispersion, SWEEP_DT, 'tme-2'),
-            GaussianSum1D.new([0.], [R.OU_SIGMA ** 2], [1.]))
 
 
 def _sweep_seed(n, b):
@@ -87,9 +76,9 @@ def _sweep_seed(n, b):
 
 @functools.lru_cache(maxsize=None)
 def _sweep_replicate(n, b, resampling, T=SWEEP_T):
-    trans, init = _sweep_model()
+    trans, init = P.sweep_model()
     ys = R.ou_data(T, np.random.default_rng(1000 * n + b), SWEEP_DT)
-    ref = P.particle_filter_ref(lambda _: trans, lambda _: _gauss_pdf, ys[None, :], lambda _: init, [_sweep_seed(n, b)], n,
+    ref = P.particle_filter_ref(lambda _: trans, lambda _: P.gauss_pdf, ys[None, :], lambda _: init, [_sweep_seed(n, b)], n,
                                 resampling)
     return ys, ref
 
@@ -107,9 +96,9 @@ def _sweep_case(n, B, resampling, T=SWEEP_T):
 @pytest.mark.parametrize('B', [1, 3, 17])
 @pytest.mark.parametrize('n', [1, 2, 63, 64, 65, 257, 1024, 1500, 4096, 5000])
 def test_shape_sweep_against_restatement(n, B, resampling):
-    trans, init = _sweep_model()
+    trans, init = P.sweep_model()
     ys, seeds, ref = _sweep_case(n, B, resampling)
-    res = bootstrap_filter(trans, _gauss_pdf, ys, init, seeds, n, RESAMPLERS[resampling], return_summaries=True)
+    res = bootstrap_filter(trans, P.gauss_pdf, ys, init, seeds, n, RESAMPLERS[resampling], return_summaries=True)
     assert res.samples.shape == (B, SWEEP_T, n) and res.means.shape == (B, SWEEP_T) and res.cfs is None
     _assert_result_close(res, ref, n, f'n={n} B={B} {resampling}')
 
@@ -117,9 +106,9 @@ def test_shape_sweep_against_restatement(n, B, resampling):
 @pytest.mark.parametrize('resampling', ['stratified', 'systematic'])
 def test_twenty_thousand_particles_cross_workgroups(resampling):
     n, B, T = 20000, 2, 6
-    trans, init = _sweep_model()
+    trans, init = P.sweep_model()
     ys, seeds, ref = _sweep_case(n, B, resampling, T)
-    res = bootstrap_filter(trans, _gauss_pdf, ys, init, seeds, n, RESAMPLERS[resampling], return_summaries=True)
+    res = bootstrap_filter(trans, P.gauss_pdf, ys, init, seeds, n, RESAMPLERS[resampling], return_summaries=True)
     _assert_result_close(res, ref, n, f'n={n} B={B} {resampling}')
 
 
@@ -186,16 +175,16 @@ def test_well_poisson_per_replicate_parameters_explicit_initial_samples():
 # ---- invariances
 def test_outputs_are_reproducible_and_consistent():
     n, B = 1500, 3
-    trans, init = _sweep_model()
+    trans, init = P.sweep_model()
     ys, seeds, _ = _sweep_case(n, B, 'stratified')
     zs = np.linspace(-3., 3., 48)
-    args = (trans, _gauss_pdf, ys, init, seeds, n, stratified)
+    args = (trans, P.gauss_pdf, ys, init, seeds, n, stratified)
     full = bootstrap_filter(*args, zs=zs, return_summaries=True)
     again = bootstrap_filter(*args, zs=zs, return_summaries=True)
     for a, b in zip(full, again):
         assert np.array_equal(a, b), 'two identical calls differ'
     for b in range(B):
-        one = bootstrap_filter(trans, _gauss_pdf, ys[b], init, int(seeds[b]), n, stratified, zs=zs,
+        one = bootstrap_filter(trans, P.gauss_pdf, ys[b], init, int(seeds[b]), n, stratified, zs=zs,
                                return_summaries=True)
         for a, o in zip(full, one):
             assert np.array_equal(a[b], o), f'replicate {b} differs between the batch and a call of its own'
@@ -203,7 +192,7 @@ def test_outputs_are_reproducible_and_consistent():
     assert lean.samples is None
     for a, b in zip(full[1:], lean[1:]):
         assert np.array_equal(a, b), 'summaries depend on return_samples'
-    by_int = bootstrap_filter(trans, _gauss_pdf, ys, init, int(seeds[0]), n, stratified)      # seeds k, k + 1, ...
+    by_int = bootstrap_filter(trans, P.gauss_pdf, ys, init, int(seeds[0]), n, stratified)      # seeds k, k + 1, ...
     assert np.array_equal(by_int[0], full.samples) and np.array_equal(by_int[1], full.nell)
     means = full.samples.mean(axis=-1)
     variances = ((full.samples - means[..., None]) ** 2).mean(axis=-1)
@@ -216,13 +205,13 @@ def test_outputs_are_reproducible_and_consistent():
 
 def test_nan_poisons_one_replicate_only():
     n, B = 1500, 3
-    trans, init = _sweep_model()
+    trans, init = P.sweep_model()
     ys, seeds, _ = _sweep_case(n, B, 'stratified')
     zs = np.linspace(-1., 1., 8)
-    clean = bootstrap_filter(trans, _gauss_pdf, ys, init, seeds, n, zs=zs, return_summaries=True)
+    clean = bootstrap_filter(trans, P.gauss_pdf, ys, init, seeds, n, zs=zs, return_summaries=True)
     bad = ys.copy()
     bad[1, 4] = 1e6           # every weight underflows to zero
-    res = bootstrap_filter(trans, _gauss_pdf, bad, init, seeds, n, zs=zs, return_summaries=True)
+    res = bootstrap_filter(trans, P.gauss_pdf, bad, init, seeds, n, zs=zs, return_summaries=True)
     assert list(res.first_nan) == [-1, 4, -1] and list(clean.first_nan) == [-1, -1, -1]
     for name in ('samples', 'means', 'variances', 'cfs'):
         out, ref = getattr(res, name), getattr(clean, name)
@@ -236,9 +225,9 @@ def test_nan_poisons_one_replicate_only():
 # ---- error codes of the C entry
 def test_argument_errors_are_codes_with_messages():
     L = _lib.lib()
-    trans, _ = _sweep_model()
+    trans, _ = P.sweep_model()
     n, T, B = 8, 3, 2
-    model, keep = build_model_struct(trans.tables, _trace_likelihood(_gauss_pdf), B)
+    model, keep = build_model_struct(trans.tables, _trace_likelihood(P.gauss_pdf), B)
     operator = _lib.MfsModel1d.from_buffer_copy(model)
     operator.trans_kind = _lib.TRANS['operator']
     good = dict(model=model, n=n, T=T, B=B, res=0, seeds=np.array([1, 2], dtype=np.uint64), n_mix=1, cumw=np.ones(1),
@@ -280,7 +269,7 @@ def test_kalman_pin_on_the_device(n):
     B = 4
     true_m, true_v, true_nell = R.kalman(ys)
     for resampling in (stratified, systematic):
-        res = bootstrap_filter(trans, _gauss_pdf, np.tile(ys, (B, 1)), init, 11, n, resampling, return_samples=False,
+        res = bootstrap_filter(trans, P.gauss_pdf, np.tile(ys, (B, 1)), init, 11, n, resampling, return_samples=False,
                                return_summaries=True)
         print(f'n={n} {resampling.name}: max |mean err| {np.abs(res.means - true_m).max():.3e}, max |nell err| '
               f'{np.abs(res.nell - true_nell).max():.3e}, max |variance err| {np.abs(res.variances - true_v).max():.3e}')

@@ -25,7 +25,7 @@ from mfs_amd.multi_dims.filtering import _model_struct, _trace_likelihood
 from mfs_amd.tme_poly_nd import BatchedTablesND, GaussianTablesND
 from tests import brute_force_ref as R
 from tests import particle_filter_nd_ref as P
-from tests import test_gpu_particle_filter as pf1d      # the 1-D filter's linear model, for the test of the shared step driver
+from tests import particle_filter_ref as P1                # the 1-D filter's linear model, for the test of the shared step driver
 
 pytestmark = pytest.mark.gpu
 
@@ -264,9 +264,9 @@ def test_split_timing_switch_leaves_the_results_alone(d, monkeypatch):
     n, B, T = 1500, 2, 3
     seeds = np.array([1, 2], dtype=np.uint64)
     if d == 1:
-        trans, init = pf1d._sweep_model()
-        ys = np.stack([R.ou_data(T, np.random.default_rng(b), pf1d.SWEEP_DT) for b in range(B)])
-        pdf = pf1d._gauss_pdf
+        trans, init = P1.sweep_model()
+        ys = np.stack([R.ou_data(T, np.random.default_rng(b), P1.SWEEP_DT) for b in range(B)])
+        pdf = P1.gauss_pdf
     else:
         trans, init, F, Q = _lin_model()
         ys = np.stack([P.lin_data(T, np.random.default_rng(b), F, Q) for b in range(B)])

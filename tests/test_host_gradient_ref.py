@@ -6,6 +6,9 @@ margin, and that is a statement about the C port alone: its values at the steps 
 1e-7 of max_p |g_ref| (truncation shrinks with h, rounding grows, so agreement over a decade bounds both).  Every case the
 device file runs is checked here; a case that misses the condition gets other measurements or a shorter run in
 gradient_ref._RUNS, never a wider bound."""
+import ast
+import os
+
 import numpy as np
 import pytest
 
@@ -46,8 +49,14 @@ def test_orders_without_a_rule_poison_in_the_first_step(case):
 
 
 def test_case_list_is_the_one_the_device_file_runs():
-    from tests import test_gpu_gradient_envelope as dev
-    assert dev.REFERENCE_CASES == G.ALL_CASES
+    """The device file is read, not imported (tests/test_host_test_layers.py): it must draw on each of the lists that make up
+    ALL_CASES."""
+    groups = ('EVERY_INSTANTIATION', 'MATRIX', 'BATCHING', 'GEOMETRY', 'LONG')
+    assert G.ALL_CASES == sum((getattr(G, g) for g in groups), [])
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'test_gpu_gradient_envelope.py')) as f:
+        used = {n.attr for n in ast.walk(ast.parse(f.read()))
+                if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == 'G'}
+    assert set(groups) <= used
     ids = [c.id for c in G.ALL_CASES + G.POISON_AT_START]
     assert len(set(ids)) == len(ids)
     assert {(c.N, c.P) for c in G.EVERY_INSTANTIATION} == {(N, P) for N in range(2, 17) for P in range(1, 5)}

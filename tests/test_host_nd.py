@@ -1,17 +1,19 @@
 """CPU-only checks of the N-D host side: multi-index tables against the golden tables generated from the reference,
 the N-D polynomial-ring TME generator against the oracle's SymPy differentiation, Kan moments, model tracing."""
-import os
-
 import math
+import os
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import _lib, sym, tme_poly_nd
+from mfs_amd import _lib, stats, sym, synth
 from mfs_amd.multi_dims import filtering, moments, multi_indices as mid, ss_models
+from mfs_amd.one_dim import moments as m1
+from mfs_amd.tme_poly_nd import PolyND, TransitionTablesND
 from mfs_amd.utils import GaussianSumND
 from oracle import multi_dims as omd, tme_sympy
+from tests import nd_envelope_models as em, nd_support as ns
 
 
 @pytest.mark.parametrize('N,d', [(3, 1), (3, 2), (4, 2), (5, 2), (6, 2), (2, 3), (3, 3)])
@@ -123,8 +125,6 @@ def test_nd_normal_closure_tables_match_kan_oracle(order):
 def test_product_likelihoods_vector_measurements_and_batching():
     """measurement_cond_pdf_2d of the reference (tests/test_filtering.py:44-46): prod(norm.pdf(y, x, sd)) on vector y, x
     traces to two Gaussian factors, one per component and measurement column; ys of shape (T, 2) / (B, T, 2)."""
-    import math
-    from mfs_amd import stats
     factors = filtering._trace_likelihood(lambda y, x: math.prod(stats.norm_pdf(y, x, 1.5)), 2)
     assert [(f.kind, f.component, f.ycol) for f in factors] == [('gaussian', 0, 0), ('gaussian', 1, 1)]
     npt.assert_allclose(factors[1].params, [1., 0., 2.25])
@@ -169,7 +169,6 @@ def test_product_likelihoods_vector_measurements_and_batching():
 def test_d1_family_has_the_same_tables_as_the_1d_factory():
     """d = 1: the N-D closure family reduces to the 1-D tables the 1-D kernels run (reference
     tests/test_filtering.py:304-329, tests/test_one_dim_moments.py:68-88: 1-D vs N-D factories bit-equal)."""
-    from mfs_amd.one_dim import moments as m1
     ell, sigma, dt = 1., 0.5, 1e-2
     nd = moments.sde_cond_moments_tme(lambda x: -x / ell, lambda _: math.sqrt(2) * sigma / math.sqrt(ell), dt, 3, d=1)
     one = m1.sde_cond_moments_tme(lambda x: -x / ell, lambda _: math.sqrt(2) * sigma / math.sqrt(ell), dt, 3)
@@ -188,10 +187,7 @@ def test_d1_family_has_the_same_tables_as_the_1d_factory():
 def test_tme_order_3_uses_the_long_table_layout():
     """TME order 3 has derivative terms up to |kappa| = 6: 27 operator rows + 2 variance rows, extent up to 7
     (include/mfs_hip.h: MFS_ND_TABLE_ROWS); order <= 2 keeps the 16-row layout."""
-    from mfs_amd import _lib
-    from mfs_amd.multi_dims import filtering, moments, ss_models
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices
-    mi = generate_graded_lexico_multi_indices(2, 5)
+    mi = mid.generate_graded_lexico_multi_indices(2, 5)
     dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
     lik = filtering._trace_likelihood(pmf, 2)
     for order, rows in ((2, _lib.ND_ROWS), (3, _lib.ND_ROWS_MAX)):
@@ -208,7 +204,6 @@ def test_tme_order_3_uses_the_long_table_layout():
 # the models of tests/nd_envelope_models.py: what tests/test_gpu_nd_envelope.py takes from the host side
 # ---------------------------------------------------------------------------------------------------------------------
 def _states(model, n=20):
-    from tests import nd_envelope_models as em
     m = em.MODELS[model]
     rng = np.random.default_rng(5)
     return m.mean0 + 2. * rng.standard_normal((n, 2)) * np.sqrt(np.diag(m.cov0)), m.mean0 + np.array([0.03, -0.02])
@@ -233,9 +228,8 @@ def test_envelope_model_tables_match_sympy(model, fam):
     """Host tables of lv2, lin2 and well2 against SymPy differentiation (oracle/tme_sympy.py) at the multi-indices of N = 4, which
     contain those of N = 3, at 20 random states: raw, central and scaled moments, mean and variance.  These closures are the
     oracle's transition at N = 5..7 in tests/test_gpu_nd_envelope.py."""
-    from tests import nd_envelope_models as em
-    mi, _ = em.tables(4)
-    assert np.array_equal(mi[:em.tables(3)[0].shape[0]], em.tables(3)[0])
+    mi, _ = ns.tables(2, 4)
+    assert np.array_equal(mi[:ns.tables(2, 3)[0].shape[0]], ns.tables(2, 3)[0])
     fns, sig = em.host_family(model, fam, 4)
     orms, ocms, oscms, omean, omean_var = em.sympy_family(model, fam, 4)
     x, c = _states(model)
@@ -253,8 +247,7 @@ def test_envelope_model_tables_match_sympy(model, fam):
 def test_bearing_example_closures_match_kan():
     """cond_moments_linear_gaussian against Kan moments of N(F x - mean, Q) per state, the closure of the bearing-only example;
     the oracle's transition at N = 5..7 in the bearing cases of tests/test_gpu_nd_envelope.py."""
-    from tests import nd_envelope_models as em
-    mi, _ = em.tables(4)
+    mi, _ = ns.tables(2, 4)
     F, Q = np.array([[1., 0.01], [0., 1.]]), np.array([[3.3e-7, 5e-5], [5e-5, 1e-2]])
     fns = moments.cond_moments_linear_gaussian(F, Q, mi)
     rng = np.random.default_rng(3)
@@ -267,7 +260,6 @@ def test_bearing_example_closures_match_kan():
 def _zeroed(tables, row):
     """The five closures of an operator table with one coefficient block zeroed: a derivative row, or (row >= n_terms) a
     variance row."""
-    from mfs_amd.tme_poly_nd import PolyND, TransitionTablesND
     Q, var = list(tables.Q), list(tables.var)
     zero = PolyND(np.float64(0.), 2)
     if row is not None and row < len(Q):
@@ -281,16 +273,14 @@ def _zeroed(tables, row):
 
 def _movement(a, b, mi):
     """How far run b is from run a: the largest of the relative NLL, mean, scale and floored moment differences (the floor of
-    tests/test_gpu_parity_nd.py::_assert_moments)."""
+    tests/nd_support.py::moment_err)."""
     if not all(np.all(np.isfinite(b[k])) for k in b):
         return np.inf
     out = [abs(a['nell'] - b['nell']) / abs(a['nell'])]
     for k in ('mean', 'scale'):
         if k in a:
             out.append(np.max(np.abs(a[k] - b[k]) / np.abs(a[k])))
-    second = [int(np.where((mi == 2 * np.eye(2, dtype=int)[k]).all(axis=1))[0][0]) for k in range(2)]
-    natural = np.prod(np.sqrt(np.abs(a['m'][:, second]))[:, None, :] ** mi[None, :, :], axis=-1)
-    out.append(np.max(np.abs(a['m'] - b['m']) / np.maximum(np.abs(a['m']), natural * 1e-2 + 1e-300)))
+    out.append(np.max(ns.moment_err(b['m'], a['m'], mi)))
     return float(max(out))
 
 
@@ -298,8 +288,7 @@ def _block_movements(tables, N, T, run):
     """Zero each non-empty block the filter reads at order N in turn -> {kappa or 'var_k': movement of the filter's outputs}.  A
     derivative row kappa is read when kappa <= n for a multi-index n of the table, i.e. |kappa| <= 2N - 1; the variance rows
     are read by scaled mode, which is the mode their zeroing runs in."""
-    from tests import nd_envelope_models as em
-    mi, _ = em.tables(N)
+    mi, _ = ns.tables(2, N)
     base = {mode: run(_zeroed(tables, None), mode) for mode in ('central', 'scaled')}
     out = {}
     for t, kap in enumerate(tables.kappas):
@@ -316,13 +305,12 @@ def test_every_block_of_the_lv2_tables_moves_the_filter(fam, N, T):
     NLL, a mean, a scale or a floored moment by at least 1e-5, 10 times the parity bar (lv2 as it stands: dt = 0.05,
     sigma = (0.1, 0.15); no parameter had to be moved).  At N = 3 the moments stop at degree 5, so no filter reads the seven
     |kappa| = 6 rows of the TME-3 table there: N = 4 is the run that holds them."""
-    from tests import nd_envelope_models as em
     m = em.MODELS['lv2']
-    mi, _ = em.tables(N)
+    mi, inds = ns.tables(2, N)
     tables = em.host_family('lv2', fam, N)[0][0].tables
     ys = em.measurements('lv2', 1, T, 100 + N)[0]
-    st, opdf = em.initial(mi, m.mean0, m.cov0), em.factor_pdfs(m.spec)[1]
-    moved = _block_movements(tables, N, T, lambda fns, mode: em.run_oracle(mode, fns, 'multi-index', opdf, ys, N, st))
+    st, opdf = ns.initial(mi, m.mean0, m.cov0), ns.factor_pdfs(m.spec)[1]
+    moved = _block_movements(tables, N, T, lambda fns, mode: ns.run_oracle(mode, fns, 'multi-index', opdf, ys, mi, inds, st))
     print(f'lv2 {fam} N={N}: ' + ', '.join(f'{k} {v:.1e}' for k, v in moved.items()))
     read = [tuple(int(v) for v in kap) for kap in tables.kappas if int(kap.sum()) <= 2 * N - 1]
     assert len(moved) == len(read) + 2
@@ -337,16 +325,14 @@ def test_prey_predator_block_movements_are_recorded(N, T):
     closes.  Printed, not required.  Measured: a zeroed |kappa| >= 5 row moves its filter by 1e-5 .. 1e-4 at N = 3 and by
     5e-5 .. 3e-3 at N = 4 (lv2: 7e-3 .. 6e-1 and 2.5e-2 .. 3.5e-1), so a row that is 1 % off sits at 1e-7 .. 3e-5, for most
     rows under the parity bar of 1e-6, where lv2 puts every row at 7e-5 or more."""
-    from mfs_amd import synth
-    from tests import nd_envelope_models as em
-    mi, inds = em.tables(N)
+    mi, inds = ns.tables(2, N)
     dt, _, _, gs, drift, disp, _, _, _ = ss_models.prey_predator(mi)
     _, _, ogs, _, _, _, opmf = omd.prey_predator(mi)
     ys, _ = synth.prey_predator_batch(1, T, dt, seed=3)
     st = {'cms': ogs.cms, 'mean': ogs.mean, 'scale': np.sqrt(np.diag(ogs.cov)),
           'scms': ogs.cms / np.prod(np.sqrt(np.diag(ogs.cov)) ** mi, axis=-1)}
     tables = moments.sde_cond_moments_tme(drift, disp, dt, 3)[0].tables
-    moved = _block_movements(tables, N, T, lambda fns, mode: em.run_oracle(mode, fns, 'multi-index', opmf, ys[0], N, st))
+    moved = _block_movements(tables, N, T, lambda fns, mode: ns.run_oracle(mode, fns, 'multi-index', opmf, ys[0], mi, inds, st))
     print(f'prey-predator tme_3 N={N}: ' + ', '.join(f'{k} {v:.1e}' for k, v in moved.items()))
     high = {k: v for k, v in moved.items() if isinstance(k, tuple) and sum(k) >= 5}
     print(f'|kappa| >= 5: {min(high.values()):.1e} .. {max(high.values()):.1e}; a row 1 % off moves the filter by 1 % of that')

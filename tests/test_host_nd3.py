@@ -13,27 +13,14 @@ from mfs_amd.multi_dims import filtering, moments
 from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from mfs_amd.tme_poly_nd import stein_moments_3d
 from oracle import multi_dims as omd, tme_sympy
+from tests.nd3_models import LV_DT, MODELS
+from tests.nd_support import host_disp, host_drift
 
 _HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'mfs_hip.h')
 
 
-def _lorenz(x):
-    """Lorenz-63 in units of 10 (x = X / 10): dx = (s (x1 - x0), x0 (r - 10 x2) - x1, 10 x0 x1 - b x2)."""
-    s, r, b = 10., 28., 8. / 3.
-    return np.array([s * (x[1] - x[0]), x[0] * (r - 10. * x[2]) - x[1], 10. * x[0] * x[1] - b * x[2]], dtype=object)
-
-
-def _lorenz_sympy(x):
-    s, r, b = 10., 28., 8. / 3.
-    return [s * (x[1] - x[0]), x[0] * (r - 10. * x[2]) - x[1], 10. * x[0] * x[1] - b * x[2]]
-
-
-def _disp(x):
-    return np.diag([0.1, 0.1, 0.1]).astype(object)
-
-
-def _disp_sympy(x):
-    return [[0.1, 0, 0], [0, 0.1, 0], [0, 0, 0.1]]
+LORENZ, LV = MODELS['lorenz'], MODELS['lv']
+_lorenz, _disp = host_drift(LORENZ), host_disp(LORENZ)      # the forms the host traces
 
 
 def test_stein_recursion_matches_kan():
@@ -57,7 +44,7 @@ def test_normal_closure_cond_moments_match_oracle(order):
         fns = moments.sde_cond_moments_euler_maruyama(_lorenz, _disp, dt, mi)
     else:
         fns = moments.sde_cond_moments_tme_normal(_lorenz, _disp, dt, order, mi)
-    _, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(_lorenz_sympy, _disp_sympy, 3, dt, order, mi)
+    _, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(LORENZ.drift, LORENZ.disp, 3, dt, order, mi)
     x = rng.normal(scale=0.5, size=(6, 3))
     c = rng.normal(scale=0.3, size=3)
     idx = np.arange(mi.shape[0])
@@ -69,17 +56,16 @@ def test_normal_closure_cond_moments_match_oracle(order):
 
 @pytest.mark.parametrize('order', ['euler', 2, 3])
 def test_lotka_volterra_normal_closures_match_kan(order):
-    """The host closures that tests/test_gpu_nd3_envelope.py hands the oracle for the Normal families, on the model with a
+    """The host closures that tests/nd3_models.py hands the oracle for the Normal families, on the model with a
     state-dependent dispersion (3-species Lotka--Volterra) and at TME order 3: against the oracle's per-node Kan moments."""
-    from .test_gpu_nd3_envelope import LV_DT, lv_model
     rng = np.random.default_rng(6)
     mi = generate_graded_lexico_multi_indices(3, 7)
-    m = lv_model()
+    drift, disp = host_drift(LV), host_disp(LV)
     if order == 'euler':
-        fns = moments.sde_cond_moments_euler_maruyama(m.drift, m.disp, LV_DT, mi)
+        fns = moments.sde_cond_moments_euler_maruyama(drift, disp, LV_DT, mi)
     else:
-        fns = moments.sde_cond_moments_tme_normal(m.drift, m.disp, LV_DT, order, mi)
-    _, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(m.odrift, m.odisp, 3, LV_DT, order, mi)
+        fns = moments.sde_cond_moments_tme_normal(drift, disp, LV_DT, order, mi)
+    _, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(LV.drift, LV.disp, 3, LV_DT, order, mi)
     x = 1. + rng.normal(scale=0.3, size=(6, 3))
     c = 1. + rng.normal(scale=0.1, size=3)
     idx = np.arange(mi.shape[0])
@@ -122,7 +108,7 @@ def test_operator_dense_table_matches_sympy():
                 ff = math.prod(math.perm(int(nn), int(k)) for nn, k in zip(n, kap))
                 v = v + Q[r] * ff * np.prod(dx ** (n - np.asarray(kap)), axis=-1)
         got[:, zi] = v
-    _, ocms, omean, omv = tme_sympy.sde_cond_moments_tme_nd(_lorenz_sympy, _disp_sympy, 3, dt, 2, mi)
+    _, ocms, omean, omv = tme_sympy.sde_cond_moments_tme_nd(LORENZ.drift, LORENZ.disp, 3, dt, 2, mi)
     want = ocms(x, mi, c)
     npt.assert_allclose(got, want, rtol=1e-9, atol=1e-12 * np.abs(want).max())
     # variance rows (scaled mode)

@@ -1,13 +1,11 @@
 """CPU-only checks of the particle filter: the random stream of include/mfs_hip.h as tests/particle_filter_ref.py restates it
 (Philox4x32-10 known answers, the uniform lattice), the restatement pinned to the exact Kalman filter, and the Python layer's
 argument handling (nothing here calls the device)."""
-import math
-
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import io, stats
+from mfs_amd import io
 from mfs_amd.classical_filters_smoothers import (bootstrap_filter, gaussian_transition, multinomial, stratified, systematic,
                                                  ParticleFilterResult)
 from mfs_amd.one_dim import ss_models
@@ -15,10 +13,6 @@ from mfs_amd.sym import NotDeviceDescribable
 from mfs_amd.utils import GaussianSum1D
 from tests import brute_force_ref as R
 from tests import particle_filter_ref as P
-
-
-def _gauss_pdf(y, x):
-    return stats.norm_pdf(y, x, math.sqrt(R.OU_R))
 
 
 # ---- the stream
@@ -62,7 +56,7 @@ def kalman_case():
 def test_restatement_matches_kalman(resampling):
     ys, trans, init = kalman_case()
     true_m, _, true_nell = R.kalman(ys)
-    _, means, _, _, nell, first_nan, _ = P.particle_filter_ref(lambda b: trans, lambda b: _gauss_pdf, ys[None, :],
+    _, means, _, _, nell, first_nan, _ = P.particle_filter_ref(lambda b: trans, lambda b: P.gauss_pdf, ys[None, :],
                                                                lambda b: init, [11], 10000, resampling)
     print(f'{resampling}: max |mean err| {np.abs(means[0] - true_m).max():.3e}, |nell err| {abs(nell[0] - true_nell):.3e}')
     npt.assert_allclose(means[0], true_m, atol=2e-1)
@@ -75,7 +69,7 @@ def test_restatement_nan_rule_and_margin():
     ys = np.stack([ys[:8], ys[:8]])
     ys[1, 3] = 1e6
     samples, means, variances, cfs, nell, first_nan, margin = P.particle_filter_ref(
-        lambda b: trans, lambda b: _gauss_pdf, ys, lambda b: init, [1, 1], 200, 'stratified', zs=np.linspace(-1., 1., 5))
+        lambda b: trans, lambda b: P.gauss_pdf, ys, lambda b: init, [1, 1], 200, 'stratified', zs=np.linspace(-1., 1., 5))
     assert list(first_nan) == [-1, 3] and np.isnan(nell[1]) and np.isfinite(nell[0])
     assert np.isnan(samples[1, 3:]).all() and np.isnan(cfs[1, 3:]).all() and np.isnan(means[1, 3:]).all()
     assert np.array_equal(samples[0, :3], samples[1, :3])          # same seed, same measurements up to the poisoned step
@@ -86,7 +80,7 @@ def test_restatement_nan_rule_and_margin():
 # ---- the Python layer: argument errors come before the library is touched
 def test_argument_errors():
     ys, trans, init = kalman_case()
-    ok = (trans, _gauss_pdf, ys[:5], init, 0, 100)
+    ok = (trans, P.gauss_pdf, ys[:5], init, 0, 100)
     with pytest.raises(NotImplementedError, match='multinomial'):
         bootstrap_filter(*ok, multinomial)
     with pytest.raises(NotImplementedError, match='sort'):
@@ -99,17 +93,17 @@ def test_argument_errors():
         with pytest.raises(ValueError, match='nsamples'):
             bootstrap_filter(*ok[:5], bad_n)
     with pytest.raises(ValueError, match='ys'):
-        bootstrap_filter(trans, _gauss_pdf, np.zeros((2, 3, 4)), init, 0, 100)
+        bootstrap_filter(trans, P.gauss_pdf, np.zeros((2, 3, 4)), init, 0, 100)
     with pytest.raises(ValueError, match='init'):
-        bootstrap_filter(trans, _gauss_pdf, ys[:5], np.zeros(99), 0, 100)
+        bootstrap_filter(trans, P.gauss_pdf, ys[:5], np.zeros(99), 0, 100)
     with pytest.raises(ValueError, match='init'):
-        bootstrap_filter(trans, _gauss_pdf, ys[:5], np.zeros((2, 100)), 0, 100)
+        bootstrap_filter(trans, P.gauss_pdf, ys[:5], np.zeros((2, 100)), 0, 100)
     with pytest.raises(ValueError, match='key'):
-        bootstrap_filter(trans, _gauss_pdf, np.zeros((3, 5)), init, np.arange(2, dtype=np.uint64), 100)
+        bootstrap_filter(trans, P.gauss_pdf, np.zeros((3, 5)), init, np.arange(2, dtype=np.uint64), 100)
     with pytest.raises(ValueError, match='key'):
-        bootstrap_filter(trans, _gauss_pdf, ys[:5], init, -1, 100)
+        bootstrap_filter(trans, P.gauss_pdf, ys[:5], init, -1, 100)
     with pytest.raises(ValueError, match='key'):
-        bootstrap_filter(trans, _gauss_pdf, ys[:5], init, np.array([0.5]), 100)
+        bootstrap_filter(trans, P.gauss_pdf, ys[:5], init, np.array([0.5]), 100)
     with pytest.raises(ValueError, match='zs'):
         bootstrap_filter(*ok, zs=np.zeros((2, 2)), return_summaries=True)
     with pytest.raises(ValueError, match='return_summaries'):
@@ -117,7 +111,7 @@ def test_argument_errors():
     with pytest.raises(ValueError, match='nothing to return'):
         bootstrap_filter(*ok, return_samples=False)
     with pytest.raises(ValueError, match='components'):
-        bootstrap_filter(trans, _gauss_pdf, ys[:5], GaussianSum1D.new(np.zeros(9), np.ones(9), np.full(9, 1 / 9)), 0, 100)
+        bootstrap_filter(trans, P.gauss_pdf, ys[:5], GaussianSum1D.new(np.zeros(9), np.ones(9), np.full(9, 1 / 9)), 0, 100)
     with pytest.raises(ValueError, match='method'):
         gaussian_transition(R.ou_drift, R.ou_dispersion, 1e-2, 'rk4')
     # per-replicate parameters without a replicate axis, or with the wrong batch
