@@ -22,8 +22,8 @@ import numpy as np
 import scipy.linalg
 import sympy as sp
 
-from mfs_amd.multi_dims import moments
-from oracle import tme_sympy
+from mfs_amd.multi_dims import moments, ss_models
+from oracle import multi_dims as omd, tme_sympy
 from tests.nd_support import all_finite, factor_pdfs, host_disp, host_drift, initial, run_oracle, tables
 
 OPERATOR = ('tme_1', 'tme_2', 'tme_3')
@@ -140,6 +140,42 @@ def oracle_family(model, fam, N):
     """The closures the oracle filter runs: SymPy tables for N <= 4; for N = 5..7 the host's NumPy closures, which
     tests/test_host_nd.py pins to SymPy at the multi-indices of N = 3, 4 (SymPy costs 10 .. 40 s per table at those orders)."""
     return sympy_family(model, fam, N) if N <= 4 else host_family(model, fam, N)[0]
+
+
+# ---- prey--predator (BASELINE config 5), for the N-D tests that live among the 1-D files -----------------------------------------
+class PreyPredator(NamedTuple):
+    mi: np.ndarray
+    inds: tuple
+    dt: float
+    gs: object             # the device's initial law (.cms, .mean); ogs: the oracle's
+    fns: tuple             # the five device closures of the family, of signature sig
+    sig: str
+    pmf: Callable
+    ogs: object
+    opmf: Callable
+
+
+@functools.lru_cache(maxsize=None)
+def prey_predator(N, family='tme_2'):
+    """The device's prey--predator model on tables(2, N) with the closures of 'tme_2' or 'tme_normal_2', and the oracle's
+    initial law and likelihood; shared, not to be written to."""
+    mi, inds = tables(2, N)
+    dt, _, _, gs, drift, disp, _, pmf, _ = ss_models.prey_predator(mi)
+    _, _, ogs, _, _, _, opmf = omd.prey_predator(mi)
+    if family == 'tme_2':
+        fns, sig = moments.sde_cond_moments_tme(drift, disp, dt, 2), 'multi-index'
+    else:
+        fns, sig = moments.sde_cond_moments_tme_normal(drift, disp, dt, 2, mi), 'index'
+    return PreyPredator(mi, inds, dt, gs, fns, sig, pmf, ogs, opmf)
+
+
+@functools.lru_cache(maxsize=None)
+def prey_predator_oracle(N, family='tme_2'):
+    """-> (cms, mean): the oracle's closures of the same family by SymPy differentiation (seconds for 'tme_2')."""
+    mi, _ = tables(2, N)
+    dt, _, _, odrift, odisp, _, _ = omd.prey_predator(mi)
+    derive = tme_sympy.sde_cond_moments_tme_nd if family == 'tme_2' else tme_sympy.sde_cond_moments_normal_nd
+    return derive(odrift, odisp, 2, dt, 2, mi)[1:3]
 
 
 def path(m, T, seed):

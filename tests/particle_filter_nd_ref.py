@@ -13,6 +13,7 @@ import math
 
 import numpy as np
 
+from mfs_amd import stats
 from mfs_amd.utils import GaussianSumND
 from tests.particle_filter_ref import draws, margin_bound, assert_close, philox4x32_10   # noqa: F401  (re-exported)
 
@@ -125,7 +126,6 @@ def lin_dispersion(x):
 
 
 def lin_pdf(y, x):
-    from mfs_amd import stats
     return stats.norm_pdf(y[0], x[0], LIN_SD) * stats.norm_pdf(y[1], x[1], LIN_SD)
 
 

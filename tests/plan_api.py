@@ -14,6 +14,7 @@ from mfs_amd import _lib, stats, synth
 from mfs_amd._lib import BUILD, TRAITS
 from mfs_amd.one_dim import filtering, moments, ss_models
 from mfs_amd.utils import GaussianSum1D
+from tests import one_dim_support
 
 
 # ---- results ------------------------------------------------------------------------------------------------------------
@@ -207,11 +208,8 @@ COMBOS = {'benes_tme3': TRAITS['central_tanh_bernoulli'], 'benes_tme_normal3': T
 def combo_model(combo, N, mode='central'):
     """(ic, tables, lik, dt) of one model in one moment mode; traced once per session."""
     if combo.startswith('benes'):
-        dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-        if combo == 'benes_tme3':
-            fns = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
-        else:
-            fns = moments.sde_cond_moments_tme_normal(drift, dispersion, dt, 3, N)
+        m = one_dim_support.benes(N, 'tme' if combo == 'benes_tme3' else 'tme_normal', 3)
+        dt, ic, fns, pmf = m.dt, m.ic, m.fns, m.pmf
     else:   # the OU / Gaussian workload of the benchmark's config 3
         dt, ell, sigma = 0.1, 1., 0.5
         F, Sigma = np.exp(-dt / ell), sigma ** 2 * (1 - np.exp(-2 * dt / ell))
@@ -229,21 +227,15 @@ def traced(combo, N):
     tables (4 operator terms), a specialised shape with run-time traits."""
     if combo != 'benes_tme2':
         return combo_model(combo, N)
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-    fns = moments.sde_cond_moments_tme(drift, dispersion, dt, 2)
-    tables, lik = filtering.trace_model('central', fns[1], fns[3], pmf)
+    dt, ic, tables, lik = benes(N, 'tme', 2)
     return ic, tables, lik, dt
 
 
 def benes(N, family, order):
     """(dt, ic, tables, lik) of Benes-Bernoulli in central mode with TME ('tme') or TME-normal ('tme_normal') tables."""
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-    if family == 'tme':
-        _, c, _, mu, _ = moments.sde_cond_moments_tme(drift, dispersion, dt, order)
-    else:
-        _, c, _, mu, _ = moments.sde_cond_moments_tme_normal(drift, dispersion, dt, order, N)
-    tables, lik = filtering.trace_model('central', c, mu, pmf)
-    return dt, ic, tables, lik
+    m = one_dim_support.benes(N, family, order)
+    tables, lik = filtering.trace_model('central', m.fns[1], m.fns[3], m.pmf)
+    return m.dt, m.ic, tables, lik
 
 
 def start(combo, N, nb):

@@ -7,7 +7,8 @@ import textwrap
 
 import numpy as np
 
-from mfs_amd import dist
+from mfs_amd import dist, synth
+from oracle import one_dim as o, models as om, tme_sympy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -75,8 +76,6 @@ def test_two_rank_sharding_and_allgather(tmp_path, kw, port):
     assert (r0[7], r0[8], r1[7], r1[8]) == (0, 3, 3, 5)     # contiguous block split
 
     # replicate order is preserved: compare with an unsharded evaluation
-    from mfs_amd import synth
-    from oracle import one_dim as o, models as om, tme_sympy
     N, T, B = 4, 25, 5
     odt, _, oic, odrift, odisp, _, opmf = om.benes_bernoulli(N)
     fns = tme_sympy.sde_cond_moments_tme_1d(odrift, odisp, odt, 2, 2 * N)

@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+from mfs_amd import _lib
 from tests import device_math_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -266,7 +267,6 @@ def test_probe_shapes_and_repeatability(n):
 
 
 def test_entry_error_codes():
-    from mfs_amd import _lib
     L = _lib.lib()
     x, out = np.zeros((60, 4)), np.zeros((4, 4))
 

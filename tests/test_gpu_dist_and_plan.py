@@ -10,6 +10,8 @@ import numpy.testing as npt
 import pytest
 
 from mfs_amd import _lib, synth, dist
+from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
+from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from mfs_amd.one_dim import filtering, moments, ss_models
 from tests.plan_api import CENTRAL_OUTPUTS, run_plan_1d, run_plan_nd
 
@@ -76,9 +78,6 @@ def test_rccl_single_rank_allgather():
 
 def test_nd_plan_device_pointers_match_host_entry():
     """mfs_plan_nd_* (data resident in HBM) runs the same kernel as mfs_filter_nd: bit-identical outputs."""
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
     N, T, B = 3, 30, 5
     mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
     inds = gram_and_hankel_indices_graded_lexico(N, 2)
@@ -171,9 +170,6 @@ def test_pipelined_nd_host_entry_is_bit_identical(monkeypatch, family, mode, rou
     start reads -- crosses the launches through a carry block, so every output has the bits of the single launch: operator
     path, scaled mode, Normal closure (warm-started Jacobi in the prediction) and the eigen-decomposition route of the
     update."""
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
     N, T, B = 4, 37, 5
     mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
     inds = gram_and_hankel_indices_graded_lexico(N, 2)
@@ -208,9 +204,6 @@ def test_host_entry_points_are_reentrant_across_threads():
     stream / event context and its own blocks from the (mutex-guarded) pool.  Four Python threads filter different batches
     at once, 1-D and N-D mixed; every result has the bits of the same call made alone."""
     import threading
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
     N = 8
     dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
     _, c, _, mu, _ = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)

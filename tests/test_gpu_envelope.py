@@ -23,40 +23,30 @@ import numpy.testing as npt
 import pytest
 
 from mfs_amd import synth
-from mfs_amd.one_dim import filtering, moments, ss_models
-from oracle import c_oracle, parity, tme_sympy, models as om
+from oracle import c_oracle, parity
+from tests.one_dim_support import benes, benes_operator_tables, load_golden, run_device
 
 pytestmark = pytest.mark.gpu
+N = 15
 
 
 def _load(golden_dir, name):
-    path = os.path.join(golden_dir, name)
-    if not os.path.exists(path):
-        pytest.fail(f'{name} is missing: see tests/golden/make_exact_golden.py / make_filter_golden.py')
-    return np.load(path)
+    return load_golden(golden_dir, name, 'see tests/golden/make_exact_golden.py / make_filter_golden.py')
 
 
-def _setup():
-    N = 15
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-    f = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
-    ys = synth.benes_bernoulli_batch(4096, 1000, dt, seed=100)[0]
-    odt, _, oic, odrift, odisp, _, _ = om.benes_bernoulli(N)
-    tab = tme_sympy.operator_tables_1d(odrift, odisp, odt, 3, 'tanh')      # SymPy derivation: independent of the product's tables
-    return N, ic, f, pmf, ys, oic, tab
+def _ys_full():
+    return synth.benes_bernoulli_batch(4096, 1000, benes(N).dt, seed=100)[0]
 
 
-def _device(mode, ic, f, pmf, ys):
-    if mode == 'central':
-        m, means, nell, fn = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys, return_first_nan=True)
-        return m, means, m[..., 2], nell, fn
-    m, means, scales, nell, fn = filtering.moment_filter_scms(f[2], f[4], pmf, ic.scms, ic.mean, math.sqrt(ic.variance), ys,
-                                                              return_first_nan=True)
-    return m, means, scales, nell, fn
+def _device(mode, ys):
+    """(moments, means, variances (central) or scales (scaled), nell, first_nan) of the headline model, TME-3."""
+    r = run_device(mode, benes(N), ys, return_first_nan=True)
+    return r._replace(scales=r.moments[..., 2]) if mode == 'central' else r
 
 
-def _cport(mode, N, oic, tab, ys):
-    lik = np.array([0., 0., 0., 0.2])
+def _cport(mode, ys):
+    # (the operator tables are SymPy's derivation: independent of the product's tables)
+    oic, tab, lik = benes(N).oic, benes_operator_tables(N), np.array([0., 0., 0., 0.2])
     if mode == 'central':
         cm, cmeans, _, cnell = c_oracle.filter_1d(1, N, ys, oic.cms, oic.mean, None, 0, 1, 6, tab, 1.0, 0, lik)
         return cm, cmeans, cm[..., 2], cnell
@@ -80,9 +70,8 @@ def _errors(mom_at_steps, means, second, nell, e, mode):
 def test_device_against_exact_arithmetic(golden_dir, mode):
     e = _load(golden_dir, 'filter_cfg2_exact.npz')
     g = _load(golden_dir, 'filter_cfg2.npz')
-    N, ic, f, pmf, ys_full, oic, tab = _setup()
     T, B = int(e['T']), int(e['B'])
-    ys = ys_full[:B, :T]
+    ys = _ys_full()[:B, :T]
     npt.assert_array_equal(np.packbits(ys.astype(np.uint8), axis=1), e['ys_bits'])
     assert np.all(e[f'{mode}_first_nan'] == -1), 'in exact arithmetic no replicate poisons'
     # 80 digits are enough: the 120-digit re-run of replicate 0 rounds to the same doubles
@@ -91,9 +80,9 @@ def test_device_against_exact_arithmetic(golden_dir, mode):
         npt.assert_array_equal(e['check120_means'], e['central_means'][0])
     steps = e['moment_steps']
     sec = 'variances' if mode == 'central' else 'scales'
-    m, means, second, nell, fn = _device(mode, ic, f, pmf, ys)
+    m, means, second, nell, fn = _device(mode, ys)
     dev = _errors(m[:, steps], means, second, nell, e, mode)
-    cm, cmeans, csecond, cnell = _cport(mode, N, oic, tab, ys)
+    cm, cmeans, csecond, cnell = _cport(mode, ys)
     cpo = _errors(cm[:, steps], cmeans, csecond, cnell, e, mode)
     ora = _errors(g[f'{mode}_moments'][:B], g[f'{mode}_means'][:B], g[f'{mode}_{sec}'][:B], g[f'{mode}_nell'][:B], e, mode)
     for name, err in (('device', dev), ('numpy/lapack', ora), ('c port', cpo)):
@@ -121,18 +110,17 @@ def test_device_against_exact_arithmetic_full_length(golden_dir):
     if not os.path.exists(path):
         pytest.skip('filter_cfg2_exact_T1000.npz not generated yet (tests/golden/make_exact_golden.py --T 1000 ...)')
     e = np.load(path)
-    N, ic, f, pmf, ys_full, oic, tab = _setup()
     T, B = int(e['T']), int(e['B'])
-    ys = ys_full[:B, :T]
+    ys = _ys_full()[:B, :T]
     npt.assert_array_equal(np.packbits(ys.astype(np.uint8), axis=1), e['ys_bits'])
     # (over 1000 steps cond(Hankel) outgrows even 80 digits for some replicates -- 1e80 where fp64 gave up at 1e16 hundreds
     #  of steps earlier; the arbiter's own horizon is recorded in the fixture and every fp64 run ends well before it)
     horizon = np.where(e['central_first_nan'] >= 0, e['central_first_nan'], T)
     steps = e['moment_steps']
-    m, means, second, nell, fn = _device('central', ic, f, pmf, ys)
+    m, means, second, nell, fn = _device('central', ys)
     assert np.all(np.where(fn >= 0, fn, T) <= horizon)
     dev = _errors(m[:, steps], means, second, nell, e, 'central')
-    cm, cmeans, csecond, cnell = _cport('central', N, oic, tab, ys)
+    cm, cmeans, csecond, cnell = _cport('central', ys)
     cpo = _errors(cm[:, steps], cmeans, csecond, cnell, e, 'central')
     for name, err in (('device', dev), ('c port', cpo)):
         print(f'T=1000 {name:8s}' + '  '.join(f'{k}: max {v.max():.1e} p99 {np.quantile(v, .99):.1e}' for k, v in err.items() if v.size))
@@ -149,12 +137,12 @@ def test_three_way_envelope_at_benchmark_size(golden_dir):
     """Device, NumPy/LAPACK (frozen: tests/golden/filter_cfg2env.npz) and the C port on the same 1024 replicates x 1000
     steps of the benchmark batch.  Pairwise: which replicates survive, where the others poison, NLL of common survivors."""
     g = _load(golden_dir, 'filter_cfg2env.npz')
-    N, ic, f, pmf, ys_full, oic, tab = _setup()
     T, B = int(g['T']), int(g['B'])
-    ys = ys_full[:B, :T]
+    ys = _ys_full()[:B, :T]
     npt.assert_array_equal(np.packbits(ys.astype(np.uint8), axis=1), g['ys_bits'])
-    m, means, second, nell, fn = _device('central', ic, f, pmf, ys)
-    _, cmeans, _, cnell = c_oracle.filter_1d(1, N, ys, oic.cms, oic.mean, None, 0, 1, 6, tab, 1.0, 0,
+    m, means, second, nell, fn = _device('central', ys)
+    oic = benes(N).oic
+    _, cmeans, _, cnell = c_oracle.filter_1d(1, N, ys, oic.cms, oic.mean, None, 0, 1, 6, benes_operator_tables(N), 1.0, 0,
                                              np.array([0., 0., 0., 0.2]), want_moments=False)
     first = {'device': np.where(fn >= 0, fn, T), 'numpy': np.where(g['central_first_nan'] >= 0, g['central_first_nan'], T),
              'cport': parity.first_nan_steps(cmeans[..., None], T)}
@@ -201,29 +189,27 @@ def test_predict_rule_from_posterior_atoms_vs_recomputed(golden_dir, monkeypatch
     3.2e-11, mean 1.2e-9 / 2.2e-9, variance 7.8e-9 / 1.8e-8, moments 1.0e-7 / 6.5e-8 for atoms / recomputed, with 17 / 15 of the 24
     replicates surviving 300 steps; in exact arithmetic all do)."""
     # (i)
-    for N, T in ((7, 100), (10, 100)):
-        dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-        f = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
-        ys = synth.benes_bernoulli_batch(16, T, dt, seed=5 + N)[0]
-        a = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys)
+    for n, T in ((7, 100), (10, 100)):
+        model = benes(n)
+        ys = synth.benes_bernoulli_batch(16, T, model.dt, seed=5 + n)[0]
+        a = run_device('central', model, ys)
         monkeypatch.setenv('MFS_PREDICT_RULE', 'recompute')
-        r = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys)
+        r = run_device('central', model, ys)
         monkeypatch.delenv('MFS_PREDICT_RULE')
-        assert np.all(np.isfinite(a[2])) and np.all(np.isfinite(r[2]))
-        npt.assert_allclose(a[2], r[2], rtol=1e-9)
-        npt.assert_allclose(a[1], r[1], rtol=1e-9, atol=1e-12)
-        err = parity.rel_err(a[0], r[0], parity.moment_floor(r[0]))
-        assert np.nanmax(err) <= (1e-9 if N == 7 else 1e-7), np.nanmax(err)
+        assert np.all(np.isfinite(a.nell)) and np.all(np.isfinite(r.nell))
+        npt.assert_allclose(a.nell, r.nell, rtol=1e-9)
+        npt.assert_allclose(a.means, r.means, rtol=1e-9, atol=1e-12)
+        err = parity.rel_err(a.moments, r.moments, parity.moment_floor(r.moments))
+        assert np.nanmax(err) <= (1e-9 if n == 7 else 1e-7), np.nanmax(err)
     # (ii)
     e = _load(golden_dir, 'filter_cfg2_exact.npz')
-    N, ic, f, pmf, ys_full, oic, tab = _setup()
     T, B = int(e['T']), int(e['B'])
-    ys, steps = ys_full[:B, :T], e['moment_steps']
+    ys, steps = _ys_full()[:B, :T], e['moment_steps']
     worst = {}
     for route in ('atoms', 'recompute'):
         if route == 'recompute':
             monkeypatch.setenv('MFS_PREDICT_RULE', 'recompute')
-        m, means, second, nell, fn = _device('central', ic, f, pmf, ys)
+        m, means, second, nell, fn = _device('central', ys)
         if route == 'recompute':
             monkeypatch.delenv('MFS_PREDICT_RULE')
         survivors = int((fn < 0).sum())                     # (in exact arithmetic all 24 survive; in fp64 about two thirds)

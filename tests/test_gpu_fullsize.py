@@ -2,40 +2,29 @@
 4e6 filter-steps in seconds): exact Kalman agreement (config 3), NaN-poisoning structure, normalisation invariants,
 replicate-order invariance, survivors' NLL against the C port on a sample (config 2), NLL grid consistency (config 4)."""
 import math
+import os
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import synth, stats
-from mfs_amd.one_dim import filtering, moments, ss_models
-from oracle import c_oracle, tme_sympy, models as om
+from mfs_amd import synth
+from mfs_amd.multi_dims import filtering as fnd
+from mfs_amd.one_dim import filtering
+from oracle import c_oracle, parity
+from tests.nd_envelope_models import prey_predator
+from tests.one_dim_support import assert_poisoned_after, benes, benes_operator_tables, ou_gaussian, run_device, well
 
 pytestmark = pytest.mark.gpu
-
-
-def _check_poison_structure(m, means, nell, first_nan, T):
-    """first_nan >= 0  <=>  nell is NaN; before first_nan everything is finite, from it on everything is NaN."""
-    dead = first_nan >= 0
-    assert np.array_equal(np.isnan(nell), dead)
-    fin = np.isfinite(means)
-    t = np.arange(T)[None, :]
-    expect_fin = np.where(dead[:, None], t < first_nan[:, None], True)
-    # the poisoned step itself may hold a mixture; everything strictly before is finite, strictly after is NaN
-    assert np.all(fin[expect_fin])
-    after = np.where(dead[:, None], t > first_nan[:, None], False)
-    assert not np.any(fin[after])
-    assert np.all(np.isnan(m[after]))
 
 
 def test_config2_benes_bernoulli_full_size():
     """Benes--Bernoulli N = 15, T = 1000, B = 4096, central, TME-3 (BASELINE configs[1])."""
     N, T, B = 15, 1000, 4096
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-    _, c, _, mu, _ = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
-    ys, _ = synth.benes_bernoulli_batch(B, T, dt, seed=100)
-    m, means, nell, fn = filtering.moment_filter_cms(c, mu, pmf, ic.cms, ic.mean, ys, return_first_nan=True)
-    _check_poison_structure(m, means, nell, fn, T)
+    model = benes(N)
+    ys, _ = synth.benes_bernoulli_batch(B, T, model.dt, seed=100)
+    m, means, _, nell, fn = run_device('central', model, ys, return_first_nan=True)
+    assert_poisoned_after(m, means, nell, fn)
     live = np.where(fn >= 0, fn, T)
     assert 0.3 < live.sum() / (B * T) < 0.9          # a large share survives, a large share poisons (SURVEY hard part 3)
     # normalisation invariants on live steps: cms[0] = 1, cms[1] = 0 (to rounding), variance > 0
@@ -46,14 +35,13 @@ def test_config2_benes_bernoulli_full_size():
     assert np.all(m[..., 2][ok] > 0)
     # replicate-order invariance, bit for bit
     perm = np.random.default_rng(0).permutation(B)[:257]
-    m2, means2, nell2 = filtering.moment_filter_cms(c, mu, pmf, ic.cms, ic.mean, ys[perm])
+    m2, means2, _, nell2, _ = run_device('central', model, ys[perm])
     npt.assert_array_equal(nell2, nell[perm])
     npt.assert_array_equal(means2, means[perm])
     # survivors against the C port of the oracle on a sample of replicates
     nb = 192
-    odt, _, oic, odrift, odisp, _, _ = om.benes_bernoulli(N)
-    tab = tme_sympy.operator_tables_1d(odrift, odisp, odt, 3, 'tanh')
-    _, cmeans, _, cnell = c_oracle.filter_1d(1, N, ys[:nb], oic.cms, oic.mean, None, 0, 1, 6, tab, 1.0, 0,
+    oic = model.oic
+    _, cmeans, _, cnell = c_oracle.filter_1d(1, N, ys[:nb], oic.cms, oic.mean, None, 0, 1, 6, benes_operator_tables(N), 1.0, 0,
                                              np.array([0., 0., 0., 0.2]), want_moments=False)
     both = np.isfinite(cnell) & np.isfinite(nell[:nb])
     assert both.sum() > nb // 5
@@ -69,8 +57,6 @@ def test_config2_benes_bernoulli_full_size():
     assert abs(np.mean(c_first) - np.mean(live[:nb])) < 0.1 * T
     # the worst replicates of THIS batch (largest device-vs-C-port deviations, tools/select_tails.py) against their
     # exact-arithmetic trajectories: the device within 1e-6 on every quantity at every finite step
-    import os
-    from oracle import parity
     e = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'filter_cfg2_exact_tails.npz'))
     idx = e['central_idx']
     assert np.array_equal(np.packbits(ys[idx].astype(np.uint8), axis=1), e['central_ys_bits'])
@@ -82,19 +68,17 @@ def test_config2_benes_bernoulli_full_size():
 def test_config3_convergence_sweep_full_size(N):
     """OU / Gaussian, T = 1000, B = 1024, central, against the exact Kalman filter (BASELINE configs[2])."""
     T, B = 1000, 1024
-    mdl = om.ou_gaussian(N)
-    F, Sigma = mdl['F'], mdl['Sigma']
+    mdl = ou_gaussian(N)
+    F, Sigma = mdl.F, mdl.Sigma
     ys, _ = synth.ou_gaussian_batch(B, T, seed=7)
-    _, cond_cms, _, cond_mean, _ = moments.sde_cond_moments_normal(lambda x: F * x, lambda x: Sigma)
-    m, means, nell, fn = filtering.moment_filter_cms(cond_cms, cond_mean, lambda y, x: stats.norm_pdf(y, x, 1.),
-                                                     mdl['cms0'], mdl['mean0'], ys, return_first_nan=True)
+    m, means, _, nell, fn = run_device('central', mdl, ys, return_first_nan=True)
     alive = fn < 0
     # cond(Hankel) reaches ~1e20 at N = 25: whether a Cholesky pivot rounds below zero within 2000 factorisations is
     # summation-order luck (measured over 256 replicates: fast path 65 % alive, dense device path 43 %, C port 45 %;
     # the NumPy/LAPACK oracle survives some replicates the others lose).  N <= 15 never poisons here.
     assert alive.mean() >= {5: 1.0, 10: 1.0, 15: 1.0, 20: 0.99, 25: 0.5}[N]
     # vectorised exact Kalman filter over the batch
-    mf, vf, knell = np.zeros(B), np.full(B, mdl['var0']), np.zeros(B)
+    mf, vf, knell = np.zeros(B), np.full(B, mdl.var0), np.zeros(B)
     kmeans, kvars = np.empty((B, T)), np.empty((B, T))
     for k in range(T):
         mp, vp = F * mf, F * vf * F + Sigma
@@ -119,27 +103,25 @@ def test_config4_nll_grid_per_replicate_theta():
     """Well--Poisson NLL grid (BASELINE configs[3], per-GPU shard shape scaled down): theta per replicate, NLL only.
     Grid points sharing a theta give identical NLLs; the C port agrees on a sample."""
     N, T = 7, 1000
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.well_poisson(3., N)
     g1, g2 = np.meshgrid(np.linspace(0.5, 6., 32), np.linspace(0.5, 6., 16), indexing='ij')
     keys = 4
     p1 = np.tile(g1.ravel(), keys)
     p2 = np.tile(g2.ravel(), keys)
     B = p1.shape[0]
-    ys_k, _ = synth.well_poisson_batch(keys, T, p1=3., p2=3., dt=dt, seed=5)
+    grid = well(N, tuple(p1), 'tme_normal', 2, tuple(p2))
+    ys_k, _ = synth.well_poisson_batch(keys, T, p1=3., p2=3., dt=grid.dt, seed=5)
     ys = np.repeat(ys_k, g1.size, axis=0)
-    _, c, _, mu, _ = moments.sde_cond_moments_tme_normal(lambda x: drift(x, p1), dispersion, dt, 2, N)
-    m, means, nell, fn = filtering.moment_filter_cms(c, mu, lambda y, x: pmf(y, x, p2), ic.cms, ic.mean, ys,
-                                                     return_first_nan=True)
+    m, means, _, nell, fn = run_device('central', grid, ys, return_first_nan=True)
     assert np.isfinite(nell).mean() > 0.5
     # duplicate the first 64 grid points at the end of the batch: same theta, same data -> same NLL, bit for bit
     idx = np.arange(64)
-    _, c2, _, mu2, _ = moments.sde_cond_moments_tme_normal(lambda x: drift(x, p1[idx]), dispersion, dt, 2, N)
-    _, _, nell2 = filtering.moment_filter_cms(c2, mu2, lambda y, x: pmf(y, x, p2[idx]), ic.cms, ic.mean, ys[idx])
+    head = well(N, tuple(p1[idx]), 'tme_normal', 2, tuple(p2[idx]))
+    nell2 = run_device('central', head, ys[idx]).nell
     npt.assert_array_equal(nell2, nell[idx])
     # the C port on a sample (tables from the product here: the SymPy route is checked in test_abi_and_host.py)
-    tables, lik = filtering.trace_model('central', c2, mu2, lambda y, x: pmf(y, x, p2[idx]))
+    tables, lik = filtering.trace_model('central', head.fns[1], head.fns[3], head.pmf)
     coef, _ = tables.table(64)
-    _, _, _, cnell = c_oracle.filter_1d(1, N, ys[idx], ic.cms, ic.mean, None, 1, 0, 0, coef, tables.mean_x_coef, 1,
+    _, _, _, cnell = c_oracle.filter_1d(1, N, ys[idx], head.ic.cms, head.ic.mean, None, 1, 0, 0, coef, tables.mean_x_coef, 1,
                                         lik.params, want_moments=False)
     both = np.isfinite(cnell) & np.isfinite(nell2)
     assert both.sum() >= 32
@@ -155,14 +137,8 @@ def test_config5_length_nd_modes_agree():
     """BASELINE config 5 at full length (d = 2, N = 6, T = 500) on a slice of the batch: no oracle can follow 500 steps
     of it in test time, so the size-independent property is the reference's own one (tests/test_filtering.py:168-242):
     the central and the scaled-central filters carry the same means and NLL."""
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
     N, T, B = 6, 500, 48
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
-    dt, _, _, gs, drift, disp, _, pmf, _ = snd.prey_predator(mi)
-    fns = mnd.sde_cond_moments_tme(drift, disp, dt, 2)
+    mi, inds, dt, gs, fns, _, pmf, _, _ = prey_predator(N, 'tme_2')
     ys, _ = synth.prey_predator_batch(B, T, dt, seed=77)
     cmss, means_c, nell_c, fn = fnd.moment_filter_nd_cms((fns[1], 'multi-index'), fns[3], pmf, ys, (mi, inds), gs.cms,
                                                          gs.mean, return_first_nan=True)

@@ -12,8 +12,7 @@ import numpy as np
 import pytest
 
 from mfs_amd import synth
-from mfs_amd.one_dim import filtering, moments, ss_models
-from oracle import one_dim as o, models as om, tme_sympy
+from tests.one_dim_support import benes, run_device, run_oracle, well
 
 pytestmark = pytest.mark.gpu
 
@@ -62,46 +61,16 @@ def _check(tag, N, mode, gm, gmean, gn, fn_dev, rm, rmean, rn):
 
 
 def _run_case(N, mode, model, trans, T, dseed, p1, B):
+    family, order = ('euler', None) if trans == 'euler' else (trans[:-2], int(trans[-1]))
     if model == 'benes':
-        dt, _, _, ic, drift, disp, _, pmf, _ = ss_models.benes_bernoulli(N)
-        odt, _, oic, odrift, odisp, _, opmf = om.benes_bernoulli(N)
-        ys, _ = synth.benes_bernoulli_batch(B, T, dt, seed=dseed)
+        pair = benes(N, family, order)
+        ys, _ = synth.benes_bernoulli_batch(B, T, pair.dt, seed=dseed)
     else:
-        dt, _, _, ic, drift0, disp, _, pmf0, _ = ss_models.well_poisson(p1, N)
-        odt, _, oic, odrift0, odisp, _, opmf0 = om.well_poisson(N)
-        drift, pmf = (lambda x, p=p1: drift0(x, p)), (lambda y, x: pmf0(y, x, 3.))
-        odrift, opmf = (lambda x, p=p1: odrift0(x, p)), (lambda y, x: opmf0(y, x, 3.))
-        ys, _ = synth.well_poisson_batch(B, T, p1=p1, p2=3., dt=dt, seed=dseed)
-    if trans == 'euler':
-        dev = moments.sde_cond_moments_euler(drift, disp, dt, N)
-        ora = tme_sympy.sde_cond_moments_euler_1d(odrift, odisp, odt, N)
-    elif trans.startswith('tme_normal'):
-        order = int(trans[-1])
-        dev = moments.sde_cond_moments_tme_normal(drift, disp, dt, order, N)
-        ora = tme_sympy.sde_cond_moments_tme_normal_1d(odrift, odisp, odt, order, N)
-    else:
-        order = int(trans[-1])
-        dev = moments.sde_cond_moments_tme(drift, disp, dt, order)
-        ora = tme_sympy.sde_cond_moments_tme_1d(odrift, odisp, odt, order, 2 * N)
+        pair = well(N, p1, family, order)
+        ys, _ = synth.well_poisson_batch(B, T, p1=p1, p2=3., dt=pair.dt, seed=dseed)
     tag = f'N={N} {mode} {model} {trans} T={T}'
-    if mode == 'raw':
-        gm, gn, fn_dev = filtering.moment_filter_rms(dev[0], pmf, ic.rms, ys, return_first_nan=True)
-        ref = [o.moment_filter_rms(ora[0], opmf, oic.rms, ys[b]) for b in range(B)]
-        rn, gmean, rmean = np.array([r[1] for r in ref]), None, None
-        rm = np.stack([r[0] for r in ref])
-    elif mode == 'central':
-        gm, gmean, gn, fn_dev = filtering.moment_filter_cms(dev[1], dev[3], pmf, ic.cms, ic.mean, ys, return_first_nan=True)
-        ref = [o.moment_filter_cms(ora[1], ora[3], opmf, oic.cms, oic.mean, ys[b]) for b in range(B)]
-        rn, rmean = np.array([r[2] for r in ref]), np.stack([r[1] for r in ref])
-        rm = np.stack([r[0] for r in ref])
-    else:
-        sc0 = np.sqrt(ic.variance)
-        gm, gmean, _, gn, fn_dev = filtering.moment_filter_scms(dev[2], dev[4], pmf, ic.scms, ic.mean, sc0, ys,
-                                                                return_first_nan=True)
-        ref = [o.moment_filter_scms(ora[2], ora[4], opmf, oic.scms, oic.mean, sc0, ys[b]) for b in range(B)]
-        rn, rmean = np.array([r[3] for r in ref]), np.stack([r[1] for r in ref])
-        rm = np.stack([r[0] for r in ref])
-    _check(tag, N, mode, gm, gmean, gn, fn_dev, rm, rmean, rn)
+    got, ref = run_device(mode, pair, ys, return_first_nan=True), run_oracle(mode, pair, ys)
+    _check(tag, N, mode, got.moments, got.means, got.nell, got.first_nan, ref.moments, ref.means, ref.nell)
 
 
 @pytest.mark.parametrize('seed', [11, 12, 13])
@@ -121,5 +90,3 @@ def test_known_one_sided_poisonings(case):
     """Replicate 2 of each: the device's pivot rounds below zero at a step where the oracle's own posterior Hankel matrix
     has cond 4e16 (N = 9, step 46) / 1e17 (N = 12, step 8-9); means, scales and even moments agree to 1e-13 up to there."""
     _run_case(**case)
-
-

@@ -8,26 +8,22 @@ ill-posed in fp64 (config 2: N = 15, cond(Hankel) up to 1e16) the 1e-6 bar is as
 both implementations, and the divergence statistics are asserted separately; tests/test_gpu_envelope.py scores both
 against exact arithmetic.
 """
-import math
-import os
-
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import synth, stats
-from mfs_amd.one_dim import filtering, moments, ss_models
+from mfs_amd import synth
+from mfs_amd.multi_dims import filtering as fnd
+from mfs_amd.utils import GaussianSum1D
 from oracle import parity
+from tests.nd_envelope_models import prey_predator
+from tests.one_dim_support import RTOL, benes, load_golden, ou_gaussian, run_device, start_of, well
 
 pytestmark = pytest.mark.gpu
-RTOL = 1e-6
 
 
 def _load(golden_dir, name):
-    path = os.path.join(golden_dir, name)
-    if not os.path.exists(path):
-        pytest.fail(f'{name} is missing: run tests/golden/make_filter_golden.py')
-    return np.load(path)
+    return load_golden(golden_dir, name, 'run tests/golden/make_filter_golden.py')
 
 
 def _unpack(bits, T):
@@ -43,18 +39,17 @@ def test_config1_benes_N7_three_modes(golden_dir):
     """BASELINE configs[0]: N = 7, T = 100, TME-3, raw / central / scaled."""
     g = _load(golden_dir, 'filter_cfg1.npz')
     N, T, B = int(g['N']), int(g['T']), int(g['B'])
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
+    model = benes(N)
     ys = _unpack(g['ys_bits'], T)
-    npt.assert_array_equal(ys, synth.benes_bernoulli_batch(B, T, dt, seed=int(g['seed']))[0])   # fixture == generator
-    f = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
-    m, nell = filtering.moment_filter_rms(f[0], pmf, ic.rms, ys)
+    npt.assert_array_equal(ys, synth.benes_bernoulli_batch(B, T, model.dt, seed=int(g['seed']))[0])   # fixture == generator
+    m, _, _, nell, _ = run_device('raw', model, ys)
     npt.assert_allclose(nell, g['raw_nell'], rtol=RTOL)
     assert _scaled_moment_error(m, g['raw_moments']).max() <= RTOL
-    m, means, nell = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys)
+    m, means, _, nell, _ = run_device('central', model, ys)
     npt.assert_allclose(nell, g['central_nell'], rtol=RTOL)
     npt.assert_allclose(means, g['central_means'], rtol=RTOL, atol=1e-9)
     assert _scaled_moment_error(m, g['central_moments']).max() <= RTOL
-    m, means, scales, nell = filtering.moment_filter_scms(f[2], f[4], pmf, ic.scms, ic.mean, math.sqrt(ic.variance), ys)
+    m, means, scales, nell, _ = run_device('scaled', model, ys)
     npt.assert_allclose(nell, g['scaled_nell'], rtol=RTOL)
     npt.assert_allclose(means, g['scaled_means'], rtol=RTOL, atol=1e-9)
     npt.assert_allclose(scales, g['scaled_scales'], rtol=RTOL)
@@ -72,17 +67,14 @@ def test_config2_headline_N15_T300_B64(golden_dir, mode):
     tests/test_gpu_envelope.py against exact arithmetic."""
     g = _load(golden_dir, 'filter_cfg2.npz')
     N, T, B = int(g['N']), int(g['T']), int(g['B'])
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
+    model = benes(N)
     ys = _unpack(g['ys_bits'], T)
-    full = synth.benes_bernoulli_batch(int(g['batch_B']), int(g['batch_T']), dt, seed=int(g['seed']))[0]
+    full = synth.benes_bernoulli_batch(int(g['batch_B']), int(g['batch_T']), model.dt, seed=int(g['seed']))[0]
     npt.assert_array_equal(ys, full[:B, :T])
-    f = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
+    m, means, second, nell, fn = run_device(mode, model, ys, return_first_nan=True)
     if mode == 'central':
-        m, means, nell, fn = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys, return_first_nan=True)
         second, ref_second = m[..., 2], g['central_variances']
     else:
-        m, means, second, nell, fn = filtering.moment_filter_scms(f[2], f[4], pmf, ic.scms, ic.mean,
-                                                                  math.sqrt(ic.variance), ys, return_first_nan=True)
         ref_second = g['scaled_scales']
     gfn = g[f'{mode}_first_nan']
     steps = g['moment_steps']
@@ -150,12 +142,9 @@ def test_config3_ou_convergence(golden_dir, N):
     T, B = int(g['T']), int(g['B'])
     ys = g['ys']
     npt.assert_array_equal(ys, synth.ou_gaussian_batch(B, T, seed=int(g['seed']))[0])
-    dt_ou, ell, sigma = 0.1, 1., 0.5
-    F, Sigma = math.exp(-dt_ou / ell), sigma ** 2 * (1 - math.exp(-2 * dt_ou / ell))
-    from mfs_amd.utils import GaussianSum1D
-    ic = GaussianSum1D.new(means=[0.], variances=[sigma ** 2], weights=[1.], N=N)
-    f = moments.sde_cond_moments_normal(lambda x: F * x, lambda x: Sigma)
-    m, means, nell = filtering.moment_filter_cms(f[1], f[3], lambda y, x: stats.norm_pdf(y, x, 1.), ic.cms, ic.mean, ys)
+    model = ou_gaussian(N)
+    ic = GaussianSum1D.new(means=[0.], variances=[model.var0], weights=[1.], N=N)      # the product's own moments of N(0, var0)
+    m, means, _, nell, _ = run_device('central', model, ys, start=start_of(ic))
     ok = np.isfinite(g[f'N{N}_nell'])
     assert ok.all() or N >= 20          # (raw mode would diverge at N >= 20; central survives these 200 steps)
     npt.assert_allclose(nell[ok], g[f'N{N}_nell'][ok], rtol=RTOL)
@@ -173,13 +162,11 @@ def test_config4_well_poisson_theta_grid(golden_dir):
     g = _load(golden_dir, 'filter_cfg4.npz')
     N, T, keys = int(g['N']), int(g['T']), int(g['keys'])
     p1, p2 = g['p1'], g['p2']
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.well_poisson(3., N)
+    model = well(N, tuple(p1), 'tme_normal', 2, tuple(p2))
     ys_k = g['ys_keys'].astype(np.float64)
-    npt.assert_array_equal(ys_k, synth.well_poisson_batch(keys, T, p1=3., p2=3., dt=dt, seed=int(g['seed']))[0])
+    npt.assert_array_equal(ys_k, synth.well_poisson_batch(keys, T, p1=3., p2=3., dt=model.dt, seed=int(g['seed']))[0])
     ys = np.repeat(ys_k, p1.shape[0] // keys, axis=0)
-    f = moments.sde_cond_moments_tme_normal(lambda x: drift(x, p1), dispersion, dt, 2, N)
-    m, means, nell, fn = filtering.moment_filter_cms(f[1], f[3], lambda y, x: pmf(y, x, p2), ic.cms, ic.mean, ys,
-                                                     return_first_nan=True)
+    m, means, _, nell, fn = run_device('central', model, ys, return_first_nan=True)
     gfn = g['central_first_nan']
     npt.assert_array_equal(fn < 0, gfn < 0)                   # N = 7: well-posed, the same replicates survive
     ok = gfn < 0
@@ -194,14 +181,9 @@ def test_config5_prey_predator_N6_T500(golden_dir):
     """BASELINE configs[4] at its own order and length: d = 2, N = 6 (z = 78, s = 21), T = 500, B = 4, central, TME-2
     ('multi-index'), and the TME-normal-2 closure ('index') on T = 100, B = 2.  1e-6 on NLL, means, variances and on
     EVERY moment (scaled by its natural magnitude prod_k sd_k^n_k where it is rounding noise around zero)."""
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
     g = _load(golden_dir, 'filter_cfg5.npz')
     N, T, B = int(g['N']), int(g['T']), int(g['B'])
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
-    dt, _, _, gs, drift, disp, _, pmf, _ = snd.prey_predator(mi)
+    mi, inds, dt, gs, f, _, pmf, _, _ = prey_predator(N, 'tme_2')
     ys = _unpack(g['ys_bits'], T)
     npt.assert_array_equal(ys, synth.prey_predator_batch(B, T, dt, seed=int(g['seed']))[0])
     deg = mi.sum(axis=1)
@@ -211,7 +193,6 @@ def test_config5_prey_predator_N6_T500(golden_dir):
         natural = np.prod(sd[..., None, :] ** mi, axis=-1)
         return (np.abs(got - ref) / np.maximum(np.abs(ref), 1e-2 * natural + 1e-300))[..., deg >= 2]
 
-    f = mnd.sde_cond_moments_tme(drift, disp, dt, 2)
     m, means, nell, fn = fnd.moment_filter_nd_cms((f[1], 'multi-index'), f[3], pmf, ys, (mi, inds), gs.cms, gs.mean,
                                                   return_first_nan=True)
     assert np.all(fn == -1)
@@ -224,7 +205,7 @@ def test_config5_prey_predator_N6_T500(golden_dir):
     print('tme_2: max scaled moment error over T = 500:', e.max())
     assert e.max() <= RTOL
     Tn, Bn = int(g['normal_T']), int(g['normal_B'])
-    fnn = mnd.sde_cond_moments_tme_normal(drift, disp, dt, 2, mi)
+    fnn = prey_predator(N, 'tme_normal_2').fns
     m, means, nell = fnd.moment_filter_nd_cms((fnn[1], 'index'), fnn[3], pmf, ys[:Bn, :Tn], (mi, inds), gs.cms, gs.mean)
     npt.assert_allclose(nell, g['normal2_nell'], rtol=RTOL)
     npt.assert_allclose(means, g['normal2_means'], rtol=RTOL)

@@ -10,8 +10,10 @@ import numpy.testing as npt
 import pytest
 
 from mfs_amd import estimation, stats, sym, synth
+from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
+from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, gram_and_hankel_indices_graded_lexico
 from mfs_amd.one_dim import filtering, moments, ss_models
-from oracle import one_dim as o, models as om, tme_sympy
+from oracle import multi_dims as omd, one_dim as o, models as om, tme_sympy
 
 pytestmark = pytest.mark.gpu
 
@@ -202,10 +204,6 @@ def test_nd_parameter_gradient_by_differences_in_one_launch():
     upstream, dardel/parameter_estimation/mf.py:37-54 carried to the N-D filter) from ONE launch of 2P + 1 filters with
     per-replicate tables (`batch_closures`, `coef_batched` / `lik_batched` of the N-D model).  theta = (dispersion scale,
     logistic offset) of the prey--predator model at N = 3; checked against central differences of the NumPy oracle's NLL."""
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
-    from oracle import multi_dims as omd
     N, T = 3, 40
     mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
     inds = gram_and_hankel_indices_graded_lexico(N, 2)

@@ -12,6 +12,7 @@ import math
 import numpy as np
 import pytest
 
+from tests.one_dim_support import assert_poisoned_from
 from tests.plan_api import (COMBOS, MID_RUN, MID_RUN_B, assert_same_bits, bernoulli_ys, combo_model, one_wave_build,
                             partner_inputs as _inputs, partner_variant as _partner)
 
@@ -34,17 +35,6 @@ def _one_wave(monkeypatch, key, combo, N, ys, m0):
     return _REFERENCES[key]
 
 
-def _assert_poison_structure(out, nt):
-    """Nothing before first_nan is NaN, everything from first_nan on is: moments and means (the NLL of a poisoned one is NaN)."""
-    moments, means, _, nell, first_nan = out
-    for b in range(means.shape[0]):
-        f = first_nan[b] if first_nan[b] >= 0 else nt
-        assert np.isfinite(means[b, :f]).all() and np.isnan(means[b, f:]).all(), (b, f)
-        if moments is not None:
-            assert np.isfinite(moments[b, :f]).all() and np.isnan(moments[b, f:]).all(), (b, f)
-        assert np.isnan(nell[b]) == (f < nt), (b, f)
-
-
 # ---- 1. window edges: launches that end inside the first window, on its last step, on and just behind a window start; the
 # guard of the window load meets t_end in the first, second, third and fourth window.  B = 5: a partial wave and three pairs of
 # waves without filters; B = 17: a second workgroup.  Replicate 1 is poisoned at step 0, so its flag is acted on in step 1.
@@ -56,7 +46,7 @@ def test_window_edges(combo, N, B, monkeypatch):
         variant = _partner(monkeypatch, combo, N, ys, m0)
         assert_same_bits(variant, _one_wave(monkeypatch, ('window', combo, N, B, nt), combo, N, ys, m0))
         assert variant.first_nan[1] == 0 and (np.delete(variant.first_nan, 1) != 0).all()
-        _assert_poison_structure(variant, nt)
+        assert_poisoned_from(variant.moments, variant.means, variant.nell, variant.first_nan)
 
 
 # ---- 2. chunk edges: windows are counted from the start of a launch, so with chunks of 1, 7, 16 and 17 steps window starts
@@ -104,7 +94,7 @@ def test_late_flag_mid_run(N, monkeypatch):
     nt, ys, m0, reference = _mid_run(N, monkeypatch)
     variant = _partner(monkeypatch, 'benes_tme3', N, ys, m0)
     np.testing.assert_array_equal(variant.first_nan, reference.first_nan)      # neither a step early nor a step late
-    _assert_poison_structure(variant, nt)
+    assert_poisoned_from(variant.moments, variant.means, variant.nell, variant.first_nan)
     assert_same_bits(variant, reference)
     assert_same_bits(_partner(monkeypatch, 'benes_tme3', N, ys, m0, moments_out=False)[1:], reference[1:])
 
@@ -115,7 +105,7 @@ def test_late_flag_at_chunk_edges(N, monkeypatch):
     for p in sorted({int(p) for p in reference.first_nan if p >= 0}):
         for chunk in (p + 1, p):      # p = chunk - 1: the last step of the first launch; p = chunk: the first step of the second
             out = _partner(monkeypatch, 'benes_tme3', N, ys, m0, chunk=chunk)
-            _assert_poison_structure(out, nt)
+            assert_poisoned_from(out.moments, out.means, out.nell, out.first_nan)
             assert_same_bits(out, reference)
 
 

@@ -4,9 +4,10 @@ import numpy as np
 import numpy.testing as npt
 import pytest
 
-from mfs_amd import io as mio, synth
+from mfs_amd import estimation, io as mio, synth
 from mfs_amd.one_dim import filtering, moments, ss_models
 from oracle import one_dim as o
+from tests.one_dim_support import benes, run_device
 
 pytestmark = pytest.mark.gpu
 
@@ -34,10 +35,8 @@ def test_characteristic_fn_matches_oracle_and_closed_form(N):
 def test_post_processing_pipeline_on_filter_outputs(tmp_path):
     """dardel/benes_bernoulli/post_processing_mf.py:37-60 on this build's outputs: filter -> npz -> characteristic fn."""
     N, T, B = 7, 40, 3
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-    _, c, _, mu, _ = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
-    ys, _ = synth.benes_bernoulli_batch(B, T, dt, seed=4)
-    cmss, means, nell = filtering.moment_filter_cms(c, mu, pmf, ic.cms, ic.mean, ys)
+    ys, _ = synth.benes_bernoulli_batch(B, T, benes(N).dt, seed=4)
+    cmss, means, _, nell, _ = run_device('central', benes(N), ys)
     assert mio.save_batch(str(tmp_path), 'central', N, (cmss, means, nell)) == B
     zs = np.linspace(-2, 2, 64)
     for k in range(B):
@@ -58,7 +57,6 @@ def test_parameter_estimation_with_in_launch_gradients():
     `measurement_cond_pmf(y, x, p2)` exactly as upstream; the optimiser gets nell and a central-difference gradient from
     one batched launch (2P + 1 filters).  The reference's stored run (examples/parameter_estimation.ipynb cell 8) learnt
     [2.56, 3.36] from one T = 1000 data set generated at (3, 3); the same experiment here must land near the truth."""
-    from mfs_amd import estimation
     N, T = 5, 1000
     dt, _, _, ic, drift, dispersion, emission, pmf, _ = ss_models.well_poisson(3., N)
     ys, _ = synth.well_poisson_batch(1, T, p1=3., p2=3., dt=dt, seed=12)

@@ -6,103 +6,77 @@ mfs/multi_dims/filtering.py) on the device against `oracle.moment_filter_*(..., 
     completion (R = L diag(d < 0 ? eps : sqrt(d)), eps = 1e-8 ||G||_F, :525-538): stable=False poisons at step 0,
     stable=True runs on and matches the oracle.
 """
-import math
+import os
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
 from mfs_amd import synth
-from mfs_amd.one_dim import filtering, moments, ss_models
-from oracle import one_dim as o, models as om, tme_sympy, parity
+from mfs_amd.multi_dims import filtering as fnd
+from oracle import multi_dims as omd, one_dim as o, parity
+from tests.nd_envelope_models import prey_predator, prey_predator_oracle
+from tests.one_dim_support import MODES, benes, run_device, run_oracle
 
 pytestmark = pytest.mark.gpu
 
 
-def _benes(N, order=2):
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-    odt, _, oic, odrift, odisp, _, opmf = om.benes_bernoulli(N)
-    dev = moments.sde_cond_moments_tme(drift, dispersion, dt, order)
-    ora = tme_sympy.sde_cond_moments_tme_1d(odrift, odisp, odt, order, 2 * N)
-    return dt, ic, pmf, dev, oic, opmf, ora
-
-
-@pytest.mark.parametrize('mode', ['raw', 'central', 'scaled'])
+@pytest.mark.parametrize('mode', MODES)
 def test_1d_stable_filter_matches_oracle_and_plain_filter(mode):
     N, T, B = 5, 60, 3
-    dt, ic, pmf, dev, oic, opmf, ora = _benes(N)
-    ys, _ = synth.benes_bernoulli_batch(B, T, dt, seed=11)
-    s0 = math.sqrt(ic.variance)
-    if mode == 'raw':
-        run = lambda st: filtering.moment_filter_rms(dev[0], pmf, ic.rms, ys, stable=st)          # noqa: E731
-        ref = [o.moment_filter_rms(ora[0], opmf, oic.rms, y, stable=True) for y in ys]
-    elif mode == 'central':
-        run = lambda st: filtering.moment_filter_cms(dev[1], dev[3], pmf, ic.cms, ic.mean, ys, stable=st)   # noqa: E731
-        ref = [o.moment_filter_cms(ora[1], ora[3], opmf, oic.cms, oic.mean, y, stable=True) for y in ys]
-    else:
-        run = lambda st: filtering.moment_filter_scms(dev[2], dev[4], pmf, ic.scms, ic.mean, s0, ys, stable=st)   # noqa: E731
-        ref = [o.moment_filter_scms(ora[2], ora[4], opmf, oic.scms, oic.mean, s0, y, stable=True) for y in ys]
-    got, plain = run(True), run(False)
+    model = benes(N, 'tme', 2)
+    ys, _ = synth.benes_bernoulli_batch(B, T, model.dt, seed=11)
+    ref = run_oracle(mode, model, ys, stable=True)
+    got, plain = run_device(mode, model, ys, stable=True), run_device(mode, model, ys, stable=False)
     for b in range(B):
-        npt.assert_allclose(got[-1][b], ref[b][-1], rtol=1e-6)
-        assert parity.rel_err(got[0][b], ref[b][0], parity.moment_floor(ref[b][0])).max() <= 1e-6
-        for k in range(1, len(got) - 1):
-            npt.assert_allclose(got[k][b], ref[b][k], rtol=1e-6, atol=1e-9)
+        npt.assert_allclose(got.nell[b], ref.nell[b], rtol=1e-6)
+        assert parity.rel_err(got.moments[b], ref.moments[b], parity.moment_floor(ref.moments[b])).max() <= 1e-6
+        for e, r in zip(got[1:3], ref[1:3]):
+            if e is not None:
+                npt.assert_allclose(e[b], r[b], rtol=1e-6, atol=1e-9)
     # Cholesky == completed LDL^T on positive definite input (reference tests/test_utils.py:198-209, at filter level)
-    npt.assert_allclose(got[-1], plain[-1], rtol=1e-9)
-    assert parity.rel_err(got[0], plain[0], parity.moment_floor(plain[0])).max() <= 1e-7
+    npt.assert_allclose(got.nell, plain.nell, rtol=1e-9)
+    assert parity.rel_err(got.moments, plain.moments, parity.moment_floor(plain.moments)).max() <= 1e-7
 
 
 def test_1d_stable_completes_an_indefinite_start():
     """cms0 with E[(x - m)^4] < E[(x - m)^2]^2: the 3 x 3 Hankel matrix has LDL^T pivots (1, 0.3, < 0)."""
     N, T = 3, 40
-    dt, ic, pmf, dev, oic, opmf, ora = _benes(N)
+    model = benes(N, 'tme', 2)
     cms0 = np.array([1., 0., 0.3, 0.01, 0.05, 0.002])      # 0.05 < 0.3^2: not a moment sequence
+    start = model.start._replace(cms=cms0, mean=0.1)
     G = cms0[np.add.outer(np.arange(N), np.arange(N))]
     _, dpiv = o.ldl(G)
     assert dpiv.min() < 0.                                   # the completion branch is taken at the first rule
-    ys, _ = synth.benes_bernoulli_batch(2, T, dt, seed=2)
-    m, means, nell, fn = filtering.moment_filter_cms(dev[1], dev[3], pmf, cms0, 0.1, ys, stable=True, return_first_nan=True)
+    ys, _ = synth.benes_bernoulli_batch(2, T, model.dt, seed=2)
+    m, means, _, nell, fn = run_device('central', model, ys, start=start, stable=True, return_first_nan=True)
     compared = 0
     for b in range(2):
-        r = o.moment_filter_cms(ora[1], ora[3], opmf, cms0, 0.1, ys[b], stable=True)
+        r = run_oracle('central', model, ys[b:b + 1], start=start, stable=True)
         # A completed rule carries a node at ~1e13 with a negligible weight: from then on the filter effectively runs on
         # N - 1 atoms, the next Hankel matrix is singular to rounding, and whether its last pivot lands at -1e-17 (completed
         # again), +1e-17 or exactly 0 (singular solve: NaN in-band) is rounding luck on either side.  What the filter
         # delivers in that regime is the NLL, the mean and the variance; the top moments are ~1e26 noise.
-        if not np.isfinite(r[2]):
+        if not np.isfinite(r.nell[0]):
             continue
         compared += 1
         assert fn[b] == -1
-        npt.assert_allclose(nell[b], r[2], rtol=1e-6)
-        npt.assert_allclose(means[b], r[1], rtol=1e-6, atol=1e-9)
-        npt.assert_allclose(m[b, :, 2], r[0][:, 2], rtol=1e-6)
-        npt.assert_allclose(m[b, 3:, 3], r[0][3:, 3], rtol=1e-5, atol=1e-9)
+        npt.assert_allclose(nell[b], r.nell[0], rtol=1e-6)
+        npt.assert_allclose(means[b], r.means[0], rtol=1e-6, atol=1e-9)
+        npt.assert_allclose(m[b, :, 2], r.moments[0][:, 2], rtol=1e-6)
+        npt.assert_allclose(m[b, 3:, 3], r.moments[0][3:, 3], rtol=1e-5, atol=1e-9)
     assert compared >= 1
     # without the completion the same start poisons at once, as the reference's Cholesky does
-    _, _, nell0, fn0 = filtering.moment_filter_cms(dev[1], dev[3], pmf, cms0, 0.1, ys, stable=False, return_first_nan=True)
+    _, _, _, nell0, fn0 = run_device('central', model, ys, start=start, stable=False, return_first_nan=True)
     assert np.all(fn0 == 0) and np.all(np.isnan(nell0))
-    r0 = o.moment_filter_cms(ora[1], ora[3], opmf, cms0, 0.1, ys[0], stable=False)
-    assert np.isnan(r0[2])
+    assert np.isnan(run_oracle('central', model, ys[:1], start=start, stable=False).nell[0])
 
 
 @pytest.mark.parametrize('family', ['tme_2', 'tme_normal_2'])
 def test_nd_stable_filter(family):
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
-    from oracle import multi_dims as omd
     N, T, B = 3, 40, 2
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
-    dt, _, _, gs, drift, disp, _, pmf, _ = snd.prey_predator(mi)
-    _, _, ogs, odrift, odisp, _, opmf = omd.prey_predator(mi)
-    if family == 'tme_2':
-        fns, sig = mnd.sde_cond_moments_tme(drift, disp, dt, 2), 'multi-index'
-        _, ocms, omean, _ = tme_sympy.sde_cond_moments_tme_nd(odrift, odisp, 2, dt, 2, mi)
-    else:
-        fns, sig = mnd.sde_cond_moments_tme_normal(drift, disp, dt, 2, mi), 'index'
-        _, ocms, omean = tme_sympy.sde_cond_moments_normal_nd(odrift, odisp, 2, dt, 2, mi)
+    mi, inds, dt, gs, fns, sig, pmf, ogs, opmf = prey_predator(N, family)
+    ocms, omean = prey_predator_oracle(N, family)
     ys, _ = synth.prey_predator_batch(B, T, dt, seed=9)
     # well-posed start: completion == Cholesky
     cs, ms, ns = fnd.moment_filter_nd_cms((fns[1], sig), fns[3], pmf, ys, (mi, inds), gs.cms, gs.mean, stable=True)
@@ -141,17 +115,9 @@ def test_nd_stable_register_front_end_against_the_dense_form_and_the_oracle(monk
     and degree 4 by 0.2 (pivot -8e-7: every implementation loses the replicate within five steps).  Compared on the steps
     before any of the three implementations is within two steps of losing the replicate (measured on those steps: register
     form 1e-10 .. 4e-9 from the oracle on the moments, LDS-tile form 2e-9 .. 8e-8)."""
-    from mfs_amd.multi_dims import filtering as fnd, moments as mnd, ss_models as snd
-    from mfs_amd.multi_dims.multi_indices import generate_graded_lexico_multi_indices, \
-        gram_and_hankel_indices_graded_lexico
-    from oracle import multi_dims as omd
     N, T, B = 5, 30, 3
-    mi = generate_graded_lexico_multi_indices(2, 2 * N - 1)
-    inds = gram_and_hankel_indices_graded_lexico(N, 2)
-    dt, _, _, gs, drift, disp, _, pmf, _ = snd.prey_predator(mi)
-    _, _, ogs, odrift, odisp, _, opmf = omd.prey_predator(mi)
-    fns, sig = mnd.sde_cond_moments_tme(drift, disp, dt, 2), 'multi-index'
-    _, ocms, omean, _ = tme_sympy.sde_cond_moments_tme_nd(odrift, odisp, 2, dt, 2, mi)
+    mi, inds, dt, gs, fns, sig, pmf, ogs, opmf = prey_predator(N)
+    ocms, omean = prey_predator_oracle(N)
     ys, _ = synth.prey_predator_batch(B, T, dt, seed=11)
     bad = gs.cms.copy()
     bad[mi.sum(axis=1) == degree] *= shrink
@@ -200,14 +166,12 @@ def test_config2_stable_runs_the_fast_kernel_and_matches_the_oracle_golden():
     amplified by 1 / eps^2; NumPy oracle vs C port: variance 1.8e-4, mean 1e-5 on these replicates): there the NLL is held to
     1e-4, mean and variance to 1e-2; each to 1e-6 on half of those replicates and to 1e-4 on three quarters, and the survivor counts
     must agree."""
-    import os
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'filter_cfg2stable.npz'))
     N, T, B = int(g['N']), int(g['T']), int(g['B'])
     ys = np.unpackbits(g['ys_bits'], axis=1)[:, :T].astype(np.float64)
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
-    f = moments.sde_cond_moments_tme(drift, dispersion, dt, 3)
-    sm, smean, snell, sfn = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys, stable=True, return_first_nan=True)
-    pm, pmean, pnell, pfn = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys, stable=False, return_first_nan=True)
+    model = benes(N, 'tme', 3)
+    sm, smean, _, snell, sfn = run_device('central', model, ys, stable=True, return_first_nan=True)
+    pm, pmean, _, pnell, pfn = run_device('central', model, ys, stable=False, return_first_nan=True)
     first = np.where(pfn >= 0, pfn, T)             # the step of a replicate's first completed rule = where the plain run poisons
     gp = g['central_first_completion']
     ofirst = np.where(gp >= 0, gp, T)              # ... and the step of the ORACLE's first completed rule (its own rounding: the

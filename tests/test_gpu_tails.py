@@ -7,15 +7,14 @@ the largest first-NaN gaps, 36 central + 28 scaled -- and tests/golden/make_exac
 (mfs/one_dim/filtering.py:140-158, :217-237) on them without rounding (oracle/exact_mp.py, 200 digits, 500 where 200 gave out).
 Against those trajectories the device must be within 1e-6 on the mean, the variance / scale, every moment order and the NLL at
 EVERY step at which it is finite.  (The CPU suite scores the C port on the same fixture: it is the side that is off.)"""
-import math
 import os
 
 import numpy as np
 import pytest
 
 from mfs_amd import synth
-from mfs_amd.one_dim import filtering, moments, ss_models
 from oracle import parity
+from tests.one_dim_support import benes, run_device
 
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'filter_cfg2_exact_tails.npz')   # (conftest's golden_dir)
@@ -27,17 +26,13 @@ def test_device_is_within_1e6_of_exact_arithmetic_on_the_worst_replicates_of_the
     N, T = int(e['N']), int(e['T'])
     idx = e[f'{mode}_idx']
     ys = np.unpackbits(e[f'{mode}_ys_bits'], axis=1)[:, :T].astype(np.float64)
-    dt, _, _, ic, drift, dispersion, _, pmf, _ = ss_models.benes_bernoulli(N)
+    model = benes(N, 'tme', int(e['tme_order']))
     # the fixture's measurements are those of the benchmark batch (same generator, same seed)
-    batch = synth.benes_bernoulli_batch(int(e['batch_B']), T, dt, seed=int(e['seed']))[0]
+    batch = synth.benes_bernoulli_batch(int(e['batch_B']), T, model.dt, seed=int(e['seed']))[0]
     assert np.array_equal(batch[idx], ys)
-    f = moments.sde_cond_moments_tme(drift, dispersion, dt, int(e['tme_order']))
+    m, means, second, nell, fn = run_device(mode, model, ys, return_first_nan=True)
     if mode == 'central':
-        m, means, nell, fn = filtering.moment_filter_cms(f[1], f[3], pmf, ic.cms, ic.mean, ys, return_first_nan=True)
         second = m[..., 2]
-    else:
-        m, means, second, nell, fn = filtering.moment_filter_scms(f[2], f[4], pmf, ic.scms, ic.mean, math.sqrt(ic.variance), ys,
-                                                                 return_first_nan=True)
     sc = parity.score_against_exact_tails(e, mode, m, means, second, nell)
     print(mode, 'device vs exact arithmetic, maxima over', sc['replicates'], 'replicates:', sc['max'])
     assert sc['finite_steps'].sum() > 0.5 * len(idx) * T            # (it is a comparison over most of the batch's steps, not a few)

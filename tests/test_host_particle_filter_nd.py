@@ -4,7 +4,7 @@ resampling margin, and the `errs` file layout of dardel/prey_predator/pf.py."""
 import numpy as np
 import pytest
 
-from mfs_amd import io, stats
+from mfs_amd import io, stats, sym
 from mfs_amd.classical_filters_smoothers import (bootstrap_filter, gaussian_transition_nd, stratified, systematic,
                                                  ParticleFilterResultND)
 from mfs_amd.classical_filters_smoothers.gfs import GaussianTransitionND
@@ -88,7 +88,6 @@ def test_argument_errors():
     three = lambda y, x: stats.norm_pdf(y[0], x[0], 1.) * stats.norm_pdf(y[1], x[1], 1.) * stats.norm_pdf(y[0], x[1], 1.)   # noqa: E731
     with pytest.raises(NotDeviceDescribable, match='factors'):
         bootstrap_filter(trans, three, ys, init, 0, 100)
-    from mfs_amd import sym
     bearing = lambda y, x: stats.norm_pdf(y, sym.arctan2(x[1], x[0]), 0.1)   # noqa: E731
     with pytest.raises(ValueError, match='one state component'):
         bootstrap_filter(trans, bearing, np.zeros(5), init, 0, 100)

@@ -1,7 +1,8 @@
 """The import layers of tests/: test modules (test_*.py) share code through plain support modules only (plan_api.py,
-nd_support.py, nd_envelope_models.py, nd3_models.py, the *_ref.py yardsticks, ...), every import is absolute
-(`from tests import x`, `from tests.x import y`), and no support module reaches a test module, directly or through another
-support module.  Every tests/**/*.py is parsed, none is imported: no GPU and no library."""
+one_dim_support.py, nd_support.py, nd_envelope_models.py, nd3_models.py, the *_ref.py yardsticks, ...), every import is
+absolute (`from tests import x`, `from tests.x import y`), no support module reaches a test module, directly or through
+another support module, and the project's own modules (mfs_amd, oracle, tests) are imported at module level, where a reader
+and this file see them.  Every tests/**/*.py is parsed, none is imported: no GPU and no library."""
 import ast
 import glob
 import os
@@ -37,6 +38,21 @@ def _imports(path):
         elif isinstance(node, ast.ImportFrom):
             out += [(node.lineno, node.level, f'{node.module}.{a.name}' if node.module else a.name) for a in node.names]
     return out
+
+
+def _imports_in_functions(path):
+    """-> [(line, dotted name)] of the import statements inside a function body, at any depth."""
+    with open(path) as f:
+        tree = ast.parse(f.read(), path)
+    out = []
+    for fn in ast.walk(tree):
+        if isinstance(fn, (ast.FunctionDef, ast.AsyncFunctionDef, ast.Lambda)):
+            for node in ast.walk(fn):
+                if isinstance(node, ast.Import):
+                    out += [(node.lineno, a.name) for a in node.names]
+                elif isinstance(node, ast.ImportFrom) and node.module:
+                    out += [(node.lineno, node.module)]
+    return sorted(set(out))
 
 
 def _where(path, line):
@@ -78,3 +94,26 @@ def _reached(module, seen):
 def test_support_modules_reach_no_test_module(module):
     reached = _reached(module, set())
     assert not [m for m in reached if _is_test(m)], sorted(reached)
+
+
+# (file under tests/, imported module) -> why this import of a project module stays inside a function
+IN_FUNCTION_IMPORTS = {
+    # The two exact-arithmetic yardsticks, and the golden generator of the second, import with mpmath and NumPy alone;
+    # only the function that hands numbers to the product, or builds the product's host tables, loads it.
+    ('device_math_ref.py', 'mfs_amd'): 'call() is the one function that needs the library',
+    ('gaussian_filters_exact.py', 'mfs_amd'): 'host_tables() builds the product\'s tables',
+    ('gaussian_filters_exact.py', 'mfs_amd.classical_filters_smoothers'): 'the rules come from the product\'s SigmaPoints',
+    ('gaussian_filters_exact.py', 'mfs_amd.tme_poly'): 'host_tables() builds the product\'s tables',
+    ('gaussian_filters_exact.py', 'mfs_amd.tme_poly_nd'): 'host_tables() builds the product\'s tables',
+    ('gaussian_filters_exact.py', 'tests'): 'restatement_of() is the one user of tests/gaussian_filters_ref.py',
+}
+
+
+def test_project_modules_are_imported_at_module_level():
+    found = {(os.path.relpath(p, TESTS), name): line for p in FILES for line, name in _imports_in_functions(p)
+             if name.split('.')[0] in ('mfs_amd', 'oracle', 'tests')}
+    bad = [f'{_where(os.path.join(TESTS, f), line)}: {name}' for (f, name), line in found.items()
+           if (f, name) not in IN_FUNCTION_IMPORTS]
+    assert not bad, bad
+    stale = sorted(set(IN_FUNCTION_IMPORTS) - set(found))
+    assert not stale, f'listed but no longer there: {stale}'
